@@ -14,6 +14,7 @@ on the fp32 MFMA engine is timed in the same run and printed under "fp32_math"; 
 error of BOTH modes against the oracle on the bench's own weights and inputs (rank 0, after the timed region).
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_outputs     # + what the last timed step computed (step_outputs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -268,6 +269,40 @@ def cpu_baseline_fill(shells_cpu, seconds_budget=5.0):
           "sample": f"{n} calls on {shells_cpu.shape[0]} x 128^3 fp32 shells"}
 
 
+DUMP_SAMPLE = 1 << 22        # elements kept of a larger output: 16 MB per array, ~48 MB for everything step_outputs returns
+
+
+def step_outputs(model, plan, loss):
+  """What the last training step computed, as float32 host arrays: its loss, the logits of its forward, the gradient slab
+  of its backward, and the parameter and BatchRenorm buffer slabs after its Adam update.  An array of more than DUMP_SAMPLE
+  elements is cut down to the elements at a seeded sample of its flat positions (sorted, repeats dropped): the same
+  positions in every run with the same arguments, so that two builds can be compared element for element."""
+  st = model.engine.store
+  def sample(x, seed):
+    x = x.detach().reshape(-1)
+    if x.numel() > DUMP_SAMPLE:
+      pos = t.randint(x.numel(), (DUMP_SAMPLE,), generator=t.Generator().manual_seed(seed)).unique()
+      x = x[pos.to(x.device)]
+    return x.float().cpu().numpy()
+  return {"loss": sample(loss, 0), "logits": sample(plan.logits, 1), "grads": sample(st.grads, 2),
+          "params": sample(st.params, 3), "buffers": sample(st.buffers, 4)}
+
+
+def restart(model, start):
+  """Puts the model's parameter, BatchRenorm buffer and num_batches_tracked slabs back to `start` (copies taken before its
+  first step) and its Adam optimizer back to no steps taken."""
+  eng = model.engine
+  side = eng.side_stream()
+  if side is not None:
+    t.cuda.current_stream().wait_stream(side)      # (the previous step's last Adam buckets may still run there)
+  for x, x0 in zip((eng.store.params, eng.store.buffers, eng.store.nbt), start):
+    x.copy_(x0)
+  if eng.adam_m is not None:
+    eng.adam_m.zero_(); eng.adam_v.zero_()
+  eng.adam_t = 0
+  model.mark_weights_dirty()
+
+
 GRAPH = os.environ.get("CRN_GRAPH", "0") == "1"      # replay the captured HIP graph of the step (off: measured slower)
 
 
@@ -293,7 +328,11 @@ def main():
   ap.add_argument("--no-fp32-side", action="store_true", help="skip the fp32-math run printed beside the headline (profiling)")
   ap.add_argument("--no-m9-side", action="store_true", help="skip the 14-class (m7 / m9) step printed beside the headline")
   ap.add_argument("--no-sr-side", action="store_true", help="skip the x2 super-resolution (h7 at 256^3) leg")
+  ap.add_argument("--dump-outputs", metavar="DIR",
+                  help="write what the last timed step of the headline computed as DIR/<name>.npy (float32; step_outputs)")
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error("--steps must be at least 1")
 
   from corenet_amd import distributed as D
   from corenet_amd.model.core_net import CoreNet, CoreNetConfig, DecoderConfig
@@ -319,8 +358,14 @@ def main():
   sync.probe = world > 1
   plan = model.engine.plan(B)
 
-  def timed(mdl, pl):
-    """W warm-up steps, then K steps timed between barrier + synchronize on both sides, max over ranks."""
+  def timed(mdl, pl, outputs=None):
+    """W warm-up steps, then K steps timed between barrier + synchronize on both sides, max over ranks.  The last timed
+    step starts again from the state the model had on entry (restart): in the default math the weight gradients are summed
+    with atomics, and Adam turns their last-bit differences into another trajectory within a few steps, so only a step from
+    a fixed state computes the same thing in every run.  The restart's device copies (~0.6 GB, once) are queued behind the
+    steps inside the clock: stopping the clock around them would cost more, the host then starts the last step with the GPU
+    idle.  `outputs` (a dict) receives step_outputs() of the last step."""
+    start = [x.clone() for x in (mdl.engine.store.params, mdl.engine.store.buffers, mdl.engine.store.nbt)]
     def step():
       return mdl.train_step(image, v2s, off, grid, loss_name, lr=4e-4, adam_eps=1e-4, world_size=world,
                             all_reduce=sync if world > 1 else None)
@@ -332,7 +377,9 @@ def main():
       dist.barrier()
     t.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+      if i == args.steps - 1:
+        restart(mdl, start)
       loss = step()
     t.cuda.synchronize()
     if world > 1:
@@ -341,6 +388,8 @@ def main():
     tt = t.tensor([dt], dtype=t.float64, device=dev)
     if world > 1:
       dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+    if outputs is not None:
+      outputs.update(step_outputs(mdl, pl, loss))     # before the probe steps below move the model on
     if world == 1 and GRAPH:
       # the timed steps were replays of the captured HIP graph (one launch per step), which cannot carry timing
       # events: the per-kernel probes come from 3 launch-by-launch steps on the same buffers right after it
@@ -353,8 +402,15 @@ def main():
     return float(tt), pr, loss
 
   progress("model built; timing the headline step")
-  dt, probes, loss = timed(model, plan)
+  outputs = {} if args.dump_outputs and rank == 0 else None
+  dt, probes, loss = timed(model, plan, outputs)
   progress("headline: %.3f ms per step" % (dt / args.steps * 1e3))
+  if outputs is not None:
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in outputs.items():
+      np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    progress("outputs of the last timed step written to %s" % args.dump_outputs)
   replicas = None
   if world > 1:
     # data parallelism keeps the replicas identical (pipeline.py:199: DDP averages the gradients, every rank takes the same

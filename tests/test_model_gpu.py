@@ -973,3 +973,60 @@ def test_super_resolution_x2_golden_and_encoder_reuse(math):
   m.train()
   with pytest.raises(AssertionError):
     sr(image.cuda(), camera, v2v, go, (256, 256, 256))
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+  """bench.py --dump-outputs DIR writes step_outputs() of the last timed step as float32 .npy files, 64 MB at most in all,
+  and its line reports the K timed steps and their time.  That step starts from the seeded initial state whatever W and K
+  are (bench.restart), so it is one training step from reset_parameters(seed=0) on bench.synthetic_batch, replayed here:
+  (i) in deterministic mode (CRN_DETERMINISTIC=1 there, crn_set_deterministic here) the dump equals the replay bit for bit;
+  (ii) in the default mode, with other W and K, it equals it to rounding -- the weight gradients' atomics reorder sums
+  (~1e-5 of a bucket's scale, profiles/r06_run_to_run_spread.txt), one Adam step from zero moments moves a parameter by at
+  most lr / eps = 4x the change of its gradient, the forward and the running statistics do not depend on the order."""
+  import json, subprocess, sys
+  import bench
+  from corenet_amd.backend import default_backend
+  from corenet_amd.model.core_net import CoreNet, CoreNetConfig, DecoderConfig
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  names = ("loss", "logits", "grads", "params", "buffers")
+
+  def run_bench(out, steps, warmup, deterministic):
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--math", "bf16x3", "--no-cpu-baseline", "--no-fp32-side", "--no-m9-side", "--no-sr-side", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=dict(os.environ, CRN_DETERMINISTIC=deterministic), capture_output=True, text=True,
+                       timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4 * 128 ** 3 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(out / (n + ".npy")) for n in names) <= 64 << 20
+    got = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["loss"][0] == np.float32(d["loss"])
+    return got
+
+  det = run_bench(tmp_path / "det", 2, 1, "1")
+  dflt = run_bench(tmp_path / "default", 3, 2, "0")
+  be = default_backend()
+  try:
+    be.set_deterministic(True)
+    m = CoreNet(CoreNetConfig(DecoderConfig((128, 128, 128), 2, 2, 64, 0.75)), device="cuda", decoder_math="bf16x3")
+    m.reset_parameters(seed=0); m.train()
+    image, v2s, off, grid = [x.cuda() for x in bench.synthetic_batch(4, seed=0, num_classes=2)]
+    loss = m.train_step(image, v2s, off, grid.to(t.int32), "iou_fgbg", lr=4e-4, adam_eps=1e-4)
+    t.cuda.synchronize()
+    want = bench.step_outputs(m, m.engine.plan(4), loss)
+  finally:
+    be.set_deterministic(False)
+  for n in names:
+    assert det[n].shape == want[n].shape == dflt[n].shape, (n, det[n].shape, want[n].shape, dflt[n].shape)
+    assert np.array_equal(det[n], want[n]), (n, float(np.abs(det[n] - want[n]).max()), float(np.abs(want[n]).max()))
+  bars = {"loss": 1e-5, "logits": 1e-5, "buffers": 1e-5, "grads": 1e-4}          # of the array's largest magnitude
+  for n, bar in bars.items():
+    err = float(np.abs(dflt[n] - want[n]).max())
+    assert err <= bar * float(np.abs(want[n]).max()), (n, err, float(np.abs(want[n]).max()))
+  err = float(np.abs(dflt["params"] - want["params"]).max())
+  assert err <= 1e-4, err                                                          # a quarter of one step (lr 4e-4)
