@@ -141,6 +141,11 @@ _SIGS = {
     "crn_fill_voxels": [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp],
     "crn_fill_voxels_strided": [vp, C.POINTER(i64), vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, sz, vp],
     "crn_fill_voxels_cpu": [vp, vp, i32, i32, i32, i32, i32, i32],
+    "crn_marching_cubes_count": [vp, C.POINTER(i64), i32, i32, i32, i32, f32, vp, sz, vp, vp],
+    "crn_marching_cubes_emit": [vp, C.POINTER(i64), i32, i32, i32, i32, f32, vp, vp, sz, vp, vp, vp, vp],
+    "crn_marching_cubes_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32],
+    "crn_box_filter": [vp, C.POINTER(i64), vp, i32, i32, i32, i32, i32, vp, sz, vp],
+    "crn_box_filter_cpu": [vp, C.POINTER(i64), vp, i32, i32, i32, i32, i32, i32],
     "crn_voxelize_mesh": [vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "crn_batch_renorm_eval_affine": [vp, vp, vp, i32, f32, vp, vp, vp],
     "crn_transform_meshes": [vp, vp, i32, vp, i32, vp, vp],
@@ -152,6 +157,7 @@ _SIZE_FNS = {
     "crn_batch_renorm_workspace_bytes": [i32],
     "crn_loss_workspace_bytes": [i32, i32],
     "crn_fill_voxels_workspace_bytes": [i32, i32, i32, i32],
+    "crn_marching_cubes_workspace_bytes": [i32, i32, i32, i32],
     "crn_convt_s2k7_ximage_bytes": [i32, i32, i32, i32],
     "crn_stem_conv_parts": [i32, i32, i32],
 }

@@ -458,6 +458,32 @@ class HipBackend:
       self.lib.crn_fill_voxels_strided(ptr(grid), gs, ptr(out), os_, _DTYPE_CODE[grid.dtype], N, D, H, W,
                                        ptr(ws), n, _lib.stream())
 
+  # -- marching cubes (corenet_amd.visualization) -------------------------------------------------
+  def marching_cubes_count(self, grid: t.Tensor, level: float, counts: t.Tensor):
+    """counts (device int64 [N, 2]) <- per-object (num_vertices, num_faces); the scanned offsets stay in the "mc"
+    workspace for marching_cubes_emit on the same grid."""
+    N, D, H, W = grid.shape
+    n = self.lib.crn_marching_cubes_workspace_bytes(N, D, H, W)
+    ws = self.workspace("mc", n, grid.device)
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_marching_cubes_count(ptr(grid), st, N, D, H, W, float(level), ptr(ws), n, ptr(counts), _lib.stream())
+
+  def marching_cubes_emit(self, grid: t.Tensor, level: float, matrices: Optional[t.Tensor], vertices: t.Tensor,
+                          normals: t.Tensor, faces: t.Tensor):
+    N, D, H, W = grid.shape
+    n = self.lib.crn_marching_cubes_workspace_bytes(N, D, H, W)
+    ws = self.workspace("mc", n, grid.device)
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_marching_cubes_emit(ptr(grid), st, N, D, H, W, float(level), ptr(matrices), ptr(ws), n, ptr(vertices),
+                                     ptr(normals), ptr(faces), _lib.stream())
+
+  def box_filter(self, grid: t.Tensor, k: int, out: t.Tensor):
+    N, D, H, W = grid.shape
+    n = 4 * grid.numel()
+    ws = self.workspace("box", n, grid.device)
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_box_filter(ptr(grid), st, ptr(out), N, D, H, W, int(k), ptr(ws), n, _lib.stream())
+
   def voxelize_mesh(self, tri, tri_mesh, view2voxel, M, D, H, W, sub_side, mult, conservative,
                     depth_mult, grid):
     self.lib.crn_voxelize_mesh(ptr(tri), ptr(tri_mesh), tri.shape[0], ptr(view2voxel), M, D, H, W,

@@ -530,6 +530,39 @@ int crn_fill_voxels_strided(const void* grid, const int64_t* grid_strides, void*
 int crn_fill_voxels_cpu(const void* grid, void* out, int dtype, int N, int D, int H, int W,
                         int num_threads);
 
+/* ---------------- marching cubes (corenet_amd.visualization) -----------------
+ * Surface of level `level` (> 0) of N independent float32 objects grid[n][d][h][w] (element strides[0..2] arbitrary,
+ * strides[3] must be 1), each padded by one zero voxel; indexed mesh in the padded index space, (x, y, z) = (w, h, d),
+ * sample grid[n, d, h, w] at (w + 1, h + 1, d + 1).  Contract (corner classification f > level, vertex formula,
+ * normals, table, output order): corenet_amd/visualization/marching_cubes.py and DESIGN section 13.
+ * Outputs: vertices / normals [V][3] f32, faces [F][3] int32 (vertex ids local to the object), objects in order.
+ * At most CRN_MC_MAX_OBJECT_CELLS cells ((D + 1)(H + 1)(W + 1)) per object: object-local vertex ids stay in int32.
+ *
+ * GPU, two calls on stream s: crn_marching_cubes_count writes counts[n] = (num_vertices, num_faces) (DEVICE int64
+ * [N][2]) and keeps the scanned offsets in `workspace` (crn_marching_cubes_workspace_bytes(N, D, H, W)); after the
+ * caller has sized the outputs from counts, crn_marching_cubes_emit with the same grid and workspace writes them.
+ * Neither waits for the GPU.  matrices: NULL or DEVICE f32 [N][4][4] applied in emit (positions as points with the
+ * homogeneous divide, normals as vectors, not renormalised).                                                      */
+#define CRN_MC_MAX_OBJECT_CELLS ((int64_t)1 << 29)
+size_t crn_marching_cubes_workspace_bytes(int N, int D, int H, int W);
+int crn_marching_cubes_count(const float* grid, const int64_t* strides, int N, int D, int H, int W, float level,
+                             void* workspace, size_t workspace_bytes, int64_t* counts, crnStream s);
+int crn_marching_cubes_emit(const float* grid, const int64_t* strides, int N, int D, int H, int W, float level,
+                            const float* matrices, void* workspace, size_t workspace_bytes, float* vertices,
+                            float* normals, int32_t* faces, crnStream s);
+/* k^3 box mean with zero padding [(k-1)/2, k-1-(k-1)/2] per axis (MarchingCubesArtifact's filter_kernel): in with
+ * element strides[4] (N, D, H, W), out contiguous [N][D][H][W] (must not alias in); separable, w then h then d, each
+ * tap sum in ascending order, the last pass times 1/k^3.  workspace: N*D*H*W floats.                              */
+int crn_box_filter(const float* in, const int64_t* strides, float* out, int N, int D, int H, int W, int k,
+                   void* workspace, size_t workspace_bytes, crnStream s);
+/* Host twins (HOST memory, same contract and bit-identical results).  crn_marching_cubes_cpu with vertices == NULL
+ * writes counts[N][2]; with vertices != NULL it reads those counts and writes the mesh.  num_threads <= 0: all. */
+int crn_marching_cubes_cpu(const float* grid, const int64_t* strides, int N, int D, int H, int W, float level,
+                           const float* matrices, int64_t* counts, float* vertices, float* normals, int32_t* faces,
+                           int num_threads);
+int crn_box_filter_cpu(const float* in, const int64_t* strides, float* out, int N, int D, int H, int W, int k,
+                       int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
