@@ -146,6 +146,12 @@ _SIGS = {
     "crn_marching_cubes_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32],
     "crn_box_filter": [vp, C.POINTER(i64), vp, i32, i32, i32, i32, i32, vp, sz, vp],
     "crn_box_filter_cpu": [vp, C.POINTER(i64), vp, i32, i32, i32, i32, i32, i32],
+    "crn_render_bin": [vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp],
+    "crn_render_raster": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "crn_render_cpu": [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i32],
+    "crn_voxel_faces_count": [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp, vp],
+    "crn_voxel_faces_emit": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, sz, vp, vp, vp, vp],
+    "crn_voxel_faces_cpu": [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32],
     "crn_voxelize_mesh": [vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "crn_batch_renorm_eval_affine": [vp, vp, vp, i32, f32, vp, vp, vp],
     "crn_transform_meshes": [vp, vp, i32, vp, i32, vp, vp],
@@ -158,6 +164,7 @@ _SIZE_FNS = {
     "crn_loss_workspace_bytes": [i32, i32],
     "crn_fill_voxels_workspace_bytes": [i32, i32, i32, i32],
     "crn_marching_cubes_workspace_bytes": [i32, i32, i32, i32],
+    "crn_voxel_faces_workspace_bytes": [i32, i32, i32, i32],
     "crn_convt_s2k7_ximage_bytes": [i32, i32, i32, i32],
     "crn_stem_conv_parts": [i32, i32, i32],
 }

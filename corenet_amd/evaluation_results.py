@@ -1,0 +1,172 @@
+"""Qualitative eval results (reference: evaluation_results.py:42-174): one PNG per scene with five camera rows (the
+dataset camera, then four tetrahedron views) of five panels each: the input image, the marching-cubes surface of the
+prediction, the ground-truth meshes, the predicted label grid and the ground-truth label grid.
+
+The reference renders every panel from every camera on its own (20 GL renders per scene, each copied to the host).
+visualize_output gathers all 3D panels x cameras of the requested batch elements into ONE batched render
+(render.render_batch), after one marching-cubes call and one voxel-face call, and gives the same pictures as the
+artifact-by-artifact path of visualization.artifacts.  CUDA inputs render on the GPU, CPU inputs through the host twin;
+both give identical images.  TensorBoard output is out of scope."""
+from __future__ import annotations
+
+import os
+from typing import Iterable, List, Optional
+
+import PIL.Image
+import torch as t
+
+from corenet_amd.geometry import transformations
+from corenet_amd.visualization import artifacts as vis
+from corenet_amd.visualization import colors, render
+from corenet_amd.visualization.marching_cubes import _triangle_soup, marching_cubes
+
+IMAGE_SIZE = (384, 384)
+
+
+def _task(task_type) -> str:
+  task = getattr(task_type, "value", task_type)
+  task = str(task).lower()
+  if task not in ("fg_bg", "semantic"):
+    raise ValueError(f"unknown task type {task_type!r}")
+  return task
+
+
+def extract_labels(pmf: t.Tensor, b, task_type):
+  """(predicted labels int32 [B, D, H, W], ground truth [B, D, H, W]) for a task (evaluation_results.py:42-54): the
+  argmax class, and for fg_bg both multiplied by the scene's mesh label."""
+  pred = pmf.argmax(dim=1).to(t.int32)
+  gt = b.grid
+  if _task(task_type) == "fg_bg":
+    labels = t.cat([t.as_tensor(v).reshape(-1) for v in b.mesh_labels]).to(pred.device, t.int32)[:, None, None, None]
+    pred = pred * labels
+    gt = gt * labels
+  return pred, gt
+
+
+def visualize_output(pmf: t.Tensor, ex, task_type, batch_indices: Optional[Iterable[int]] = None) -> List[List[t.Tensor]]:
+  """Per requested batch element, five uint8 rows [384, 1920, 3] on pmf's device (evaluation_results.py:57-118).
+
+  pmf f32 [B, C, D, H, W] class probabilities; ex the voxelized BatchedExample (grid, v2x_transform, vertices, ...).
+  Cameras, boxes and matrices are built on the host in float32, and every box is computed with device-independent
+  arithmetic (artifacts.points_box, render.voxel_faces), so the GPU and the host path draw the same pictures."""
+  task = _task(task_type)
+  dev = pmf.device
+  B, C = pmf.shape[:2]
+  idx = [int(i) for i in batch_indices] if batch_indices else list(range(B))
+  if len(ex.scene_id) != B or any(not 0 <= i < B for i in idx):
+    raise ValueError(f"visualize_output: pmf has {B} elements, the batch {len(ex.scene_id)}, indices {idx}")
+  n = len(idx)
+  palette = t.as_tensor(colors.DEFAULT_COLOR_PALETTE, dtype=t.float32)
+  pred_lbl, gt_lbl = extract_labels(pmf, ex, task)
+  mesh_num_tri = [t.as_tensor(v).to(t.int64).cpu() for v in ex.mesh_num_tri]
+  mesh_labels = [t.as_tensor(v).to(t.int64).cpu().reshape(-1) for v in ex.mesh_labels]
+  scene_num_tri = [int(v.sum()) for v in mesh_num_tri]
+  offsets = [sum(scene_num_tri[:b]) for b in range(B)]
+  v2x_inv = [ex.v2x_transform[b].detach().cpu().to(t.float32).inverse() for b in idx]
+  world_to_view = [ex.view_transform[b].detach().cpu().to(t.float32) for b in idx]
+  view_to_world = [t.inverse(m) for m in world_to_view]
+  default_cams = [ex.camera_transform[b].detach().cpu().to(t.float32) for b in idx]
+
+  # marching cubes of every foreground class of every element, in one call
+  K = C - 1
+  mc_mats = t.stack([v2x_inv[e] for e in range(n) for _ in range(K)])
+  mesh = marching_cubes(pmf[idx][:, 1:].reshape((n * K,) + tuple(pmf.shape[2:])), level=0.5, matrices=mc_mats.to(dev))
+  mh = mc_mats.to(t.float64)
+  h = mh @ t.ones(4, dtype=t.float64)
+  dummy_v = (h[:, :3] / h[:, 3:]).to(t.float32)[:, None, :].expand(n * K, 3, 3)
+  dummy_n = (mh[:, :3, :3] @ t.ones(3, dtype=t.float64)).to(t.float32)[:, None, :].expand(n * K, 3, 3)
+  mc_tri, mc_nrm, mc_cnt = _triangle_soup(mesh, dummy_v, dummy_n)
+  mc_cnt = mc_cnt.to(t.int64).cpu()
+
+  # exposed voxel faces of the predicted and the ground-truth grids, in one call
+  grids = t.cat([pred_lbl[idx], gt_lbl[idx].to(dev, t.int32)], 0)
+  vmats = t.stack(v2x_inv + v2x_inv)
+  bmats = t.stack([transformations.chain([view_to_world[e % n], v2x_inv[e % n]]) for e in range(2 * n)])
+  faces = render.voxel_faces(grids, palette, vmats, material_base=0, box_matrices=bmats)
+  vox_cnt = faces.num_triangles.cpu()
+  vox_box = faces.boxes.cpu()
+
+  # materials: the voxel palette at 0, then per element the marching-cubes and the ground-truth mesh colours
+  P = palette.shape[0]
+  mats = [render.voxel_materials(palette)]
+  base, mc_base, gt_base = P, [], []
+  for e, b in enumerate(idx):
+    if task == "fg_bg":
+      assert mesh_labels[b].shape == (1,)
+      mc_colors = palette[mesh_labels[b]]
+    else:
+      mc_colors = palette[1:C]
+    mc_base.append(base)
+    mats.append(render.make_materials(mc_colors))
+    base += mc_colors.shape[0]
+    gt_base.append(base)
+    mats.append(render.make_materials(palette[mesh_labels[b]]))
+    base += mesh_labels[b].shape[0]
+  mats = t.cat(mats, 0)
+
+  # one buffer of triangles: [mc of all elements][gt meshes of all elements][voxel faces of all grids]
+  gt_tri = [ex.vertices[offsets[b]:offsets[b] + scene_num_tri[b]].to(dev, t.float32) for b in idx]
+  mc_mid = t.repeat_interleave(t.tensor([mc_base[e] + k for e in range(n) for k in range(K)], dtype=t.int32), mc_cnt)
+  gt_mid = [t.repeat_interleave(t.arange(len(mesh_num_tri[b]), dtype=t.int32) + gt_base[e], mesh_num_tri[b])
+            for e, b in enumerate(idx)]
+  T_mc, T_gt = int(mc_cnt.sum()), sum(scene_num_tri[b] for b in idx)
+  tri = t.cat([mc_tri.to(dev), *gt_tri, faces.triangles], 0)
+  nrm = t.cat([mc_nrm.to(dev), t.zeros((T_gt, 3, 3), dtype=t.float32, device=dev), faces.normals], 0)
+  mid = t.cat([mc_mid.to(dev), *[g.to(dev) for g in gt_mid], faces.material_ids], 0)
+
+  # per element: the panels' triangle ranges and boxes -> the four extra cameras
+  mc_start = t.cumsum(mc_cnt.reshape(n, K).sum(1), 0) - mc_cnt.reshape(n, K).sum(1)
+  gt_start = T_mc
+  vox_start = t.cumsum(vox_cnt, 0) - vox_cnt + T_mc + T_gt
+  ranges, vps, modes = [], [], []
+  aspect = IMAGE_SIZE[1] / IMAGE_SIZE[0]
+  for e, b in enumerate(idx):
+    r_mc = (int(mc_start[e]), int(mc_start[e]) + int(mc_cnt[e * K:(e + 1) * K].sum()))
+    r_gt = (gt_start, gt_start + scene_num_tri[b])
+    gt_start += scene_num_tri[b]
+    r_pv = (int(vox_start[e]), int(vox_start[e]) + int(vox_cnt[e]))
+    r_gv = (int(vox_start[n + e]), int(vox_start[n + e]) + int(vox_cnt[n + e]))
+    boxes = [vis.points_box(tri[r_mc[0]:r_mc[1]].reshape(-1, 3), view_to_world[e]),
+             vis.points_box(tri[r_gt[0]:r_gt[1]].reshape(-1, 3), view_to_world[e])]
+    boxes = [x.cpu() for x in boxes] + [vox_box[e], vox_box[n + e]]
+    ltf = t.stack([x[0] for x in boxes]).min(0)[0]
+    rbb = t.stack([x[1] for x in boxes]).max(0)[0]
+    cams = [default_cams[e]] + vis.extra_views_for_box(ltf, rbb, aspect, view_to_world[e])
+    for cam in cams:
+      for r, mode in ((r_mc, 1), (r_gt, 0), (r_pv, 2), (r_gv, 2)):
+        ranges.append(r)
+        vps.append(cam)
+        modes.append(mode)
+  imgs = render.render_batch(tri, mid, mats.to(dev), ranges, t.stack(vps), IMAGE_SIZE, normals=nrm, normal_modes=modes,
+                             cull_back_facing=False)
+  imgs = imgs.reshape(n, 5, 4, IMAGE_SIZE[0], IMAGE_SIZE[1], 3)
+  out = []
+  for e, b in enumerate(idx):
+    picture = vis.resize_image(ex.input_image[b], IMAGE_SIZE).to(dev)
+    out.append([t.cat([picture] + [imgs[e, c, p] for p in range(4)], 1) for c in range(5)])
+  return out
+
+
+class QualitativeResults:
+  """Writes img_<scene_id with / -> _>.png (the five rows stacked) for the first num_qualitative_results scenes of
+  the dataset (evaluation_results.py:121-174, without the TensorBoard part)."""
+
+  def __init__(self, dataset, image_output_dir: str, task_type="fg_bg", num_qualitative_results: int = 10):
+    n = min(int(num_qualitative_results), len(dataset))
+    self.disk_result_ids = {dataset[i].scene_id for i in range(n)}
+    self.image_output_dir = image_output_dir
+    self.task_type = task_type
+
+  def _write_image(self, scene_id: str, scene_images: List[t.Tensor]):
+    image = t.cat(scene_images, dim=0)
+    fn = os.path.join(self.image_output_dir, "img_%s.png" % scene_id.replace("/", "_"))
+    os.makedirs(os.path.dirname(fn) or ".", exist_ok=True)
+    PIL.Image.fromarray(image.cpu().numpy()).save(fn, format="png")
+
+  def add_batch(self, pmf: t.Tensor, ex):
+    """Renders and writes the batch elements whose scene is of interest."""
+    batch_indices = [i for i, v in enumerate(ex.scene_id) if v in self.disk_result_ids]
+    if not batch_indices:
+      return
+    for i, images in zip(batch_indices, visualize_output(pmf, ex, self.task_type, batch_indices)):
+      self._write_image(ex.scene_id[i], images)

@@ -155,8 +155,12 @@ def _triangle_soup(m: Meshes, dummy_v: t.Tensor, dummy_n: t.Tensor) -> Tuple[t.T
     cnt = t.where(empty, t.ones_like(nf), nf)
     start = t.cumsum(cnt, 0) - cnt                                        # first triangle of every object in the output
     T = int(cnt.sum())
-    tri_out = dummy_v.to(dev).expand(T, 3, 3).clone()
-    nrm_out = dummy_n.to(dev).expand(T, 3, 3).clone()
+    if dummy_v.dim() == 3:                                                # one dummy triangle per object
+      owner = t.repeat_interleave(t.arange(len(cnt), device=dev), cnt, output_size=T)
+      tri_out, nrm_out = dummy_v.to(dev)[owner], dummy_n.to(dev)[owner]
+    else:
+      tri_out = dummy_v.to(dev).expand(T, 3, 3).clone()
+      nrm_out = dummy_n.to(dev).expand(T, 3, 3).clone()
     pos = start[obj] + (t.arange(len(obj), device=dev) - (t.cumsum(nf, 0) - nf)[obj])
     tri_out[pos], nrm_out[pos] = tri, nrm
     return tri_out, nrm_out, cnt.to(t.int32)

@@ -1,0 +1,319 @@
+"""Rendering of triangle soups and voxel grids (reference: visualization/scene_renderer.py, voxel_renderer.py and their
+GLSL shaders, drawn there through OpenGL on an EGL context).  Here a software renderer draws many images in one call:
+CUDA(HIP) tensors run the kernels of csrc/render.hip, CPU tensors the library's host twin (csrc/render_cpu.cpp).  Both
+give identical images when no material has a specular term (powf may differ by one level otherwise); a CUDA tensor
+never goes to the host twin.
+
+Contract, GL's rules for one draw of triangles without MSAA:
+  * clip = VP . (p, 1); window x = (x_ndc + 1) / 2 * W, y = (y_ndc + 1) / 2 * H; image row r, column c samples the
+    pixel centre (c + 0.5, r + 0.5), so row 0 is NDC y = -1 (GL's read-back order, not flipped).
+    camera_util.perspective_projection flips y, which puts world-up at row 0.
+  * Coverage: homogeneous edge functions with a top-left rule on exact zeros, so shared edges leave no holes and no
+    pixel twice.  Only the part of a triangle in front of the eye (w > 0) covers pixels; there is no wrap-around.
+    A fragment survives iff z_ndc, linear in screen space, is in [-1, 1] (NaN never survives).
+  * Depth: GL LESS_EQUAL in submission order, i.e. the nearest fragment wins and on equal depth the later triangle.
+  * Attributes (position, normal) are interpolated perspective-correct.
+  * Shading, point_light_illumination.frag: N = normalize(normal), L = normalize(light - pos),
+    V = -normalize(cam - pos), R = L - 2 dot(N, L) N; colour = ambient + diffuse |dot(N, L)| light_colour +
+    ambient_light diffuse + specular light_colour max(dot(R, V), 0)^shininess, clamped to [0, 1], rint(255 c).
+    Uncovered pixels get the clear colour.
+  * cam = inverse(VP) . (0, 0, -1, 1), dehomogenised, in float32 on the host; the light defaults to it.
+  * Textures are not supported.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch as t
+
+from corenet_amd.geometry import transformations
+from corenet_amd.visualization import camera_util
+from corenet_amd.visualization.colors import DEFAULT_COLOR_PALETTE
+
+TILE = 16
+_IMAGE_WORDS = 40      # sizeof(crnRenderImage) / 4 (include/corenet_hip.h)
+
+
+def _lib():
+  from corenet_amd import _lib as L
+  return L.lib()
+
+
+def _host(v, dtype=t.float32) -> t.Tensor:
+  return t.as_tensor(v, dtype=dtype).detach().cpu()
+
+
+def camera_position(view_projection) -> t.Tensor:
+  """The eye of a view-projection matrix f32[4, 4]: inverse(VP) . (0, 0, -1, 1), dehomogenised (host float32)."""
+  c = t.mv(t.inverse(_host(view_projection)), t.tensor([0, 0, -1, 1], dtype=t.float32))
+  return c[:3] / c[3]
+
+
+def _rows(v, n: int, k: int, name: str) -> t.Tensor:
+  v = _host(v)
+  if v.dim() == 1:
+    v = v.expand(n, v.shape[0])
+  if tuple(v.shape) != (n, k):
+    raise ValueError(f"render: {name} must be [{k}] or [{n}, {k}], got {tuple(v.shape)}")
+  return v
+
+
+def make_materials(diffuse, ambient=0.05, specular=(0.0, 0.0, 0.0), shininess=2048.0) -> t.Tensor:
+  """Material table f32[M, 10] (ambient 3, diffuse 3, specular 3, shininess) from diffuse f32[M, 3]; the others are
+  [3] / [M, 3] (ambient, specular) and a scalar or [M] (shininess)."""
+  d = _host(diffuse).reshape(-1, 3)
+  M = d.shape[0]
+  a = _host(ambient)
+  a = a.expand(M, 3) if a.dim() == 0 else _rows(a, M, 3, "ambient")
+  s = _rows(specular, M, 3, "specular")
+  sh = _host(shininess).reshape(-1).expand(M) if _host(shininess).numel() == 1 else _host(shininess).reshape(M)
+  return t.cat([a, d, s, sh[:, None]], 1).contiguous()
+
+
+def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tensor, ranges, view_projections,
+                 image_size: Tuple[int, int], normals: Optional[t.Tensor] = None, normal_modes=None,
+                 light_positions=None, light_colors=(1.0, 1.0, 1.0), ambient_light_colors=(0.2, 0.2, 0.2),
+                 clear_colors=(0.0, 0.0, 0.0), cull_back_facing=False) -> t.Tensor:
+  """Renders I images of image_size = (H, W) in one call -> uint8 [I, H, W, 3] on the triangles' device.
+
+  Image i draws triangles ranges[i] = [t0, t1) of the shared buffers: triangles f32 [T, 3, 3] (world space),
+  material_ids int32 [T] into materials f32 [M, 10] (make_materials; an id outside [0, M) shades black) and normals
+  f32 [T, 3, 3] (optional).  normal_modes[i]: 1 = interpolate the per-vertex normals, 2 = flat, normals[t, 0], 0 = the
+  geometric normal normalize(cross(normalize(v1 - v0), normalize(v2 - v0))); default 1 with normals, 0 without.
+  view_projections [I, 4, 4]; light_positions None (each image's camera) or [I, 3]; light_colors,
+  ambient_light_colors, clear_colors [3] or [I, 3]; cull_back_facing a bool or [I] (culls when the signed NDC area is
+  <= 0).  On the GPU the call synchronises once: a read of the number of (tile, triangle) pairs."""
+  H, W = (int(v) for v in image_size)
+  dev = triangles.device
+  triangles = t.as_tensor(triangles, dtype=t.float32).contiguous()
+  if triangles.dim() != 3 or triangles.shape[1:] != (3, 3):
+    raise ValueError(f"render: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+  T = triangles.shape[0]
+  material_ids = t.as_tensor(material_ids).to(dev, t.int32).contiguous()
+  materials = t.as_tensor(materials, dtype=t.float32).to(dev).contiguous()
+  if material_ids.shape != (T,) or materials.dim() != 2 or materials.shape[1] != 10:
+    raise ValueError("render: material_ids must be [T] and materials [M, 10]")
+  if normals is not None:
+    normals = t.as_tensor(normals, dtype=t.float32).to(dev).contiguous()
+    if normals.shape != triangles.shape:
+      raise ValueError("render: normals must have the triangles' shape")
+  ranges = _host(ranges, t.int64).reshape(-1, 2)
+  I = ranges.shape[0]
+  if I < 1 or H < 1 or W < 1:
+    raise ValueError("render: need at least one image of positive size")
+  if (ranges[:, 0] < 0).any() or (ranges[:, 1] < ranges[:, 0]).any() or (ranges[:, 1] > T).any() or T >= 1 << 31:
+    raise ValueError("render: every range must satisfy 0 <= t0 <= t1 <= T < 2^31")
+  vps = _host(view_projections).reshape(I, 4, 4)
+  if normal_modes is None:
+    normal_modes = t.full((I,), 1 if normals is not None else 0, dtype=t.int64)
+  normal_modes = _host(normal_modes, t.int64).reshape(-1).expand(I)
+  if normals is None and bool((normal_modes != 0).any()):
+    raise ValueError("render: normal modes 1 and 2 need normals")
+  cams = t.stack([camera_position(vps[i]) for i in range(I)])
+  lights = cams if light_positions is None else _rows(light_positions, I, 3, "light_positions")
+  cull = _host(cull_back_facing, t.int64).reshape(-1).expand(I)
+  lens = ranges[:, 1] - ranges[:, 0]
+  inst0 = t.cumsum(lens, 0) - lens
+  num_inst = int(lens.sum())
+  if num_inst >= 1 << 31:
+    raise ValueError("render: at most 2^31 - 1 (image, triangle) pairs per call")
+  rec = np.zeros((I, _IMAGE_WORDS), np.float32)
+  rec[:, :16] = vps.reshape(I, 16).numpy()
+  rec[:, 16:19] = lights.numpy()
+  rec[:, 19:22] = cams.numpy()
+  rec[:, 22:25] = _rows(light_colors, I, 3, "light_colors").numpy()
+  rec[:, 25:28] = _rows(ambient_light_colors, I, 3, "ambient_light_colors").numpy()
+  rec[:, 28:31] = _rows(clear_colors, I, 3, "clear_colors").numpy()
+  ints = rec.view(np.int32)
+  ints[:, 31] = cull.numpy()
+  ints[:, 32] = normal_modes.numpy()
+  ints[:, 33] = ranges[:, 0].numpy()
+  ints[:, 34] = ranges[:, 1].numpy()
+  ints[:, 35] = inst0.numpy()
+  images = t.from_numpy(rec)
+  max_len = int(lens.max())
+  M = materials.shape[0]
+  lib = _lib()
+  if dev.type == "cuda":
+    from corenet_amd import _lib as L
+    images = images.to(dev)
+    ntiles = ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
+    records = t.empty((max(num_inst, 1), 16), dtype=t.float32, device=dev)
+    counts = t.empty(I * ntiles, dtype=t.int32, device=dev)
+    offsets = t.empty(I * ntiles + 1, dtype=t.int64, device=dev)
+    s = L.stream()
+    lib.crn_render_bin(triangles.data_ptr(), images.data_ptr(), I, H, W, max_len, num_inst, records.data_ptr(),
+                       counts.data_ptr(), offsets.data_ptr(), s)
+    total = int(offsets[-1].item())                                     # the call's one synchronisation
+    bins = t.empty(max(total, 1), dtype=t.int32, device=dev)
+    out = t.empty((I, H, W, 3), dtype=t.uint8, device=dev)
+    lib.crn_render_raster(triangles.data_ptr(), None if normals is None else normals.data_ptr(), material_ids.data_ptr(),
+                          materials.data_ptr(), M, images.data_ptr(), I, H, W, max_len, records.data_ptr(),
+                          counts.data_ptr(), offsets.data_ptr(), bins.data_ptr(), out.data_ptr(), s)
+    return out
+  if dev.type != "cpu":
+    raise ValueError(f"render: unsupported device {dev}")
+  out = t.empty((I, H, W, 3), dtype=t.uint8)
+  lib.crn_render_cpu(triangles.data_ptr(), None if normals is None else normals.data_ptr(), material_ids.data_ptr(),
+                     materials.data_ptr(), M, images.data_ptr(), I, H, W, out.data_ptr(), t.get_num_threads())
+  return out
+
+
+class VoxelFaces(NamedTuple):
+  triangles: t.Tensor      # f32 [T, 3, 3], view space
+  normals: t.Tensor        # f32 [T, 3, 3], the face's flat normal three times
+  material_ids: t.Tensor   # int32 [T], material_base + label
+  num_triangles: t.Tensor  # int64 [N]
+  boxes: Optional[t.Tensor]  # f32 [N, 2, 3] or None
+
+
+def voxel_faces(labels, palette, matrices, material_base: int = 0, box_matrices=None) -> VoxelFaces:
+  """The triangles the voxel renderer draws for N label grids labels [N, D, H, W] (voxel_renderer.geom).
+
+  Voxel (x, y, z) = (w, h, d) is the unit cube [x, x + 1] x [y, y + 1] x [z, z + 1] iff palette[label] (f32 [P, 3])
+  exists and has no negative channel; it goes through matrices[n] (f32 [N, 4, 4] or [4, 4], voxel -> view, no
+  homogeneous divide).  Faces come in the order +x, -x, +y, -y, +z, -z, each as the quad (center, dy, dx) of the
+  shader split into the strip's two triangles (v0, v1, v2), (v2, v1, v3); the flat normal is
+  normalize(cross(dx', dy')) after the transform.  Deliberate difference from the reference, which emits all six
+  faces of every voxel: only faces whose neighbour is not drawn (or outside the grid) are emitted, in the reference's
+  order.  A face between two drawn voxels is hidden behind a nearer face from every eye outside the solid, so the
+  images agree while the triangle count drops by about the solid's volume / surface ratio.
+
+  box_matrices (f32 [N, 4, 4], optional): also returns, per grid, the bounds [2, 3] of the centres (x, y, z) + 0.5 of
+  the voxels with label != 0 transformed as points (VoxelGridArtifact.get_3d_box; zeros if there are none).
+  On the GPU the call synchronises once (the per-grid counts)."""
+  labels = t.as_tensor(labels)
+  if labels.dim() != 4 or any(s == 0 for s in labels.shape):
+    raise ValueError(f"voxel_faces: labels must be a non-empty [N, D, H, W], got {tuple(labels.shape)}")
+  dev = labels.device
+  labels = labels.to(t.int32).contiguous()
+  N, D, H, W = labels.shape
+  pal = t.as_tensor(palette, dtype=t.float32).to(dev).reshape(-1, 3).contiguous()
+  mats = t.as_tensor(matrices, dtype=t.float32).to(dev)
+  mats = (mats.expand(N, 4, 4) if mats.shape == (4, 4) else mats).contiguous()
+  if tuple(mats.shape) != (N, 4, 4):
+    raise ValueError(f"voxel_faces: matrices must be [N, 4, 4] or [4, 4], got {tuple(mats.shape)}")
+  bm = None
+  if box_matrices is not None:
+    bm = t.as_tensor(box_matrices, dtype=t.float32).to(dev)
+    bm = (bm.expand(N, 4, 4) if bm.shape == (4, 4) else bm).contiguous()
+  P = pal.shape[0]
+  lib = _lib()
+  if dev.type == "cuda":
+    from corenet_amd import _lib as L
+    from corenet_amd.backend import default_backend
+    n = lib.crn_voxel_faces_workspace_bytes(N, D, H, W)
+    ws = default_backend().workspace("vxf", n, dev)
+    counts = t.empty(N, dtype=t.int64, device=dev)
+    boxes = t.empty((N, 2, 3), dtype=t.float32, device=dev) if bm is not None else None
+    s = L.stream()
+    lib.crn_voxel_faces_count(labels.data_ptr(), N, D, H, W, pal.data_ptr(), P, None if bm is None else bm.data_ptr(),
+                              None if boxes is None else boxes.data_ptr(), ws.data_ptr(), n, counts.data_ptr(), s)
+    T = int(counts.sum().item())                                        # the call's one synchronisation
+    tri = t.empty((T, 3, 3), dtype=t.float32, device=dev)
+    nrm = t.empty((T, 3, 3), dtype=t.float32, device=dev)
+    mid = t.empty(T, dtype=t.int32, device=dev)
+    if T:
+      lib.crn_voxel_faces_emit(labels.data_ptr(), N, D, H, W, pal.data_ptr(), P, mats.data_ptr(), int(material_base),
+                               ws.data_ptr(), n, tri.data_ptr(), nrm.data_ptr(), mid.data_ptr(), s)
+    return VoxelFaces(tri, nrm, mid, counts, boxes)
+  if dev.type != "cpu":
+    raise ValueError(f"voxel_faces: unsupported device {dev}")
+  nt = t.get_num_threads()
+  counts = t.empty(N, dtype=t.int64)
+  boxes = t.empty((N, 2, 3), dtype=t.float32) if bm is not None else None
+  lib.crn_voxel_faces_cpu(labels.data_ptr(), N, D, H, W, pal.data_ptr(), P, None if bm is None else bm.data_ptr(),
+                          None if boxes is None else boxes.data_ptr(), None, 0, counts.data_ptr(), None, None, None, nt)
+  T = int(counts.sum())
+  tri = t.empty((T, 3, 3), dtype=t.float32)
+  nrm = t.empty((T, 3, 3), dtype=t.float32)
+  mid = t.empty(T, dtype=t.int32)
+  if T:
+    lib.crn_voxel_faces_cpu(labels.data_ptr(), N, D, H, W, pal.data_ptr(), P, None, None, mats.data_ptr(),
+                            int(material_base), counts.data_ptr(), tri.data_ptr(), nrm.data_ptr(), mid.data_ptr(), nt)
+  return VoxelFaces(tri, nrm, mid, counts, boxes)
+
+
+def _finish(img: t.Tensor, output_type, return_rgb: bool = True) -> t.Tensor:
+  if output_type != t.uint8:
+    raise NotImplementedError("render: only uint8 output is supported")
+  if not return_rgb:
+    img = t.cat([img, t.full(img.shape[:-1] + (1,), 255, dtype=t.uint8, device=img.device)], -1)
+  return img
+
+
+def render_scene(vertex_positions, view_projection_matrix=None, image_size: Tuple[int, int] = (256, 256),
+                 normals=None, material_ids=None, diffuse_coefficients=None, specular_coefficient=None,
+                 ambient_coefficients=None, cull_back_facing=True, light_position=None, light_color=(1.0, 1.0, 1.0),
+                 ambient_light_color=(0.2, 0.2, 0.2), clear_color=(0, 0, 0, 1), output_type=t.uint8,
+                 return_rgb=True) -> t.Tensor:
+  """Renders triangles f32 [T, 3, 3] (scene_renderer.render_scene without textures) -> uint8 [H, W, 3] on their
+  device.  normals f32 [T, 3, 3] per vertex (normalised) or None (the geometric normal); material_ids int32 [T]
+  (default all 0) into diffuse_coefficients [M, 3] (default 0.8), ambient_coefficients [M, 3] (default 0.05) and
+  specular_coefficient [M, 4] (rgb + shininess, default (0, 0, 0, 2048)).  view_projection_matrix defaults to
+  camera_util.get_default_camera_for_mesh; light_position to the camera."""
+  v = t.as_tensor(vertex_positions, dtype=t.float32)
+  if v.dim() != 3 or v.shape[1:] != (3, 3):
+    raise ValueError(f"render_scene: vertex_positions must be [T, 3, 3], got {tuple(v.shape)}")
+  dev, T = v.device, v.shape[0]
+  if view_projection_matrix is None:
+    view_projection_matrix = camera_util.get_default_camera_for_mesh(v)
+  vp = _host(view_projection_matrix)
+  if material_ids is None:
+    material_ids = t.zeros(T, dtype=t.int32)
+  material_ids = t.as_tensor(material_ids).to(dev, t.int32)
+  used = int(material_ids.max()) + 1 if T else 1
+
+  def coeffs(arr, k, default):
+    arr = t.ones(used, k) * t.tensor(default, dtype=t.float32) if arr is None else _host(arr)
+    arr = arr[:used]
+    if tuple(arr.shape) != (used, k):
+      raise ValueError(f"render_scene: material coefficients must be [{used}, {k}], got {tuple(arr.shape)}")
+    return arr
+
+  diffuse = coeffs(diffuse_coefficients, 3, 0.8)
+  ambient = coeffs(ambient_coefficients, 3, 0.05)
+  spec = coeffs(specular_coefficient, 4, (0.0, 0.0, 0.0, 2048.0))
+  mats = make_materials(diffuse, ambient, spec[:, :3], spec[:, 3])
+  img = render_batch(v, material_ids, mats.to(dev), [[0, T]], vp[None], image_size, normals=normals,
+                     light_positions=None if light_position is None else _host(light_position)[None],
+                     light_colors=light_color, ambient_light_colors=ambient_light_color,
+                     clear_colors=_host(clear_color)[:3], cull_back_facing=bool(cull_back_facing))[0]
+  return _finish(img, output_type, return_rgb)
+
+
+def voxel_materials(palette) -> t.Tensor:
+  """The voxel renderer's materials f32 [P, 10]: ambient 0, diffuse = palette, specular 0, shininess 1."""
+  return make_materials(palette, 0.0, (0.0, 0.0, 0.0), 1.0)
+
+
+def render_voxel_grid(voxel_grid, view_projection_matrix=None, image_size: Tuple[int, int] = (256, 256),
+                      voxel_to_view_matrix=None, diffuse_coefficients=None, light_position=None,
+                      light_color=(1.0, 1.0, 1.0), ambient_light_color=(0.2, 0.2, 0.2), clear_color=(0, 0, 0),
+                      output_type=t.uint8) -> t.Tensor:
+  """Renders a label grid int32 [D, H, W] as unit cubes (voxel_renderer.render_voxel_grid) -> uint8 [H, W, 3] on the
+  grid's device.  Label l is drawn with diffuse_coefficients[l] (default DEFAULT_COLOR_PALETTE) unless that colour has
+  a negative channel; ambient 0, no specular, no culling.  voxel_to_view_matrix defaults to scale(1 / max(shape)), the
+  camera to get_default_camera_for_mesh of the grid's box.  Only exposed faces are drawn (see voxel_faces)."""
+  g = t.as_tensor(voxel_grid)
+  if g.dim() != 3:
+    raise ValueError(f"render_voxel_grid: voxel_grid must be [D, H, W], got {tuple(g.shape)}")
+  if voxel_to_view_matrix is None:
+    d = 1.0 / max(g.shape)
+    voxel_to_view_matrix = transformations.scale([d, d, d])
+  v2v = _host(voxel_to_view_matrix)
+  if view_projection_matrix is None:
+    box = t.tensor([[[0.0] * 3, [0.0] * 3, [float(s) for s in g.shape[::-1]]]])
+    view_projection_matrix = camera_util.get_default_camera_for_mesh(transformations.transform_mesh(box, v2v))
+  if diffuse_coefficients is None:
+    diffuse_coefficients = DEFAULT_COLOR_PALETTE
+  pal = _host(diffuse_coefficients).reshape(-1, 3)
+  f = voxel_faces(g[None], pal, v2v)
+  img = render_batch(f.triangles, f.material_ids, voxel_materials(pal).to(g.device), [[0, f.triangles.shape[0]]],
+                     _host(view_projection_matrix)[None], image_size, normals=f.normals, normal_modes=[2],
+                     light_positions=None if light_position is None else _host(light_position)[None],
+                     light_colors=light_color, ambient_light_colors=ambient_light_color,
+                     clear_colors=_host(clear_color)[:3], cull_back_facing=False)[0]
+  return _finish(img, output_type)

@@ -563,6 +563,54 @@ int crn_marching_cubes_cpu(const float* grid, const int64_t* strides, int N, int
 int crn_box_filter_cpu(const float* in, const int64_t* strides, float* out, int N, int D, int H, int W, int k,
                        int num_threads);
 
+/* ---------------- rendering (corenet_amd.visualization.render) -----------------
+ * Batched software renderer of triangle soups: I images of H x W, uint8 RGB out[I][H][W][3], row 0 = NDC y = -1.
+ * Image i draws triangles [t0, t1) of the shared buffers triangles [T][3][3] (world space), normals [T][3][3]
+ * (normal_mode 1: per vertex; 2: flat, normals[t][0]; 0: unused, the geometric normal) and material_ids [T] into
+ * materials [M][10] (ambient 3, diffuse 3, specular 3, shininess; an id outside [0, M) shades black).  Coverage, depth
+ * and shading rules: corenet_amd/visualization/render.py and DESIGN section 14.  The winner of a pixel is decided by
+ * (depth, triangle index) alone, so the result does not depend on execution order; GPU and host twin give identical
+ * images when no material has a nonzero specular term (powf may differ by one level otherwise).
+ * inst0: the image's first setup record; images' records are consecutive, inst0 = sum of the earlier (t1 - t0).     */
+#define CRN_RENDER_TILE 16
+typedef struct {
+  float vp[16];              /* view-projection, row major, clip = vp . (p, 1) */
+  float light[3], cam[3], light_color[3], ambient_light[3], clear[3];
+  int32_t cull, normal_mode, t0, t1, inst0, pad[4];
+} crnRenderImage;
+/* GPU, two calls on stream s.  crn_render_bin: setup records [num_inst][16] f32, per-(image, tile) triangle counts
+ * bin_counts int32 [I * tiles] and their exclusive scan bin_offsets int64 [I * tiles + 1] (tiles = ceil(H / 16) *
+ * ceil(W / 16)); the caller reads bin_offsets[I * tiles] and sizes bin_list int32 with it.  crn_render_raster with the
+ * same images, records and bins fills the lists (consuming bin_counts) and writes out.  images: DEVICE
+ * crnRenderImage[I]; max_len = max (t1 - t0).  Neither waits for the GPU.                                        */
+int crn_render_bin(const float* triangles, const crnRenderImage* images, int I, int H, int W, int max_len,
+                   int64_t num_inst, float* records, int32_t* bin_counts, int64_t* bin_offsets, crnStream s);
+int crn_render_raster(const float* triangles, const float* normals, const int32_t* material_ids, const float* materials,
+                      int M, const crnRenderImage* images, int I, int H, int W, int max_len, const float* records,
+                      int32_t* bin_counts, const int64_t* bin_offsets, int32_t* bin_list, uint8_t* out, crnStream s);
+/* Host twin (HOST memory): same contract, one image per task. */
+int crn_render_cpu(const float* triangles, const float* normals, const int32_t* material_ids, const float* materials,
+                   int M, const crnRenderImage* images, int I, int H, int W, uint8_t* out, int num_threads);
+/* Exposed faces of N label grids labels[n][d][h][w] (int32, contiguous) as the voxel renderer draws them: voxel
+ * (x, y, z) = (w, h, d) is a unit cube iff palette[label] (f32 [P][3]) exists and has no negative channel; of its faces
+ * +x, -x, +y, -y, +z, -z only those whose neighbour is not drawn (or outside) are emitted, each as two triangles.
+ * Order: grid, voxel raster order, face order.  count: counts[n] (DEVICE int64 [N]) = triangles of grid n; with
+ * box_matrices (f32 [N][16]) box_out[n] (f32 [N][6], min xyz then max xyz) = bounds of the transformed centres of the
+ * voxels with label != 0 (zeros when there are none).  emit: triangles [T][3][3] through matrices[n] (f32 [N][16],
+ * voxel -> view, no divide), normals [T][3][3] (the flat normal three times), material_ids [T] = material_base + label.
+ * workspace: crn_voxel_faces_workspace_bytes(N, D, H, W), kept between count and emit.                            */
+size_t crn_voxel_faces_workspace_bytes(int N, int D, int H, int W);
+int crn_voxel_faces_count(const int32_t* labels, int N, int D, int H, int W, const float* palette, int P,
+                          const float* box_matrices, float* box_out, void* workspace, size_t workspace_bytes,
+                          int64_t* counts, crnStream s);
+int crn_voxel_faces_emit(const int32_t* labels, int N, int D, int H, int W, const float* palette, int P,
+                         const float* matrices, int material_base, void* workspace, size_t workspace_bytes,
+                         float* triangles, float* normals, int32_t* material_ids, crnStream s);
+/* Host twin: triangles == NULL -> counts (and box_out); else reads counts and writes the faces. */
+int crn_voxel_faces_cpu(const int32_t* labels, int N, int D, int H, int W, const float* palette, int P,
+                        const float* box_matrices, float* box_out, const float* matrices, int material_base,
+                        int64_t* counts, float* triangles, float* normals, int32_t* material_ids, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
