@@ -197,9 +197,8 @@ class HipBackend:
 
   def convt_ximage(self, x: t.Tensor, tr: Optional[Transform], img: Optional[t.Tensor] = None) -> Optional[t.Tensor]:
     """Operand image of T(x) for the parity-walk weight gradient (crn_convt_s2k7_ximage): x [B,16,D,H,W] dense inside a sample.
-    Returns the image (`img` when it is large enough, else a fresh buffer the caller should keep) or None when the path is off
-    (CRN_CT_XIMG=0, deterministic mode)."""
-    if os.environ.get("CRN_CT_XIMG", "1") == "0" or self._deterministic:
+    Returns the image (`img` when it is large enough, else a fresh buffer the caller should keep) or None in deterministic mode."""
+    if self._deterministic:
       return None
     B, cin, D, H, W = x.shape
     assert cin == 16 and x[0].is_contiguous()
@@ -223,7 +222,7 @@ class HipBackend:
       xs, ds = x.storage, dy.storage     # of the layer's input, dy: the space-to-depth view of the output gradient tensor
       xp = xs.data_ptr() + 4 * (x.offset - xs.storage_offset())
       img = ximg                   # (the caller made it earlier, e.g. under the forward pass on its side stream)
-      if img is None and os.environ.get("CRN_CT_XIMG", "1") != "0" and not self._deterministic:
+      if img is None and not self._deterministic:
         # T(x) transformed and split once (crn_convt_s2k7_ximage) instead of in every workgroup of the four parity pairs
         nb = self.lib.crn_convt_s2k7_ximage_bytes(x.B, x.D, x.H, x.W)
         img = self.workspace("ct_ximg", nb, xs.device)

@@ -730,7 +730,7 @@ inline bool vec_ok(int64_t S, std::initializer_list<int64_t> strides, std::initi
 
 inline int nsplit_for(int64_t S, int C, int B) {
   // enough blocks to fill 256 CUs x 8, >= 4096 elements per block
-  static const int kWant = getenv("CRN_BN_WANT") ? atoi(getenv("CRN_BN_WANT")) : 2048;       // tuning aid
+  constexpr int kWant = 2048;
   int64_t want = std::max<int64_t>(1, kWant / std::max(1, C * B));
   int64_t maxs = std::max<int64_t>(1, S / 4096);
   return (int)std::min<int64_t>(std::min(want, maxs), 64);
@@ -836,8 +836,8 @@ extern "C" int crn_batch_renorm_finalize(const double* ws, int nparts, int C, do
                                          float* scale, float* shift, float* saved, crnStream stream) {
   CRN_ENTRY(stream);
   if (!ws || nparts < 1 || nparts > kMaxParts || C < 1 || !(count >= 1.0)) return CRN_EINVAL;
-  static const int kWide = getenv("CRN_BN_FINALIZE_WIDE") ? atoi(getenv("CRN_BN_FINALIZE_WIDE")) : 512;      // parts per channel from which on
-  if (kWide > 0 && nparts >= kWide && (((uintptr_t)ws) & 15) == 0)
+  constexpr int kWide = 512;      // parts per channel from which on
+  if (nparts >= kWide && (((uintptr_t)ws) & 15) == 0)
     hipLaunchKernelGGL(bn_finalize_wide_kernel, dim3(C), dim3(kThreads), 0, (hipStream_t)stream, ws, nparts, C, count,
                        gamma, beta, running_mean, running_var, nbt, eps, momentum, scale, shift, saved);
   else
@@ -906,13 +906,10 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
   // SIMD) on it.  In the decoder's backward those run beside the data-gradient chain all the time: stage 4's two norms (64 / 112
   // channels = workgroups) took 125-150 us each inside the step against ~35 us alone.  The two-pass form (50 / 46 registers, many
   // workgroups) slots in beside them: step 7.30 -> 7.19 ms.  Applies to the pre-ReLU norms (the decoder's; the encoder's run
-  // beside small weight gradients).  CRN_BN_BWD_DEC16: 0 the register form as before, 1 the streaming owner kernel, 2 (default)
-  // two passes, 3 two passes for every norm of that size; CRN_BN_BWD_DEC_MIN: elements per channel from which it applies.
-  static const int dec16 = getenv("CRN_BN_BWD_DEC16") ? atoi(getenv("CRN_BN_BWD_DEC16")) : 2;
-  static const int dec_min = getenv("CRN_BN_BWD_DEC_MIN") ? atoi(getenv("CRN_BN_BWD_DEC_MIN")) : 8192;
-  const bool big_dec = dec16 && (pre_relu || dec16 == 3) && !head && (int64_t)B * S > dec_min;
-  const bool owner_ok = owner_form(S, C, B) && !(big_dec && dec16 >= 2);
-  const bool reg_form = owner_ok && v && (int64_t)B * S <= 16384 && !big_dec;
+  // beside small weight gradients), from 8192 elements per channel on.
+  const bool big_dec = pre_relu && !head && (int64_t)B * S > 8192;
+  const bool owner_ok = owner_form(S, C, B) && !big_dec;
+  const bool reg_form = owner_ok && v && (int64_t)B * S <= 16384;
   if (head) {
     const int rcf = crn_splitk_flush(st);          // (dy is formed here: nothing pending can be meant for this call)
     if (rcf != CRN_OK) return rcf;

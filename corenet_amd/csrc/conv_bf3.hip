@@ -59,8 +59,7 @@ struct Bf3Geom {
   int nchunks, chunks_per_split;
   int ctab;                // entries of the per-channel LDS tables (multiple of 16)
   int mode;                // 0 store, 1 accumulate, 3 split-K partial sums to a dense scratch [split][b][n][pos]
-                           // (+ reduction launch), 4 the same, summed by the last workgroup of each tile
-  crnView yreal; int accumulate_real; int* counters;      // mode 4
+                           // (+ reduction launch)
   int lead;
   int vec_store;
   int n_groups, c_groups;
@@ -69,7 +68,6 @@ struct Bf3Geom {
   const void* wslab;       // weights pre-arranged as slab images (crn_bf3_operands, slab order), or nullptr: w is staged
   int UP;                  // wave-specialised kernel: staging units per patch plane (PH * pw2)
   unsigned magic_UP;
-  int dbg;
   int rowskip;             // 4 x 4 window planes with tap boxes: a tap group = a window row, rows outside the box are skipped
   int half_last;           // the last chunk has <= 4 real channels: 8 taps x 4 channels per MFMA (conv_bf3_kernel, plane_half)
   long long* stamps;       // tuning aid (CRN_BF3_STAMPS=1): shader-clock stamps of workgroup 0, 4 per staging step
@@ -411,7 +409,6 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   auto mark = [&](int i) { if (stamp && step_no < 24) g.stamps[step_no * 8 + i] = (long long)__builtin_amdgcn_s_memtime(); };
   int zd = 0, zend = 0, hrow = 0;
   int chunk = first_step(cbeg, zd, zend, hrow);
-  bool first = true;
   bool fresh = true;                                     // the patch of `chunk` is in registers, not yet in LDS
   if (chunk < cend) {
     patch_issue(chunk * kCK);
@@ -432,106 +429,101 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
     mark(1);
     __syncthreads();                                     // every wave is done reading the LDS of the previous step
     mark(2);
-    if (g.dbg < 3 || first) {
-      if (fresh) patch_commit(c0);
-      weights_commit();
-    }
-    first = false;
+    if (fresh) patch_commit(c0);
+    weights_commit();
     mark(3);
     __syncthreads();
     mark(4);
-    if (nchunk < cend && g.dbg != 2) {
+    if (nchunk < cend) {
       if (nchunk != chunk) patch_issue(nchunk * kCK);    // flies under this slab's MFMAs
       weights_issue(nchunk * kCK, nzd);
     }
     mark(5);
-    if (g.dbg != 1) {
-      // one window plane: every group runs (weights outside a tap box are zero): no control flow between the
-      // groups, so the compiler keeps the next group's LDS reads in flight under this group's MFMAs
-      auto plane = [&](int z, const bf16x8* bh0, const bf16x8* bl0) {
-        const int zoff = z * g.PHW;
-        const int rlo = hrow & 255, rhi = hrow >> 8;
+    // one window plane: every group runs (weights outside a tap box are zero): no control flow between the
+    // groups, so the compiler keeps the next group's LDS reads in flight under this group's MFMAs
+    auto plane = [&](int z, const bf16x8* bh0, const bf16x8* bl0) {
+      const int zoff = z * g.PHW;
+      const int rlo = hrow & 255, rhi = hrow >> 8;
 #pragma unroll
-        for (int gq = 0; gq < NG; ++gq) {
-          if (NG == 4 && g.rowskip && (gq < rlo || gq >= rhi)) continue;   // (workgroup-uniform: a scalar branch)
-          const int off = toff[gq] + zoff;
-          bf16x8 bh[NSUB], bl[NSUB], ah[kMSUB], al[kMSUB];
+      for (int gq = 0; gq < NG; ++gq) {
+        if (NG == 4 && g.rowskip && (gq < rlo || gq >= rhi)) continue;   // (workgroup-uniform: a scalar branch)
+        const int off = toff[gq] + zoff;
+        bf16x8 bh[NSUB], bl[NSUB], ah[kMSUB], al[kMSUB];
+#pragma unroll
+        for (int ns = 0; ns < NSUB; ++ns) {
+          bh[ns] = bh0[(gq * 4 + kk) * NB + ns * 16 + i16];
+          bl[ns] = bl0[(gq * 4 + kk) * NB + ns * 16 + i16];
+        }
+#pragma unroll
+        for (int ms = 0; ms < kMSUB; ++ms) { ah[ms] = Ahi[PA(ms) + (unsigned)off]; al[ms] = Alo[PA(ms) + (unsigned)off]; }
+#pragma unroll
+        for (int ms = 0; ms < kMSUB; ++ms)
 #pragma unroll
           for (int ns = 0; ns < NSUB; ++ns) {
-            bh[ns] = bh0[(gq * 4 + kk) * NB + ns * 16 + i16];
-            bl[ns] = bl0[(gq * 4 + kk) * NB + ns * 16 + i16];
+            mfma3(acc[ms][ns], ah[ms], al[ms], bh[ns], bl[ns]);
+          }
+      }
+    };
+    // HALF CHUNK.  A last chunk with at most 4 real channels (stage_6.c1: 28 = 3 x 8 + 4) multiplies 8 TAPS x 4 channels per
+    // MFMA instead of 4 taps x 8 channels of which half are padding: lane group kk owns taps 8 gq + 2 kk and + 1, its operand
+    // registers are the low halves (channels 0-3: 8 bytes) of the two taps' entries, for the patch and for the weight slab
+    // alike -- two ds_read_b64 per fragment, the same LDS images.  ceil(KHW / 8) groups per plane instead of ceil(KHW / 4):
+    // 4 instead of 7 for a 5 x 5 plane, 125 instead of 140 MFMA triples per sub-tile for stage_6.c1 (the matrix pipe of
+    // this part is power-limited at ~1.4 PFLOP/s under this load -- a lone wave per SIMD issues one MFMA per 28 cycles with
+    // or without its LDS reads, round 4 -- so executed MFMAs, not bubbles, are what is left to remove).
+    auto plane_half = [&](int z, const bf16x8* bh0, const bf16x8* bl0) {
+      typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+      constexpr int NGH = (NG * 4 + 7) / 8;
+      const int zoff = z * g.PHW;
+      auto lo8 = [](const bf16x8* p) { return *reinterpret_cast<const unsigned long long*>(p); };
+      int kk2 = kk;
+      asm volatile("" : "+v"(kk2));                           // (the tap arithmetic below stays inside the step: 5 of a tile's 20)
+#pragma unroll
+      for (int gq = 0; gq < NGH; ++gq) {
+        // (slots KHW .. 4 NG - 1 of the slab hold zero weights; a slot past the slab reads the last of them)
+        const int t0 = min(gq * 8 + 2 * kk2, NG * 4 - 1), t1 = min(gq * 8 + 2 * kk2 + 1, NG * 4 - 1);
+        const int u0 = t0 < g.KHW ? t0 : 0, u1 = t1 < g.KHW ? t1 : 0;
+        const int zh0 = mdiv(u0, g.magic_kw), zh1 = mdiv(u1, g.magic_kw);
+        const int o0 = zh0 * g.PW + (u0 - zh0 * g.kw) + zoff, o1 = zh1 * g.PW + (u1 - zh1 * g.kw) + zoff;
+        const int s0 = t0 * NB + i16, s1 = t1 * NB + i16;
+        bf16x8 bh[NSUB], bl[NSUB];
+#pragma unroll
+        for (int ns = 0; ns < NSUB; ++ns) {
+          bh[ns] = __builtin_bit_cast(bf16x8, (u64x2){lo8(bh0 + s0 + ns * 16), lo8(bh0 + s1 + ns * 16)});
+          bl[ns] = __builtin_bit_cast(bf16x8, (u64x2){lo8(bl0 + s0 + ns * 16), lo8(bl0 + s1 + ns * 16)});
+        }
+        constexpr int MQ = 1;                                  // sub-tiles per pass: the kernel has to stay at 128 registers
+#pragma unroll
+        for (int mh = 0; mh < kMSUB; mh += MQ) {
+          bf16x8 ah[MQ], al[MQ];
+#pragma unroll
+          for (int m = 0; m < MQ; ++m) {
+            ah[m] = __builtin_bit_cast(bf16x8, (u64x2){lo8(Ahi + (PA(mh + m) + (unsigned)o0)), lo8(Ahi + (PA(mh + m) + (unsigned)o1))});
+            al[m] = __builtin_bit_cast(bf16x8, (u64x2){lo8(Alo + (PA(mh + m) + (unsigned)o0)), lo8(Alo + (PA(mh + m) + (unsigned)o1))});
           }
 #pragma unroll
-          for (int ms = 0; ms < kMSUB; ++ms) { ah[ms] = Ahi[PA(ms) + (unsigned)off]; al[ms] = Alo[PA(ms) + (unsigned)off]; }
-#pragma unroll
-          for (int ms = 0; ms < kMSUB; ++ms)
+          for (int m = 0; m < MQ; ++m)
 #pragma unroll
             for (int ns = 0; ns < NSUB; ++ns) {
-              mfma3(acc[ms][ns], ah[ms], al[ms], bh[ns], bl[ns]);
+              mfma3(acc[mh + m][ns], ah[m], al[m], bh[ns], bl[ns]);
             }
-        }
-      };
-      // HALF CHUNK.  A last chunk with at most 4 real channels (stage_6.c1: 28 = 3 x 8 + 4) multiplies 8 TAPS x 4 channels per
-      // MFMA instead of 4 taps x 8 channels of which half are padding: lane group kk owns taps 8 gq + 2 kk and + 1, its operand
-      // registers are the low halves (channels 0-3: 8 bytes) of the two taps' entries, for the patch and for the weight slab
-      // alike -- two ds_read_b64 per fragment, the same LDS images.  ceil(KHW / 8) groups per plane instead of ceil(KHW / 4):
-      // 4 instead of 7 for a 5 x 5 plane, 125 instead of 140 MFMA triples per sub-tile for stage_6.c1 (the matrix pipe of
-      // this part is power-limited at ~1.4 PFLOP/s under this load -- a lone wave per SIMD issues one MFMA per 28 cycles with
-      // or without its LDS reads, round 4 -- so executed MFMAs, not bubbles, are what is left to remove).
-      auto plane_half = [&](int z, const bf16x8* bh0, const bf16x8* bl0) {
-        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-        constexpr int NGH = (NG * 4 + 7) / 8;
-        const int zoff = z * g.PHW;
-        auto lo8 = [](const bf16x8* p) { return *reinterpret_cast<const unsigned long long*>(p); };
-        int kk2 = kk;
-        asm volatile("" : "+v"(kk2));                           // (the tap arithmetic below stays inside the step: 5 of a tile's 20)
-#pragma unroll
-        for (int gq = 0; gq < NGH; ++gq) {
-          // (slots KHW .. 4 NG - 1 of the slab hold zero weights; a slot past the slab reads the last of them)
-          const int t0 = min(gq * 8 + 2 * kk2, NG * 4 - 1), t1 = min(gq * 8 + 2 * kk2 + 1, NG * 4 - 1);
-          const int u0 = t0 < g.KHW ? t0 : 0, u1 = t1 < g.KHW ? t1 : 0;
-          const int zh0 = mdiv(u0, g.magic_kw), zh1 = mdiv(u1, g.magic_kw);
-          const int o0 = zh0 * g.PW + (u0 - zh0 * g.kw) + zoff, o1 = zh1 * g.PW + (u1 - zh1 * g.kw) + zoff;
-          const int s0 = t0 * NB + i16, s1 = t1 * NB + i16;
-          bf16x8 bh[NSUB], bl[NSUB];
-#pragma unroll
-          for (int ns = 0; ns < NSUB; ++ns) {
-            bh[ns] = __builtin_bit_cast(bf16x8, (u64x2){lo8(bh0 + s0 + ns * 16), lo8(bh0 + s1 + ns * 16)});
-            bl[ns] = __builtin_bit_cast(bf16x8, (u64x2){lo8(bl0 + s0 + ns * 16), lo8(bl0 + s1 + ns * 16)});
-          }
-          constexpr int MQ = 1;                                  // sub-tiles per pass: the kernel has to stay at 128 registers
-#pragma unroll
-          for (int mh = 0; mh < kMSUB; mh += MQ) {
-            bf16x8 ah[MQ], al[MQ];
-#pragma unroll
-            for (int m = 0; m < MQ; ++m) {
-              ah[m] = __builtin_bit_cast(bf16x8, (u64x2){lo8(Ahi + (PA(mh + m) + (unsigned)o0)), lo8(Ahi + (PA(mh + m) + (unsigned)o1))});
-              al[m] = __builtin_bit_cast(bf16x8, (u64x2){lo8(Alo + (PA(mh + m) + (unsigned)o0)), lo8(Alo + (PA(mh + m) + (unsigned)o1))});
-            }
-#pragma unroll
-            for (int m = 0; m < MQ; ++m)
-#pragma unroll
-              for (int ns = 0; ns < NSUB; ++ns) {
-                mfma3(acc[mh + m][ns], ah[m], al[m], bh[ns], bl[ns]);
-              }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      };
-      if constexpr (ZS == 1) {
-        if constexpr (kHalf) plane_half(zd, Bhi, Blo);
-        else plane(zd, Bhi, Blo);
-      } else {
-        int z0, z1, hr_;
-        chunk_zrange(c0, z0, z1, hr_);
-        const int zlo = max(zd, z0), zhi = min(zd + ZS, zend);
-#pragma unroll 1
-        for (int z = zlo; z < zhi; ++z) {
-          int zz = z;
-          asm volatile("" : "+v"(zz));                    // keep the planes a real loop (registers: one plane in flight)
-          plane(zz, Bhi + (zz - zd) * (NG * 4 * NB), Blo + (zz - zd) * (NG * 4 * NB));
           __builtin_amdgcn_sched_barrier(0);
         }
+      }
+    };
+    if constexpr (ZS == 1) {
+      if constexpr (kHalf) plane_half(zd, Bhi, Blo);
+      else plane(zd, Bhi, Blo);
+    } else {
+      int z0, z1, hr_;
+      chunk_zrange(c0, z0, z1, hr_);
+      const int zlo = max(zd, z0), zhi = min(zd + ZS, zend);
+#pragma unroll 1
+      for (int z = zlo; z < zhi; ++z) {
+        int zz = z;
+        asm volatile("" : "+v"(zz));                    // keep the planes a real loop (registers: one plane in flight)
+        plane(zz, Bhi + (zz - zd) * (NG * 4 * NB), Blo + (zz - zd) * (NG * 4 * NB));
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
     mark(6);
@@ -604,49 +596,6 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
     }
   }
   if (g.bn_ws) bn_bwd_sums_store<NSUB>(g, smem, bn_s1, bn_s2, wave, kk, i16, n0, tid);
-  if (g.mode == 4) {      // fused split-K reduction by the last workgroup of the tile (see conv_fwd_kernel, mode 4)
-    __threadfence();
-    int* s_last = reinterpret_cast<int*>(smem);           // the channel tables are dead by now
-    __syncthreads();
-    if (tid == 0) {
-      const int id = blockIdx.x + gridDim.x * blockIdx.y;
-      const int ticket = atomicAdd(g.counters + id, 1);
-      const int last = ticket == (int)gridDim.z - 1;
-      if (last) g.counters[id] = 0;
-      *s_last = last;
-    }
-    __syncthreads();
-    if (!*s_last) return;
-    __threadfence();
-    const int64_t slab = (int64_t)g.x.B * g.y.sB;
-    const int nsplit = gridDim.z;
-    const float* sb = g.y.base + (int64_t)b * g.y.sB;
-    float* yr = g.yreal.base + (int64_t)b * g.yreal.sB;
-#pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns) {
-      const int n = n0 + ns * 16 + i16;
-      if (n >= g.y.C) continue;
-      const int64_t co = view_chan(g.y, n), cor = view_chan(g.yreal, n);
-#pragma unroll
-      for (int ms = 0; ms < kMSUB; ++ms) {
-        int s_ = wave * kMSUB + ms;
-        const int sw = s_ % g.nsw; s_ /= g.nsw;
-        const int sh = s_ % g.nsh, sd = s_ / g.nsh;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int p = kk * 4 + r;
-          const int od = d0 + sd, oh = h0 + sh * g.mh + p / g.mw, ow = w0 + sw * g.mw + p % g.mw;
-          if (od < g.y.D && oh < g.y.H && ow < g.y.W) {
-            const float* src = sb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
-            float sum = 0.f;
-            for (int sp = 0; sp < nsplit; ++sp) sum += __builtin_nontemporal_load(src + sp * slab);
-            float* dst = yr + cor + (int64_t)od * g.yreal.sD + (int64_t)oh * g.yreal.sH + (int64_t)ow * g.yreal.sW;
-            *dst = g.accumulate_real ? *dst + sum : sum;
-          }
-        }
-      }
-    }
-  }
 }
 
 template <int NSUB, int XM, int NG, int ZS, bool WS>
@@ -768,7 +717,7 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
     // (the producer is the youngest wave of its SIMD and would lose every issue arbitration against the two consumers:
     // its ~300 VALU / LDS / VMEM instructions per step took 4-5 k cycles that way -- more than the step; with priority
     // they slot in between the MFMAs, which issue from their own pipe)
-    if (g.dbg != 6) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     const int ptid = tid - kWsConsumers * 64;
     const crn_rsrc xrs = make_rsrc(g.x.base + (int64_t)b * g.x.sB);
     XT pv[3][kCK];
@@ -784,7 +733,7 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
       const Bf3WsPlanes w = bf3_ws_planes_at<KD>(T, nch);
       const int c = pz ? w.c1 : w.c0, p = pz ? w.p1 : w.p0;
       const int gd = d0 + p - g.pd;
-      const bool ld = pz < w.n && in_hw && (unsigned)gd < (unsigned)g.x.D && g.dbg != 5;
+      const bool ld = pz < w.n && in_hw && (unsigned)gd < (unsigned)g.x.D;
       msk = ld ? 1u : 0u;
       const int c0 = (cbeg + c) * kCK;
       const unsigned sp = (unsigned)gd * (unsigned)g.x.sD + sp_hw;
@@ -838,7 +787,7 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
       pmark(t, 5);
       wait_loads1d_n<2 * kCK>(pv[S]);
       pmark(t, 6);
-      if (g.dbg != 4) commit(t, pv[S], inm[S]);
+      commit(t, pv[S], inm[S]);
       pmark(t, 7);
     };
     issue(0, pv[0], inm[0]);                                   // the pipeline is two iterations deep before the loop
@@ -919,7 +868,7 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
     if (n >= 0 && n < nsteps) {
       const int c = n / KD, zd = n - c * KD;
       const int zr = __builtin_amdgcn_readfirstlane(zrtab[c]);
-      if (zd >= (zr & 255) && zd < (zr >> 8) && g.dbg != 1) {  // (outside: only structural zeros)
+      if (zd >= (zr & 255) && zd < (zr >> 8)) {  // (outside: only structural zeros)
         const int abase = ((PD * c + zd + sd_w) & (kWsR - 1)) * g.PHW;
         const bf16x8* bh0 = Bhi + (n & 1) * kSlab;
         const bf16x8* bl0 = Blo + (n & 1) * kSlab;
@@ -1068,8 +1017,7 @@ struct Bf3WgGeom {
   int PD, PH, PW, PHW, NP, pw2, nunits, lead;
   int tilesD, tilesH, tilesW, ntiles, tiles_per_split;
   unsigned magic_pw2, magic_PH, magic_kw, magic_KHW;
-  int dbg;
-  int inherit;             // tiles inherit the kd - 1 patch planes they share with the tile below (CRN_BF3_WG_INHERIT=0: off)
+  int inherit;             // tiles inherit the kd - 1 patch planes they share with the tile below
   // tap boxes of the output columns (crnTapBoxes, transposed convolutions): a workgroup whose columns share a (d, h) tap range
   // deals only the window rows inside it to its waves (boxskip; kw == 4: two tap pairs per row)
   int boxskip, n_groups;
@@ -1326,7 +1274,6 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
     stage_commit();
     __syncthreads();
     if (tl + 1 < tend) { tile_origin(tl + 1); stage_issue(); }
-    if (g.dbg == 1) continue;
     if constexpr (!PIPE) {
       // the compiler's own schedule of the reads (measured faster for the 4^3 windows, TPW 4)
       for (int kb = 0; kb < 16; ++kb) {
@@ -1421,11 +1368,9 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
 
 template <int NSUB, int DM, int TPW, int TWT>
 int launch_bf3_wgrad(const Bf3WgGeom& g, dim3 grid, size_t lds, hipStream_t st) {
-  // software-pipelined LDS reads: measured per variant (profiles/r03_wgrad_pipe_ab.txt); CRN_BF3_WG_PIPE = 0 / 1 forces
-  static const int force = getenv("CRN_BF3_WG_PIPE") ? atoi(getenv("CRN_BF3_WG_PIPE")) : -1;
-  static const int force2 = getenv("CRN_BF3_WG_PIPE2") ? atoi(getenv("CRN_BF3_WG_PIPE2")) : -1;   // ... of the 32-column instances only
-  const bool pipe = (NSUB == 2 && force2 >= 0) ? force2 != 0 : force >= 0 ? force != 0 : (NSUB == 1 || (TPW == 8 && TWT == 16));
-  auto k = pipe ? conv_bf3_wgrad_kernel<NSUB, DM, TPW, TWT, true> : conv_bf3_wgrad_kernel<NSUB, DM, TPW, TWT, false>;
+  // software-pipelined LDS reads: measured per variant (profiles/r03_wgrad_pipe_ab.txt)
+  constexpr bool pipe = NSUB == 1 || (TPW == 8 && TWT == 16);
+  auto k = conv_bf3_wgrad_kernel<NSUB, DM, TPW, TWT, pipe>;
   if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k, grid, dim3(kThreads), lds, st, g);
   CRN_CHECK_LAUNCH();
@@ -1584,9 +1529,8 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   g.tilesD = crn_cdiv(y->D, g.TD); g.tilesH = crn_cdiv(y->H, g.TH); g.tilesW = crn_cdiv(y->W, g.TW);
   g.nchunks = crn_cdiv(x->C, kCK);
   g.magic_pw2 = magic20b(g.pw2); g.magic_PH = magic20b(g.PH); g.magic_kw = magic20b(kw);
-  static const bool no_boxes = getenv("CRN_NO_BOXES") != nullptr;
   bool have_nbox = false;
-  if (boxes && !no_boxes) {
+  if (boxes) {
     if (boxes->n_groups > 0 && y->C % boxes->n_groups == 0) { g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box)); have_nbox = true; }
     if (boxes->c_groups > 0 && x->C % boxes->c_groups == 0) { g.c_groups = boxes->c_groups; memcpy(g.c_box, boxes->c_box, sizeof(g.c_box)); }
   }
@@ -1595,7 +1539,7 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   g.ctab = (x->C + 15) & ~15;
   auto lds_of = [&](int nsub, int zs) { return (size_t)(3 * g.ctab * 4) + (size_t)2 * g.NP * 16 + (size_t)2 * zs * g.NG * 4 * nsub * 16 * 16; };
   // N block (NSUB x 16 columns per workgroup), measured per layer with the pre-arranged weight slabs (tools/bf3bench.sh
-  // with CRN_BF3_NSUB = 1 / 2 / 4, profiles/r02_bf3_nsub_sweep.txt): wide blocks re-use the staged patch, narrow ones
+  // with NSUB = 1 / 2 / 4, profiles/r02_bf3_nsub_sweep.txt): wide blocks re-use the staged patch, narrow ones
   // keep two workgroups on a CU and (transposed convolutions) skip more structural zeros.  32 columns is within 10 %
   // of the best everywhere; 64 wins on the 16^3 maps (32 tiles: one big workgroup per tile and split-K over the
   // channels beat four narrow ones: stage_4 -18 ... -33 %) and for few input channels without tap boxes (stage_5.c1
@@ -1606,14 +1550,12 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   else if (Npad <= 32) NSUB = 2;
   else NSUB = ((g.mw == 16 && tiles <= 64) || (!have_nbox && x->C <= 32)) ? 4 : 2;
   while (NSUB > 1 && lds_of(NSUB, 1) > kLdsMax) NSUB >>= 1;
-  if (const char* f = getenv("CRN_BF3_NSUB")) NSUB = atoi(f);
-  if (NSUB != 1 && NSUB != 2 && NSUB != 4) return CRN_EINVAL;
   // Whole-window slabs (ZS = kd: one staging step per chunk instead of one per window plane) were measured
   // SLOWER than plane-by-plane slabs (s6c1 fwd 584 vs 464 us, s5t1 fwd 343 vs 270 us): the long commit phase
   // stalls all eight waves at once, while short steps let the two waves of a SIMD overlap.  ZS stays 1.
   // Also measured and dropped: double-buffered weight slabs with ONE barrier per step (the next slab is written
   // right after the barrier into the idle buffer): no gain on any layer, and the extra 14 KiB of LDS costs
-  // stage_6.c1 forward its second workgroup per CU (556 vs 455 us).  Ablations of that launch (tools/bf3dbg.sh):
+  // stage_6.c1 forward its second workgroup per CU (556 vs 455 us).  Ablations of that launch:
   // 462 us complete, 170 us without the MFMA loop, 438 us without global loads, 420 us without LDS commits --
   // the MFMA + LDS-read phase itself runs at ~60 % of the free-running loop of tools/mfma_bf3_loop.hip.
   // Round 3, again with the pre-arranged slabs (a commit is two LDS writes per item) on the 4^3 windows of the transposed
@@ -1629,7 +1571,6 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   const int64_t blocks = tiles * crn_cdiv(Npad, NSUB * 16);
   int splits = 1;
   if (blocks < 192) splits = (int)std::min<int64_t>(std::min(g.nchunks, 16), crn_cdiv(256, blocks));
-  if (const char* f = getenv("CRN_BF3_SPLITS")) splits = std::max(1, std::min(atoi(f), g.nchunks));
   g.chunks_per_split = crn_cdiv(g.nchunks, splits);
   splits = crn_cdiv(g.nchunks, g.chunks_per_split);
   g.mode = accumulate ? 1 : 0;
@@ -1652,9 +1593,6 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
     if (!scratch) { splits = 1; g.chunks_per_split = g.nchunks; }
     else {
       g.mode = 3;
-      g.yreal = *y; g.accumulate_real = accumulate ? 1 : 0;
-      static const bool sk_launch = getenv("CRN_SPLITK_FUSED") == nullptr;   // default: separate reduction launch
-      if (!sk_launch && (g.counters = crn_splitk_counters((size_t)tiles * crn_cdiv(Npad, NSUB * 16))) != nullptr) g.mode = 4;
       g.y.base = scratch; g.y.chan_off = nullptr;
       g.y.sW = 1; g.y.sH = y->W; g.y.sD = y->H * y->W; g.y.sC = S; g.y.sB = (int64_t)y->C * S;
     }
@@ -1663,26 +1601,20 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   g.vec_store = (g.mw >= 4 && yo.sW == 1 && (yo.W & 3) == 0 && (yo.sH & 3) == 0 && (yo.sD & 3) == 0 && (yo.sB & 3) == 0 &&
                  (yo.sC & 3) == 0 && (((uintptr_t)yo.base) & 15) == 0 && yo.chan_off == nullptr) ? 1 : 0;
   const int64_t tiles_bn = tiles;
-  // two users of this epilogue, each behind its own switch: the BatchRenorm BACKWARD sums of a data gradient
-  // (fuse->x = the norm's input; CRN_BN_BWD_FUSE=0) and the forward STATISTICS of the next norm (fuse->x == nullptr:
-  // crn_conv_fwd_bf3_slabs_stats; CRN_DEC_STATS_FUSE=0), which knows nothing of x / sB_x / ndsum
-  static const bool bn_fuse_off = getenv("CRN_BN_BWD_FUSE") != nullptr && atoi(getenv("CRN_BN_BWD_FUSE")) == 0;
-  static const bool stats_fuse_off = getenv("CRN_DEC_STATS_FUSE") != nullptr && atoi(getenv("CRN_DEC_STATS_FUSE")) == 0;
+  // two users of this epilogue: the BatchRenorm BACKWARD sums of a data gradient (fuse->x = the norm's input)
+  // and the forward STATISTICS of the next norm (fuse->x == nullptr: crn_conv_fwd_bf3_slabs_stats), which knows nothing of
+  // x / sB_x / ndsum
   const bool stats_mode = fuse && fuse->x == nullptr;
-  const bool mode_ok = fuse && (stats_mode ? !stats_fuse_off
-                                           : (!bn_fuse_off && fuse->ndsum <= kThreads && (fuse->sB_x & 3) == 0 &&
-                                              (((uintptr_t)fuse->x) & 15) == 0));
+  const bool mode_ok = fuse && (stats_mode || (fuse->ndsum <= kThreads && (fuse->sB_x & 3) == 0 &&
+                                               (((uintptr_t)fuse->x) & 15) == 0));
   if (mode_ok && splits == 1 && g.vec_store && y->sW == 1 && tiles_bn <= 0x7fffffff &&
       fuse->ws_bytes >= (size_t)y->C * (size_t)tiles_bn * 2 * sizeof(double) && (((int64_t)y->D * y->H * y->W) & 3) == 0) {
     g.bn_x = fuse->x; g.bn_sB = fuse->sB_x; g.bn_S = (int64_t)y->D * y->H * y->W; g.bn_saved = fuse->saved;
     g.bn_pre_relu = fuse->pre_relu; g.bn_ws = fuse->ws; g.bn_dsum = fuse->dsum; g.bn_ndsum = fuse->dsum ? fuse->ndsum : 0;
     fuse->nparts = (int)tiles_bn;
   }
-  g.dbg = getenv("CRN_DBG_MODE") ? atoi(getenv("CRN_DBG_MODE")) : 0;
-  static const bool rowskip_off = getenv("CRN_BF3_ROWSKIP") != nullptr && atoi(getenv("CRN_BF3_ROWSKIP")) == 0;
-  g.rowskip = (!rowskip_off && kh == 4 && kw == 4 && (g.n_groups > 0 || g.c_groups > 0)) ? 1 : 0;
-  static const bool half_off = getenv("CRN_BF3_HALF") != nullptr && atoi(getenv("CRN_BF3_HALF")) == 0;
-  g.half_last = (!half_off && x->C % kCK >= 1 && x->C % kCK <= 4 && ZS == 1) ? 1 : 0;
+  g.rowskip = (kh == 4 && kw == 4 && (g.n_groups > 0 || g.c_groups > 0)) ? 1 : 0;
+  g.half_last = (x->C % kCK >= 1 && x->C % kCK <= 4 && ZS == 1) ? 1 : 0;
 #ifdef CRN_TOOLS
   static const bool want_stamps = getenv("CRN_BF3_STAMPS") != nullptr;
 #else
@@ -1694,11 +1626,6 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
     g.stamps = g_bf3_stamps;
   }
   dim3 grid((unsigned)tiles, (unsigned)crn_cdiv(Npad, NSUB * 16), (unsigned)splits);
-  static const bool dbg = getenv("CRN_DEBUG") != nullptr;
-  if (dbg)
-    fprintf(stderr, "[crn_conv_fwd_bf3] x(C%d %dx%dx%d) y(C%d %dx%dx%d) k%dx%dx%d: NSUB %d ZS %d xmode %d tile %dx%dx%d patch "
-            "%dx%dx%d units %d NG %d grid %ux%ux%u lds %zu\n", x->C, x->D, x->H, x->W, y->C, y->D, y->H, y->W, kd, kh, kw, NSUB,
-            ZS, xmode, g.TD, g.TH, g.TW, g.PD, g.PH, g.PW, g.nunits, g.NG, grid.x, grid.y, grid.z, lds);
   int rc = CRN_EINVAL;
   // the wave-specialised kernel (conv_bf3_ws_kernel): pre-arranged slabs, 4 x 8 x 16 tiles, N blocks of 16 / 32
   // columns, cubic 5^3 / 4^3 windows
@@ -1706,24 +1633,17 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   // of 32 columns on 5^3 windows (stage_6.c1 data gradient 359 -> 336 us, stage_5.c1 forward 181 -> 161 us) -- and loses
   // on the 16-column blocks (stage_6.c1 forward 426 -> 486 us, stage_6.t1 160 -> 190 us): there a step is 2.7 k cycles of
   // MFMA fed by 2.2 k cycles of LDS reads (one A fragment pair per three MFMAs), and the ~0.9 k cycles of DMA issue, slab
-  // wait and barrier per step cost more than two co-resident workgroups of the kernel above lose.  CRN_BF3_WS = 0 / 1:
-  // never / wherever it applies.
-  static const int ws_force = getenv("CRN_BF3_WS") ? atoi(getenv("CRN_BF3_WS")) : -1;
-  const bool ws_on = ws_force >= 0 ? ws_force != 0 : (NSUB == 2 && g.NG == 7);
-  if (ws_on && wslab && xmode == 1 && g.mw == 16 && NSUB <= 2 && g.mode != 4 && kd == (g.NG == 7 ? 5 : 4)) {
+  // wait and barrier per step cost more than two co-resident workgroups of the kernel above lose.
+  if (NSUB == 2 && g.NG == 7 && wslab && xmode == 1 && g.mw == 16 && kd == 5) {
     Bf3Geom gw = g;
     gw.UP = gw.PH * gw.pw2; gw.magic_UP = magic20b(gw.UP);
     const int NB = NSUB * 16;
     const size_t lds_ws = (size_t)(3 * gw.ctab * 4) + 256 + (size_t)2 * kWsR * gw.PHW * 16 + (size_t)4 * gw.NG * 4 * NB * 16;
     const int nch = std::min(g.chunks_per_split, g.nchunks);
     const bool ok = 2 * gw.UP <= kWsPL && lds_ws <= kLdsMax && nch <= 64 &&
-                    (kd == 5 ? bf3_ws_timetable_ok<5>(nch) : bf3_ws_timetable_ok<4>(nch));
+                    bf3_ws_timetable_ok<5>(nch);
     if (ok) {
-      if (dbg) fprintf(stderr, "[crn_conv_fwd_bf3] wave-specialised: %d chunks x %d planes, lds %zu\n", nch, kd, lds_ws);
-#define CRN_BF3_WS_CASE(N, X, G) if (NSUB == N && xmode == X && gw.NG == G) rc = launch_bf3_ws<N, X, G>(gw, grid, lds_ws, st);
-      CRN_BF3_WS_CASE(1, 1, 7) CRN_BF3_WS_CASE(2, 1, 7)
-      CRN_BF3_WS_CASE(1, 1, 4) CRN_BF3_WS_CASE(2, 1, 4)
-#undef CRN_BF3_WS_CASE
+      rc = launch_bf3_ws<2, 1, 7>(gw, grid, lds_ws, st);
       if (rc == CRN_OK && g.mode == 3) rc = finish_splits();
       return rc;
     }
@@ -1779,32 +1699,22 @@ extern "C" int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* 
   g.magic_pw2 = magic20b(g.pw2); g.magic_PH = magic20b(g.PH); g.magic_kw = magic20b(kw); g.magic_KHW = magic20b(g.KHW);
   if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * g.T * Npad * 4, st));
   int NSUB = (Npad % 32 == 0) ? 2 : 1;
-  if (const char* f = getenv("CRN_BF3_WG_NSUB")) NSUB = atoi(f);
-  if (NSUB != 1 && NSUB != 2) return CRN_EINVAL;
   const int NB = NSUB * 16;
   const size_t lds = 1024 + (size_t)2 * g.NP * 16 + (size_t)2 * kWgTile * NB * 2;
   if (lds > 160 * 1024 - 512) return CRN_EINVAL;
   const int cblocks = crn_cdiv(x->C, kCK), nblocks = crn_cdiv(Npad, NB);
-  static const int kBlocks = getenv("CRN_BF3_WG_BLOCKS") ? atoi(getenv("CRN_BF3_WG_BLOCKS")) : 256;
+  constexpr int kBlocks = 256;
   int splits = std::max(1, std::min(g.ntiles, kBlocks / std::max(1, cblocks * nblocks)));
   if (crn_deterministic()) splits = 1;                       // one workgroup per dw element: one add, no order to vary
   g.tiles_per_split = crn_cdiv(g.ntiles, splits);
   splits = crn_cdiv(g.ntiles, g.tiles_per_split);
-  g.dbg = getenv("CRN_DBG_MODE") ? atoi(getenv("CRN_DBG_MODE")) : 0;
-  static const int inherit_env = getenv("CRN_BF3_WG_INHERIT") ? atoi(getenv("CRN_BF3_WG_INHERIT")) : 1;
   // the in-LDS plane copy [TDT, PD) -> [0, PD - TDT) runs on all threads at once: only disjoint ranges (kd - 1 <= TDT) may
   // inherit (every model layer; a (7,3,3) window over 4-plane tiles would race -- ADVICE r5), others stage full patches
-  g.inherit = (inherit_env && kd - 1 <= TDT) ? 1 : 0;
-  static const bool boxskip_off = getenv("CRN_BF3_WG_BOXSKIP") != nullptr && atoi(getenv("CRN_BF3_WG_BOXSKIP")) == 0;
-  if (boxes && !boxskip_off && boxes->n_groups > 0 && dy->C % boxes->n_groups == 0 && kw == 4) {
+  g.inherit = (kd - 1 <= TDT) ? 1 : 0;
+  if (boxes && boxes->n_groups > 0 && dy->C % boxes->n_groups == 0 && kw == 4) {
     g.boxskip = 1; g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box));
   }
   dim3 grid((unsigned)cblocks, (unsigned)nblocks, (unsigned)splits);
-  static const bool dbg = getenv("CRN_DEBUG") != nullptr;
-  if (dbg)
-    fprintf(stderr, "[crn_conv_wgrad_bf3] x(C%d %dx%dx%d) dy(C%d %dx%dx%d) k%dx%dx%d: NSUB %d dmode %d TPW %d grid %ux%ux%u "
-            "tiles/split %d lds %zu\n", x->C, x->D, x->H, x->W, dy->C, dy->D, dy->H, dy->W, kd, kh, kw, NSUB, dmode, TPW,
-            grid.x, grid.y, grid.z, g.tiles_per_split, lds);
 #define CRN_BF3WG_CASE(N, D, P, W) if (NSUB == N && dmode == D && TPW == P && TWT == W) return launch_bf3_wgrad<N, D, P, W>(g, grid, lds, st);
   CRN_BF3WG_CASE(1, 1, 8, 16) CRN_BF3WG_CASE(2, 1, 8, 16)
   CRN_BF3WG_CASE(1, 2, 4, 16) CRN_BF3WG_CASE(2, 2, 4, 16)

@@ -48,8 +48,8 @@ struct E2dGeom {
   int nchunks, chunks_per_split;
   int tab;                // entries of the scale / shift tables in LDS (channels of one split)
   int mode;               // 0 store, 1 accumulate (read-modify-write), 3 split-K partial sums [split][b][n][pos]
-  int dbg;                // tuning aid (CRN_E2D_DBG): 1 return at once, 2 no chunk loop, 4 no MFMAs, 8 no stores,
-                          // 16 shader-clock stamps of workgroup 0 / wave 0 into stamps[] (crn_e2d_debug_stamps)
+  int dbg;                // tools build only (CRN_E2D_DBG=16): shader-clock stamps of workgroup 0 / wave 0 into stamps[]
+                          // (crn_e2d_debug_stamps); zero in the product library
   long long* stamps;
 };
 
@@ -764,12 +764,14 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
   if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
   g.wop = wop; g.bias = bias; g.bias_sB = bias_sB;
   g.ntn = Npad / 16; g.nblk = x->C / 32; g.ph = ph; g.pw = pw;
-  static const int dbg = getenv("CRN_E2D_DBG") ? atoi(getenv("CRN_E2D_DBG")) : 0;
-  g.dbg = dbg;
-  if (dbg & 16) {
+#ifdef CRN_TOOLS
+  static const bool want_stamps = getenv("CRN_E2D_DBG") && (atoi(getenv("CRN_E2D_DBG")) & 16);
+  if (want_stamps) {
     if (!g_stamps) CRN_HIP(hipMalloc(&g_stamps, 32 * sizeof(long long)));
     g.stamps = g_stamps;
+    g.dbg = 16;
   }
+#endif
   int TW = 16, CB = 1;
   int64_t tiles;
   if (k3) {
@@ -788,11 +790,9 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
     g.nchunks = (g.nblk + CB - 1) / CB;
   }
   const int64_t base_blocks = tiles * x->B * (y->C / 64);
-  static const int kFill = getenv("CRN_E2D_FILL") ? atoi(getenv("CRN_E2D_FILL")) : 256;
-  static const int force_splits = getenv("CRN_E2D_SPLITS") ? atoi(getenv("CRN_E2D_SPLITS")) : 0;
+  constexpr int kFill = 256;
   int splits = 1;
   while (base_blocks * splits < kFill && splits * 2 <= g.nchunks && splits < 16) splits *= 2;
-  if (force_splits > 0) splits = std::min(force_splits, g.nchunks);
   g.chunks_per_split = (g.nchunks + splits - 1) / splits;
   splits = (g.nchunks + g.chunks_per_split - 1) / g.chunks_per_split;
   g.tab = g.tr.scale ? g.chunks_per_split * CB * 32 : 0;
@@ -864,7 +864,7 @@ extern "C" int crn_conv_wgrad_2d_bf3(const crnView* x, const crnInTransform* tr,
     g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S; g.H = x->H; g.W = x->W;
     g.ksteps = (int)((int64_t)x->B * S / 32);
     const int tiles = crn_cdiv(3 * x->C, 32) * crn_cdiv(dy->C, 32);
-    static const int kFill3 = getenv("CRN_WG3_FILL") ? atoi(getenv("CRN_WG3_FILL")) : 512;
+    constexpr int kFill3 = 512;
     int splits = std::max(1, std::min(g.ksteps / 8, crn_cdiv(kFill3, tiles)));
     if (crn_deterministic()) splits = 1;
     g.ksteps_per_block = crn_cdiv(g.ksteps, splits);
@@ -883,7 +883,7 @@ extern "C" int crn_conv_wgrad_2d_bf3(const crnView* x, const crnInTransform* tr,
   g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S;
   g.ksteps = (int)((int64_t)x->B * S / 32);
   const int tiles = crn_cdiv(x->C, 64) * crn_cdiv(dy->C, 32);
-  static const int kFill = getenv("CRN_WG1_FILL") ? atoi(getenv("CRN_WG1_FILL")) : 512;
+  constexpr int kFill = 512;
   int splits = std::max(1, std::min(g.ksteps / 8, crn_cdiv(kFill, tiles)));       // >= 2 K steps per wave
   if (crn_deterministic()) splits = 1;
   g.ksteps_per_block = crn_cdiv(g.ksteps, splits);

@@ -49,14 +49,10 @@ struct PwGeom {
   int bias_sB, mode;
   int splits, cps;                 // split-K: blockIdx.z = split*B + b, cps input channels per split (multiple
                                    // of 32); partial sums go to the dense scratch y (mode 0), split*B + b as batch
-  // fused reduction (counters != nullptr): the last workgroup of a tile adds the splits up and writes yr
-  float* yr; int64_t yr_sB, yr_sC, yr_sP; int yr_accumulate; int* counters;
   long long* stamps;               // tuning aid (CRN_PW_STAMPS=1): shader-clock stamps of workgroup 0
-  int ablate;                      // tuning aid (CRN_PW_ABLATE bits): 1 no MFMAs, 2 no global loads, 4 no stores, 8 no LDS commit
 };
 
-// NS = 16-column blocks per workgroup (2: 64 x 32 tiles; 4: 64 x 64 tiles -- half the workgroups and half the
-// re-reads of x for the wide layers)
+// NS = 16-column blocks per workgroup (2: 64 x 32 tiles)
 constexpr int kPwTab = 2048;        // channels of one workgroup (its split's range) whose scale / shift are staged in LDS
 template <int NS>
 __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
@@ -65,7 +61,7 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   __shared__ __attribute__((aligned(16))) float ldsA[KC * SA];
   __shared__ __attribute__((aligned(16))) float ldsB[KC * SB];
   crn_kernargs_now(g.x, g.y, g.w, g.bias, g.tr.scale, g.tr.shift, g.tr.pre_relu, g.tr.post_relu, g.B, g.C, g.N, g.Npad,
-                   g.S, g.xsB, g.ysB, g.ysC, g.ysP, g.bias_sB, g.mode, g.splits, g.cps, g.counters);
+                   g.S, g.xsB, g.ysB, g.ysC, g.ysP, g.bias_sB, g.mode, g.splits, g.cps);
   const long long t_entry = (long long)__builtin_amdgcn_s_memtime();
   const long long r_entry = (long long)__builtin_amdgcn_s_memrealtime();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -103,13 +99,13 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
 #pragma unroll
     for (int q = 0; q < NRA; ++q) {
       const int c_a = c0 + ka + q * 16;
-      const unsigned off = (a_ok && c_a < cend && !(g.ablate & 2)) ? (unsigned)(c_a * g.S + m0 + ca) * 4u : kOOBo;
+      const unsigned off = (a_ok && c_a < cend) ? (unsigned)(c_a * g.S + m0 + ca) * 4u : kOOBo;
       crnk::crn_bload4(pa_[q], xrs, off);
     }
 #pragma unroll
     for (int q = 0; q < NRB; ++q) {
       const int c_b = c0 + kb + q * BROWS;
-      const unsigned off = (b_ok && c_b < cend && !(g.ablate & 2)) ? (unsigned)(c_b * g.Npad + n0 + cb) * 4u : kOOBo;
+      const unsigned off = (b_ok && c_b < cend) ? (unsigned)(c_b * g.Npad + n0 + cb) * 4u : kOOBo;
       crnk::crn_bload4(pb_[q], wrs, off);
     }
   };
@@ -144,17 +140,14 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   auto step = [&](int c0, f32x4 (&pa_)[NRA], f32x4 (&pb_)[NRB]) {
     wait_slot(pa_, pb_);
     mark();
-    if (!(g.ablate & 8)) {
     __syncthreads();                                   // (first step: the tables; later: the previous chunk's MFMA reads)
 #pragma unroll
     for (int q = 0; q < NRA; ++q) *reinterpret_cast<f32x4*>(ldsA + (ka + q * 16) * SA + ca) = xform(pa_[q], c0 + ka + q * 16);
 #pragma unroll
     for (int q = 0; q < NRB; ++q) *reinterpret_cast<f32x4*>(ldsB + (kb + q * BROWS) * SB + cb) = pb_[q];
     __syncthreads();
-    }
     mark();
     issue(c0 + 2 * KC, pa_, pb_);                      // this slot's registers are free: the chunk after the next
-    if (g.ablate & 1) { mark(); return; }
     const float* pa = ldsA + kk * SA + wave * 16 + i16;
     const float* pb = ldsB + kk * SB + i16;
 #pragma unroll
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   }
   // D: rows kk*4..kk*4+3 = 4 consecutive positions, col i16 = channel -> one float4 per lane
   const int m = m0 + wave * 16 + kk * 4;
-  if (m < g.S && !(g.ablate & 4)) {
+  if (m < g.S) {
 #pragma unroll
     for (int ns = 0; ns < NS; ++ns) {
       const int n = n0 + ns * 16 + i16;
@@ -204,163 +197,6 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
     g.stamps[31] = (long long)__builtin_amdgcn_s_memtime() - t_entry;
     g.stamps[30] = (long long)__builtin_amdgcn_s_memrealtime() - r_entry;      // 100 MHz: cycles / this = shader clock
   }
-  if (g.counters) {       // fused split-K reduction: see conv_fwd_kernel (mode 4)
-    __threadfence();
-    __shared__ int s_last;
-    __syncthreads();
-    if (tid == 0) {
-      const int id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * b);
-      const int ticket = atomicAdd(g.counters + id, 1);
-      const int last = ticket == g.splits - 1;
-      if (last) g.counters[id] = 0;
-      s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    if (m < g.S) {
-      const int64_t slab = (int64_t)g.B * g.ysB;
-#pragma unroll
-      for (int ns = 0; ns < NS; ++ns) {
-        const int n = n0 + ns * 16 + i16;
-        if (n < g.N) {
-          const float* src = g.y + (int64_t)b * g.ysB + (int64_t)n * g.ysC + m;      // scratch: dense [n][pos]
-          f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-          for (int sp = 0; sp < g.splits; ++sp) sum += __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + sp * slab));
-          float* dst = g.yr + (int64_t)b * g.yr_sB + (int64_t)n * g.yr_sC + (int64_t)m * g.yr_sP;
-          if (g.yr_sP == 1) {
-            if (g.yr_accumulate) sum += *reinterpret_cast<const f32x4*>(dst);
-            *reinterpret_cast<f32x4*>(dst) = sum;
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dst[i * g.yr_sP] = g.yr_accumulate ? dst[i * g.yr_sP] + sum[i] : sum[i];
-          }
-        }
-      }
-    }
-  }
-}
-
-// --------------------------- pointwise convolutions, operands straight from HBM -------------------------------
-// The kernel above stages K chunks of 64 channels through LDS, two barriers per chunk, and every chunk waits out most
-// of a memory latency (~2 us on a busy chip): 11-19 us per launch for layers whose FLOPs and bytes are worth 3-5 us
-// -- 80 launches, 1.1 ms of a 8 ms training step (profiles/r02_bench_kernel_stats.csv, its top line).  This one has no
-// staging at all:
-//   * NCHW activations are K-major for the A operand and the packed weights [Cin][Npad] for the B operand once the
-//     16 rows / 16 columns of an MFMA tile are taken with stride 4: lane (i16, kk) loads ONE float4 = positions
-//     p0 + 4*i16 .. +3 of channel c + kk, and element j of it is row i16 of M tile j (positions p0 + 4*i + j); the
-//     same for the weights (columns n0 + 4*i + jn).  One A float4 and one B float4 per lane feed 16
-//     v_mfma_f32_16x16x4_f32 (4 M tiles x 4 N tiles, K = 4 channels): a wave owns a 64 position x 64 column tile, all
-//     loads are full 256-byte rows, and nothing goes through LDS on the way in.
-//   * Work split: a workgroup = NW waves on one 64 x 64 tile, wave w takes the 16-channel groups w, w + NW, ... of
-//     the workgroup's K slice (GPW groups per wave, all their loads issued at once: one memory latency per
-//     workgroup), then the NW partial tiles are added up through LDS (one barrier) and stored as float4 rows.
-//     Layers with few tiles split K over workgroups as well (partial sums to the split-K scratch, summed by the
-//     BatchRenorm launch that follows -- crn_splitk_defer -- or by the reduction launch).
-//   * The BatchRenorm-apply + ReLU of the producer is applied to the A registers (scale / shift of the lane's channel).
-// fp32 MFMA like the kernel above: same products, different summation order (2e-5 of the output range in the tests).
-struct Pw2Geom {
-  const float* x; const float* w; const float* bias; float* y;
-  crnInTransform tr;
-  int B, C, N, Npad, S, tilesS;
-  int64_t xsB, ysB, ysC;
-  int bias_sB, mode;           // mode 1: y += result
-  int ksl, ksplits;            // channels per workgroup slice (multiple of 16), slices; slices > 1: y is the scratch,
-};                             // batch index split * B + b, no bias except slice 0
-
-template <int NW, int GPW>
-__global__ __launch_bounds__(NW * 64) void pw2_kernel(Pw2Geom g) {
-  crn_kernargs_now(g.x, g.w, g.bias, g.y, g.tr.scale, g.tr.shift, g.tr.pre_relu, g.tr.post_relu, g.B, g.C, g.N, g.Npad,
-                   g.S, g.tilesS, g.xsB, g.ysB, g.ysC, g.bias_sB, g.mode, g.ksl, g.ksplits);
-  extern __shared__ __attribute__((aligned(16))) f32x4 red[];        // [NW][16][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i16 = lane & 15, kk = lane >> 4;
-  const int b = blockIdx.x / g.tilesS, p0 = (blockIdx.x - b * g.tilesS) * 64;
-  const int n0 = blockIdx.y * 64;
-  const int split = blockIdx.z;
-  const int cbeg = split * g.ksl, cend = min(g.C, cbeg + g.ksl);
-  const __amdgpu_buffer_rsrc_t xrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.x + (int64_t)b * g.xsB), 0, g.C * g.S * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.w), 0, g.C * g.Npad * 4, 0x00020000);
-  const bool p_ok = p0 + 4 * i16 < g.S, n_ok = n0 + 4 * i16 < g.Npad;
-  const bool has_tr = g.tr.scale != nullptr;
-  f32x4 av[GPW][4], bv[GPW][4];
-  float sc[GPW][4], sh[GPW][4];
-  constexpr unsigned kOut = 0x80000000u;                             // past the buffer: reads 0
-#pragma unroll
-  for (int t = 0; t < GPW; ++t)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int c = cbeg + 16 * (wave + NW * t) + 4 * q + kk;
-      const bool ok = c < cend;
-      av[t][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-          xrs, (ok && p_ok) ? (unsigned)(c * g.S + p0 + 4 * i16) * 4u : kOut, 0, 0));
-      bv[t][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-          wrs, (ok && n_ok) ? (unsigned)(c * g.Npad + n0 + 4 * i16) * 4u : kOut, 0, 0));
-      sc[t][q] = (has_tr && ok) ? g.tr.scale[c] : 1.f;
-      sh[t][q] = (has_tr && ok) ? g.tr.shift[c] : 0.f;
-    }
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn) acc[j][jn] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int t = 0; t < GPW; ++t)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4 a = av[t][q];
-      if (has_tr) {
-        const int c = cbeg + 16 * (wave + NW * t) + 4 * q + kk;
-        if (c < cend && p_ok) {                                      // (channels / positions past the end stay 0)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float v = a[j];
-            if (g.tr.pre_relu) v = fmaxf(v, 0.f);
-            v = v * sc[t][q] + sh[t][q];
-            if (g.tr.post_relu) v = fmaxf(v, 0.f);
-            a[j] = v;
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) acc[j][jn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], bv[t][q][jn], acc[j][jn], 0, 0, 0);
-    }
-  // D row kk*4 + r of M tile j = position p0 + 4*(kk*4 + r) + j, col i16 of N tile jn = column n0 + 4*i16 + jn: the four
-  // M tiles of one (jn, r) are four consecutive positions -> one float4 per (jn, r) and lane, in output order
-#pragma unroll
-  for (int jn = 0; jn < 4; ++jn)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      red[(wave * 16 + jn * 4 + r) * 64 + lane] = (f32x4){acc[0][jn][r], acc[1][jn][r], acc[2][jn][r], acc[3][jn][r]};
-  __syncthreads();
-  constexpr int EPW = 16 / NW;                                       // (jn, r) pairs summed and stored by each wave
-#pragma unroll
-  for (int e = 0; e < EPW; ++e) {
-    const int pr = wave * EPW + e, jn = pr >> 2, r = pr & 3;
-    f32x4 v = red[pr * 64 + lane];
-#pragma unroll
-    for (int w2 = 1; w2 < NW; ++w2) v += red[(w2 * 16 + pr) * 64 + lane];
-    const int n = n0 + 4 * i16 + jn, p = p0 + 16 * kk + 4 * r;
-    if (n < g.N && p < g.S) {
-      if (g.bias && split == 0) v += g.bias[(int64_t)b * g.bias_sB + n];
-      float* dst = g.y + (int64_t)(split * g.B + b) * g.ysB + (int64_t)n * g.ysC + p;
-      if (g.mode == 1) v += *reinterpret_cast<const f32x4*>(dst);
-      *reinterpret_cast<f32x4*>(dst) = v;
-    }
-  }
-}
-
-template <int NW, int GPW>
-int launch_pw2(const Pw2Geom& g, dim3 grid, hipStream_t st) {
-  auto k = pw2_kernel<NW, GPW>;
-  const size_t lds = (size_t)NW * 16 * 64 * 16;
-  if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
 }
 
 // --------------------------- dense layers on 1^3 grids ------------------------------------------------------
@@ -608,20 +444,6 @@ float* splitk_scratch(size_t floats, hipStream_t st) {
   return sl->buf;
 }
 
-// arrival counters of the fused split-K reduction (mode 4): zero at allocation, every call leaves them zero
-int* splitk_counters(size_t n) {
-  constexpr int kMaxDev = 16;
-  constexpr size_t kCap = 1 << 16;
-  static int* buf[kMaxDev] = {};
-  int dev = 0;
-  if (n > kCap || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
-  if (!buf[dev]) {
-    if (hipMalloc(&buf[dev], kCap * sizeof(int)) != hipSuccess) { buf[dev] = nullptr; return nullptr; }
-    if (hipMemset(buf[dev], 0, kCap * sizeof(int)) != hipSuccess) return nullptr;
-  }
-  return buf[dev];
-}
-
 int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 unsigned magic20(int d) { return (unsigned)(((1u << 20) + d - 1) / d); }
 // staging slots (planes padded to a power of two) needed for nplanes planes of `plane` elements
@@ -772,7 +594,6 @@ extern "C" int crn_splitk_release(crnStream stream) {
   }
   return CRN_OK;
 }
-int* crn_splitk_counters(size_t n) { return splitk_counters(n); }
 int crn_splitk_reduce(const crnView& y, const float* scratch, int splits, int accumulate, hipStream_t st) {
   const int64_t ytot = (int64_t)y.B * y.C * y.D * y.H * y.W;
   const int64_t per_b = (int64_t)y.C * y.D * y.H * y.W;
@@ -835,45 +656,6 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
       Sx == (int64_t)y->D * y->H * y->W && (Sx & 3) == 0 && (((uintptr_t)w) & 15) == 0 &&
       (int64_t)x->C * Sx * 4 < ((int64_t)1 << 31) && (int64_t)x->C * Npad * 4 < ((int64_t)1 << 31) &&
       (!tr || !tr->scale || x->C <= kPwTab)) {           // (buffer offsets of the hand-tracked loads; the LDS tables)
-    static const bool pw2_on = getenv("CRN_PW2") && atoi(getenv("CRN_PW2")) != 0;   // measured (tools/pw_trace.sh, profiles/r03_pw_trace.txt): 13-15 us per layer like the staged kernel -- both sit at ~38 TF/s on these 0.5 GFLOP launches -- plus a split-K reduction where it splits: off by default
-    if (pw2_on && plain_view(*y) && (x->C & 15) == 0 && x->C >= 64 && (y->sB & 3) == 0 && (y->sC & 3) == 0) {
-      // operands straight from HBM (pw2_kernel).  Decomposition: 64 x 64 tiles; 8 waves per workgroup (4 for 64 input
-      // channels), one or two 16-channel groups per wave; K slices of NW * GPW * 16 channels over blockIdx.z
-      Pw2Geom q{};
-      q.x = x->base; q.w = w; q.bias = bias; q.y = y->base;
-      q.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
-      q.B = x->B; q.C = x->C; q.N = y->C; q.Npad = Npad; q.S = (int)Sx; q.tilesS = (int)crn_cdiv(Sx, 64);
-      q.xsB = x->sB; q.ysB = y->sB; q.ysC = y->sC; q.bias_sB = bias_sB; q.mode = accumulate ? 1 : 0;
-      const int groups = x->C / 16;
-      const int NW = groups >= 8 ? 8 : 4;
-      const int64_t tiles = (int64_t)q.tilesS * x->B * crn_cdiv(y->C, 64);
-      static const int pw2_fill = getenv("CRN_PW2_FILL") ? atoi(getenv("CRN_PW2_FILL")) : 384;
-      int GPW = (groups >= 2 * NW && tiles * crn_cdiv(groups, 2 * NW) >= pw2_fill) ? 2 : 1;
-      if (const char* f = getenv("CRN_PW2_GPW")) GPW = atoi(f) == 2 ? 2 : 1;
-      q.ksl = NW * GPW * 16;
-      q.ksplits = crn_cdiv(x->C, q.ksl);
-      float* scratch2 = nullptr;
-      if (q.ksplits > 1) {
-        const int64_t ytot2 = (int64_t)y->B * y->C * Sx;
-        scratch2 = splitk_scratch((size_t)q.ksplits * ytot2, st);
-        if (scratch2) { q.y = scratch2; q.ysB = (int64_t)y->C * Sx; q.ysC = Sx; q.mode = 0; }
-      }
-      if (q.ksplits == 1 || scratch2) {
-        const dim3 grid((unsigned)(q.tilesS * x->B), (unsigned)crn_cdiv(y->C, 64), (unsigned)q.ksplits);
-        int rc2;
-        if (NW == 8) rc2 = GPW == 2 ? launch_pw2<8, 2>(q, grid, st) : launch_pw2<8, 1>(q, grid, st);
-        else rc2 = launch_pw2<4, 1>(q, grid, st);
-        if (rc2 != CRN_OK) return rc2;
-        if (q.ksplits > 1) {
-          if (armed && !accumulate && y->sB == (int64_t)y->C * Sx) {
-            crn_splitk_set_pending(*y, scratch2, q.ksplits, st);
-            return CRN_OK;
-          }
-          return crn_splitk_reduce(*y, scratch2, q.ksplits, accumulate, st);
-        }
-        return CRN_OK;
-      }
-    }
     PwGeom p{};
     p.x = x->base; p.y = y->base; p.w = w; p.bias = bias;
     p.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
@@ -883,35 +665,24 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
     p.splits = 1; p.cps = (x->C + 63) & ~63;
     // long reductions over few positions (stage4/5 of the encoder: K = 1024..2048, 64..256 positions per sample):
     // split the channels over blocks, partial sums to the split-K scratch, one reduction launch
-    // 64-column tiles (CRN_PW_NS=4) were measured equal to 32-column ones on the whole step (10.07 vs 10.04 ms): these
-    // launches are latency bound, not operand-traffic bound; 32 stays the default
-    static const char* pw_ns_env = getenv("CRN_PW_NS");
-    const bool wide = pw_ns_env && atoi(pw_ns_env) == 4 && Npad % 64 == 0;
-    const int BNh = wide ? 64 : 32;
+    // (64-column tiles were measured equal to 32-column ones on the whole step, 10.07 vs 10.04 ms: these launches are
+    // latency bound, not operand-traffic bound)
+    constexpr int BNh = 32, pw_blocks = 256, pw_fill = 512, pw_minc = 128;
     const int64_t blocks = crn_cdiv(Sx, 64) * crn_cdiv(y->C, BNh) * (int64_t)x->B;
     const int64_t ytot = (int64_t)y->B * y->C * Sx;
-    static const bool pw_nosplit = getenv("CRN_PW_NOSPLIT") != nullptr;
     float* scratch = nullptr;
-    static const int pw_blocks = getenv("CRN_PW_BLOCKS") ? atoi(getenv("CRN_PW_BLOCKS")) : 256;   // tuning aids
-    static const int pw_fill = getenv("CRN_PW_FILL") ? atoi(getenv("CRN_PW_FILL")) : 512;
-    static const int pw_minc = getenv("CRN_PW_MINC") ? atoi(getenv("CRN_PW_MINC")) : 128;
-    if (splits < 1 && !pw_nosplit && blocks < pw_blocks && x->C >= 2 * pw_minc) {
+    if (splits < 1 && blocks < pw_blocks && x->C >= 2 * pw_minc) {
       int sp = (int)std::min<int64_t>(std::min<int64_t>(x->C / pw_minc, 16), crn_cdiv(pw_fill, blocks));
       if (sp > 1) {
         p.cps = (crn_cdiv(x->C, sp) + 31) & ~31;
         sp = crn_cdiv(x->C, p.cps);
         if (sp > 1 && (scratch = splitk_scratch((size_t)sp * ytot, st)) != nullptr) {
-          p.yr = y->base; p.yr_sB = y->sB; p.yr_sC = y->sC; p.yr_sP = y->sW; p.yr_accumulate = accumulate ? 1 : 0;
           p.splits = sp; p.y = scratch; p.ysB = (int64_t)y->C * Sx; p.ysC = Sx; p.ysP = 1; p.mode = 0;
-          static const bool sk_launch_pw = getenv("CRN_SPLITK_FUSED") == nullptr;
-          if (!sk_launch_pw) p.counters = splitk_counters((size_t)crn_cdiv(Sx, 64) * crn_cdiv(y->C, BNh) * x->B);
         } else {
           p.cps = (x->C + 31) & ~31;
         }
       }
     }
-    static const int pw_ablate = getenv("CRN_PW_ABLATE") ? atoi(getenv("CRN_PW_ABLATE")) : 0;
-    p.ablate = pw_ablate;
 #ifdef CRN_TOOLS
     static const bool want_stamps = getenv("CRN_PW_STAMPS") != nullptr;
 #else
@@ -926,10 +697,9 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
     }
     dim3 grid((unsigned)crn_cdiv(Sx, 64), (unsigned)crn_cdiv(y->C, BNh), (unsigned)(x->B * p.splits));
     const size_t tab_bytes = p.tr.scale ? (size_t)2 * p.cps * sizeof(float) : 0;
-    if (wide) hipLaunchKernelGGL(pointwise_fwd_kernel<4>, grid, dim3(256), tab_bytes, st, p);
-    else hipLaunchKernelGGL(pointwise_fwd_kernel<2>, grid, dim3(256), tab_bytes, st, p);
+    hipLaunchKernelGGL(pointwise_fwd_kernel<2>, grid, dim3(256), tab_bytes, st, p);
     CRN_CHECK_LAUNCH();
-    if (p.splits > 1 && !p.counters) {
+    if (p.splits > 1) {
       if (armed && !accumulate && plain_view(*y) && y->sB == (int64_t)y->C * Sx) {
         crn_splitk_set_pending(*y, scratch, p.splits, st);
         return CRN_OK;
@@ -942,9 +712,8 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   // the grid (with split-K as a fallback) fills 256 CUs.
   static const int kM[4] = {8, 4, 2, 1};
   static const int kN[3] = {4, 2, 1};
-  static const bool no_vec = getenv("CRN_NO_VEC") != nullptr;
   // staging of x: float4 units (unit-stride views), position pairs (stride-2 space-to-depth views), scalars
-  const int xmode = no_vec ? 0 : (vec_view(*x) ? 1 : ((x->sW == 2 && (x->W & 1) == 0) ? 2 : 0));   // s2d views and stride-2 views
+  const int xmode = vec_view(*x) ? 1 : ((x->sW == 2 && (x->W & 1) == 0) ? 2 : 0);   // s2d views and stride-2 views
   g_stage_unit = xmode == 2 ? 2 : 4;
   const int lead = xmode == 1 ? vec_lead(pw) : (xmode == 2 ? ((pw % 2) + 2) % 2 : -1);
   // Estimated cycles per CU (calibrated on tools/sweep_fwd.sh): work that adds up on the SIMDs
@@ -952,8 +721,8 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   // load->commit->barrier latency per chunk and pair of resident workgroups; split-K pays a
   // zero-fill launch and an atomic epilogue.
   // split-K now costs one small reduction launch (tuned on bench.py: 20000 / 512 beat 40000 / 256 by 0.3 ms)
-  static const double kSplitPenalty = getenv("CRN_SPLIT_PENALTY") ? atof(getenv("CRN_SPLIT_PENALTY")) : 20000.0;
-  static const int kSplitFill = getenv("CRN_SPLIT_FILL") ? atoi(getenv("CRN_SPLIT_FILL")) : 512;
+  constexpr double kSplitPenalty = 20000.0;
+  constexpr int kSplitFill = 512;
   FwdCfg best{}; bool have = false; double best_cost = 1e300; int best_splits = 1;
   for (int mi = 0; mi < 4; ++mi)
     for (int ni = 0; ni < 3; ++ni) {
@@ -976,12 +745,6 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
       }
     }
   bool forced = false;
-  if (const char* f = getenv("CRN_FWD_FORCE")) {     // tuning aid: "MSUB,NSUB"
-    int fM, fN; FwdCfg c;
-    if (sscanf(f, "%d,%d", &fM, &fN) == 2 && fwd_cfg(fM, fN, y->B, x->C, Npad, y->D, y->H, y->W, kd, kh, kw, lead, &c)) {
-      best = c; have = true; forced = true;
-    }
-  }
   int xvec = lead >= 0 ? xmode : 0;
   if (!have && xvec) {       // no 16-byte configuration fits (tiny W): scalar staging
     xvec = 0;
@@ -1006,9 +769,8 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   g.CC = CC; g.WSP = pad16mod32(g.T * NSUB * 16);
   g.nchunks = crn_cdiv(x->C, CC);
   if (splits < 1) {   // auto split-K (atomic accumulate) only when the output grid cannot fill the chip
-    static const char* fs = getenv("CRN_FWD_SPLITS");
-    splits = fs ? atoi(fs) : (forced ? (best.blocks >= 192 ? 1 : (int)std::min<int64_t>(std::min(g.nchunks, 16), crn_cdiv(256, best.blocks)))
-                                     : best_splits);
+    splits = forced ? (best.blocks >= 192 ? 1 : (int)std::min<int64_t>(std::min(g.nchunks, 16), crn_cdiv(256, best.blocks)))
+                    : best_splits;
   }
   if (splits > g.nchunks) splits = g.nchunks;
   g.chunks_per_split = crn_cdiv(g.nchunks, splits);
@@ -1024,12 +786,9 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   // only when the scratch cannot be had
   const crnView yreal = *y;
   const int64_t ytot = (int64_t)y->B * y->C * y->D * y->H * y->W;
-  static const bool sk_atomic = getenv("CRN_SPLITK_ATOMIC") != nullptr;
-  float* scratch = (g.mode == 2 && !sk_atomic) ? splitk_scratch((size_t)splits * ytot, st) : nullptr;
-  static const bool sk_launch = getenv("CRN_SPLITK_FUSED") == nullptr;   // default: the separate reduction launch (see conv_kernels.h, mode 4)
+  float* scratch = g.mode == 2 ? splitk_scratch((size_t)splits * ytot, st) : nullptr;
   if (scratch) {
     g.mode = 3;
-    g.yreal = *y; g.accumulate_real = accumulate ? 1 : 0;
     const int64_t S = (int64_t)y->D * y->H * y->W;
     g.y.base = scratch; g.y.chan_off = nullptr;
     g.y.sW = 1; g.y.sH = y->W; g.y.sD = y->H * y->W; g.y.sC = S; g.y.sB = (int64_t)y->C * S;
@@ -1042,25 +801,17 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   }
   dim3 grid((unsigned)(g.tilesD * g.tilesH * g.tilesW * y->B), (unsigned)crn_cdiv(Npad, NSUB * 16),
             (unsigned)splits);
-  if (g.mode == 3 && !sk_launch && (g.counters = splitk_counters((size_t)grid.x * grid.y)) != nullptr) g.mode = 4;
   const size_t lds_bytes = best.lds;
   {
     bool al = y->sW == 1 && g.mw >= 4 && (y->W & 3) == 0 && (y->sH & 3) == 0 && (y->sD & 3) == 0 && (y->sB & 3) == 0 &&
               (y->sC & 3) == 0 && (((uintptr_t)y->base) & 15) == 0 && y->chan_off == nullptr && g.mode != 2;
     g.vec_store = al ? 1 : 0;
   }
-  static const bool no_boxes = getenv("CRN_NO_BOXES") != nullptr;
-  if (boxes && !no_boxes) {
+  if (boxes) {
     // groups must divide the channel counts, otherwise the information is ignored
     if (boxes->n_groups > 0 && y->C % boxes->n_groups == 0) { g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box)); }
     if (boxes->c_groups > 0 && x->C % boxes->c_groups == 0) { g.c_groups = boxes->c_groups; memcpy(g.c_box, boxes->c_box, sizeof(g.c_box)); }
   }
-  g.dbg = getenv("CRN_DBG_MODE") ? atoi(getenv("CRN_DBG_MODE")) : 0;
-  static const bool dbg = getenv("CRN_DEBUG") != nullptr;
-  if (dbg)
-    fprintf(stderr, "[crn_conv_fwd] x(C%d %dx%dx%d) y(C%d %dx%dx%d) k%dx%dx%d: MSUB %d NSUB %d CC %d tile %dx%dx%d "
-            "grid %ux%ux%u lds %zu npass %d lg2 %d xvec %d units %d\n", x->C, x->D, x->H, x->W, y->C, y->D, y->H, y->W, kd, kh, kw,
-            best.MSUB, NSUB, CC, g.TD, g.TH, g.TW, grid.x, grid.y, grid.z, lds_bytes, g.npass, g.lg2, xvec, g.nunits);
   int rc = CRN_EINVAL;
 #define CRN_FWD_CASE(M, N) if (best.MSUB == M && NSUB == N) rc = crn_launch_fwd_##M##_##N(g, xvec, grid, lds_bytes, st);
   CRN_FWD_CONFIGS(CRN_FWD_CASE)
@@ -1115,25 +866,21 @@ bool wg_cand(int TD, int TH, int TW, int RSUB, int NSUB, int Cin, int Npad, int 
 }  // namespace
 
 namespace {
-// One weight-gradient launch: window kd x kh x kw, which may be the sub-box (bd0,bh0,bw0) of a packed
-// window khf x kwf with Tfull taps; columns [0, ncols) of dw (row stride Npad).
-int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad, int ncols,
-                 int kd, int kh, int kw, int pd, int ph, int pw, int Tfull, int khf, int kwf, int bd0, int bh0,
-                 int bw0, int max_blocks, const crnTapBoxes* boxes, hipStream_t st) {
+// One weight-gradient launch: window kd x kh x kw, dw [Cin][T][Npad].
+int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                 int kd, int kh, int kw, int pd, int ph, int pw, const crnTapBoxes* boxes, hipStream_t st) {
   const int T = kd * kh * kw;
   g_stage_unit = 4;                              // x patches of the weight gradient: float4 units only
-  const int NpadC = (ncols + 15) & ~15;          // columns this launch covers
   const int Dy = dy->D, Hy = dy->H, Wy = dy->W;
   const int TWc = Wy >= 16 ? 16 : ((Wy + 3) & ~3);
-  static const bool no_vec = getenv("CRN_NO_VEC") != nullptr;
-  int xlead = (vec_view(*x) && !no_vec) ? vec_lead(pw) : -1;
+  int xlead = vec_view(*x) ? vec_lead(pw) : -1;
   // dy staging: float4 units for unit-stride views, position pairs for the stride-2 space-to-depth views of
   // the transposed convolutions (one float4 holds two positions of this parity), scalars otherwise
-  int dvec = no_vec ? 0 : (vec_view(*dy) ? 1 : ((dy->sW == 2 && dy->chan_off != nullptr && (dy->W & 1) == 0) ? 2 : 0));
+  int dvec = vec_view(*dy) ? 1 : ((dy->sW == 2 && dy->chan_off != nullptr && (dy->W & 1) == 0) ? 2 : 0);
   WgCand best{}; bool have = false;
   auto consider = [&](int TD, int TH, int RSUB, int NSUB, size_t budget) {
     WgCand c;
-    if (!wg_cand(std::min(TD, Dy), std::min(TH, Hy), TWc, RSUB, NSUB, x->C, NpadC, kd, kh, kw, xlead, dvec, budget, &c))
+    if (!wg_cand(std::min(TD, Dy), std::min(TH, Hy), TWc, RSUB, NSUB, x->C, Npad, kd, kh, kw, xlead, dvec, budget, &c))
       return false;
     if (RSUB > 1 && c.CC * T <= 32 * RSUB) return false;   // a smaller RSUB covers it
     if (!have || c.cost < best.cost) { best = c; have = true; }
@@ -1149,21 +896,12 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
   };
   search();
   if (!have && (xlead >= 0 || dvec)) { xlead = -1; dvec = 0; search(); }   // tiny maps: scalar staging
-  if (const char* f = getenv("CRN_WG_FORCE")) {      // tuning aid: "TD,TH,RSUB,NSUB"
-    int fTD, fTH, fR, fN;
-    if (sscanf(f, "%d,%d,%d,%d", &fTD, &fTH, &fR, &fN) == 4) {
-      WgCand c;
-      if (wg_cand(std::min(fTD, Dy), std::min(fTH, Hy), TWc, fR, fN, x->C, NpadC, kd, kh, kw, xlead, dvec, 150 * 1024, &c)) {
-        best = c; have = true;
-      }
-    }
-  }
   if (!have) return CRN_EINVAL;
   if (xlead < 0) dvec = 0;                           // instantiated variants: scalar, x, x+dy, x+dy pairs
   if (xlead < 0 || !dvec) {
     // the candidate was costed with dvec; re-derive it with the variant that will run
     WgCand c;
-    if (!wg_cand(best.TD, best.TH, best.TW, best.RSUB, best.NSUB, x->C, NpadC, kd, kh, kw, xlead, dvec, 150 * 1024, &c)) {
+    if (!wg_cand(best.TD, best.TH, best.TW, best.RSUB, best.NSUB, x->C, Npad, kd, kh, kw, xlead, dvec, 150 * 1024, &c)) {
       have = false; search();
       if (!have) return CRN_EINVAL;
     } else {
@@ -1184,10 +922,9 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
   g.CC = CC;
   g.tilesD = crn_cdiv(Dy, g.TD); g.tilesH = crn_cdiv(Hy, g.TH); g.tilesW = crn_cdiv(Wy, g.TW);
   g.ntiles = g.tilesD * g.tilesH * g.tilesW * dy->B;
-  const int cblocks = crn_cdiv(x->C, CC), nblocks = crn_cdiv(NpadC, NB);
-  static const int kWgBlocks = getenv("CRN_WG_BLOCKS") ? atoi(getenv("CRN_WG_BLOCKS")) : 512;
-  // one resident round: at most kWgBlocks (= 2 per CU) workgroups, or the stragglers double the time
-  const int budget = max_blocks > 0 ? std::min(max_blocks, kWgBlocks) : kWgBlocks;
+  const int cblocks = crn_cdiv(x->C, CC), nblocks = crn_cdiv(Npad, NB);
+  // one resident round: at most 512 (= 2 per CU) workgroups, or the stragglers double the time
+  constexpr int budget = 512;
   int splits = std::max(1, std::min(g.ntiles, budget / (cblocks * nblocks)));
   if (crn_deterministic()) splits = 1;                       // (the per-group splits below follow: min(ntiles, ~splits))
   g.tiles_per_split = crn_cdiv(g.ntiles, splits);
@@ -1223,18 +960,10 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
     g.magic_PLU = magic20(g.plu); g.magic_PW4 = magic20(g.pw4);
   }
   if (dvec) { g.np4 = npos / (dvec == 2 ? 2 : 4); g.dnunits = NB * g.np4; g.magic_NP4 = magic20(g.np4); }
-  g.Tfull = Tfull; g.khf = khf; g.kwf = kwf; g.bd0 = bd0; g.bh0 = bh0; g.bw0 = bw0; g.ncols = ncols;
-  g.dbg = getenv("CRN_DBG_MODE") ? atoi(getenv("CRN_DBG_MODE")) : 0;
-  // (with per-group split counts the idle tail blocks must stay spread over the XCDs: plain round robin)
-  g.xcd = getenv("CRN_WG_XCD") ? atoi(getenv("CRN_WG_XCD")) : 1;
+  // the whole packed window in one launch: no tap sub-box, every column, XCD-aware block order
+  g.Tfull = T; g.khf = kh; g.kwf = kw; g.ncols = Npad; g.xcd = 1;
   dim3 grid((unsigned)cblocks, (unsigned)(g.balanced ? 1 : nblocks), (unsigned)(g.balanced ? g.zoff[g.n_groups] : splits));
   const size_t lds_bytes = best.lds;
-  static const bool dbg = getenv("CRN_DEBUG") != nullptr;
-  if (dbg)
-    fprintf(stderr, "[crn_conv_wgrad] x(C%d %dx%dx%d) dy(C%d %dx%dx%d) k%dx%dx%d: RSUB %d NSUB %d CC %d tile %dx%dx%d "
-            "grid %ux%ux%u lds %zu npass %d dnpass %d tiles/split %d xvec %d dvec %d units %d/%d\n", x->C, x->D, x->H,
-            x->W, dy->C, dy->D, dy->H, dy->W, kd, kh, kw, RSUB, NSUB, CC, g.TD, g.TH, g.TW, grid.x, grid.y, grid.z,
-            lds_bytes, g.npass, g.dnpass, g.tiles_per_split, xlead >= 0, (int)dvec, g.nunits, g.dnunits);
 #define CRN_WG_CASE(R, N) \
   if (RSUB == R && NSUB == N) return crn_launch_wgrad_##R##_##N(g, xlead >= 0, dvec, grid, lds_bytes, st);
   CRN_WG_CONFIGS(CRN_WG_CASE)
@@ -1261,22 +990,6 @@ extern "C" int crn_conv_wgrad(const crnView* x, const crnInTransform* tr, const 
   }
   // Tap boxes: inside the single launch every block enumerates only the (channel, tap) rows of its output
   // group's box (conv_wgrad_kernel).  The alternative -- one launch per output parity with a smaller
-  // window -- LOSES on MI355X (eight prologues and atomic epilogues: s5t1 1.02 ms vs 0.94 ms) and stays an
-  // experiment (CRN_WG_BOXES=1).
-  static const bool wg_boxes = getenv("CRN_WG_BOXES") != nullptr;
-  if (boxes && wg_boxes && boxes->n_groups > 1 && boxes->n_groups <= 8 && dy->C % boxes->n_groups == 0 &&
-      ((dy->C / boxes->n_groups) & 15) == 0 && dy->chan_off != nullptr) {
-    const int per = dy->C / boxes->n_groups;
-    for (int gi = 0; gi < boxes->n_groups; ++gi) {
-      const signed char* b = boxes->n_box[gi];
-      crnView dyg = *dy;
-      dyg.C = per; dyg.chan_off = dy->chan_off + (size_t)gi * per;
-      const int rc = wgrad_launch(x, tr, &dyg, dw + (size_t)gi * per, Npad, per, b[1] - b[0], b[3] - b[2], b[5] - b[4],
-                                  pd - b[0], ph - b[2], pw - b[4], T, kh, kw, b[0], b[2], b[4], 0, nullptr, st);
-      if (rc != CRN_OK) return rc;
-    }
-    return CRN_OK;
-  }
-  static const bool no_boxes = getenv("CRN_NO_BOXES") != nullptr;
-  return wgrad_launch(x, tr, dy, dw, Npad, Npad, kd, kh, kw, pd, ph, pw, T, kh, kw, 0, 0, 0, 0, no_boxes ? nullptr : boxes, st);
+  // window -- LOSES on MI355X (eight prologues and atomic epilogues: s5t1 1.02 ms vs 0.94 ms).
+  return wgrad_launch(x, tr, dy, dw, Npad, kd, kh, kw, pd, ph, pw, boxes, st);
 }

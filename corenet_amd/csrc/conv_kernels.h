@@ -28,10 +28,7 @@ struct ConvGeom {
   int tilesD, tilesH, tilesW;
   int nchunks, chunks_per_split;
   int mode;                // 0 store, 1 accumulate (rmw), 2 atomic add, 3 split-K partials to scratch (+ reduce
-                           // launch), 4 split-K partials to scratch, summed by the last workgroup of each tile
-  crnView yreal;           // mode 4: the tensor the sums go to, accumulate_real: += instead of =
-  int accumulate_real;
-  int* counters;           // mode 4: one arrival counter per (tile, N block), zero between calls
+                           // launch)
   int lg2, npass;          // patch staging: plane padded to 2^lg2 slots, passes of 256 slots
   unsigned magic_PW, magic_PD, magic_T;
   int vec_store;           // epilogue may use 16-B stores (unit W stride, 4-aligned rows)
@@ -40,7 +37,6 @@ struct ConvGeom {
   int lead;                // extra patch columns on the left (16-byte staging), already included in pw/PW
   int nunits, plu, pw4;    // 16-byte staging geometry (PatchDesc)
   unsigned magic_PLU, magic_PW4;
-  int dbg;                 // tuning aid (CRN_DBG_MODE): 1 = no MFMA loop, 2 = stage only the first chunk
 };
 
 __device__ __forceinline__ int64_t view_chan(const crnView& v, int c) {
@@ -550,8 +546,6 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
   }
   for (int chunk = cbeg; chunk < cend; ++chunk) {
     const int c0 = chunk * g.CC;
-    const bool stage = !(g.dbg >= 2 && chunk > cbeg);
-    if (stage) {
     if constexpr (XV != 0) crn_wait_loads4n(pv4); else crn_wait_loads(pval);
     crn_wait_loads4(wval);
     __syncthreads();                       // previous chunk's MFMA reads are done
@@ -560,8 +554,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
     weights_commit(c0);
     if (chunk + 1 < cend) stage_choff(g.x, g.tr, choff + ((chunk + 1) & 1) * kChTab, c0 + g.CC, g.CC);
     __syncthreads();
-    }
-    if (stage && g.dbg < 2 && chunk + 1 < cend) {                // next chunk's loads fly under this chunk's MFMAs
+    if (chunk + 1 < cend) {                // next chunk's loads fly under this chunk's MFMAs
       if constexpr (XV != 0) patch_issue_v<XPU>(pdsc, choff + ((chunk + 1) & 1) * kChTab, xrs, c0 + g.CC, d0, h0, w0, pv4, inmask);
       else patch_issue(pdsc, choff + ((chunk + 1) & 1) * kChTab, phw, xrs, nplanes, npass, c0 + g.CC, d0, pval);
       weights_issue(c0 + g.CC);
@@ -571,21 +564,19 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
     // accumulators never cross a control-flow merge inside them (a merge costs 32 v_mov per row,
     // and on gfx950 every VALU instruction next to an MFMA stream costs 4-8 MFMA cycles:
     // tools/mfma_peak.hip).
-    if (g.dbg != 1) {
-      const int ksteps = g.CC >> 2;
-      // taps that can hold non-zero weights for this block's output columns and this chunk's channels
-      const TapBox tb = box_intersect(nbox, box_union(g.c_box, g.c_groups, g.x.C, c0, min(c0 + g.CC, g.x.C) - 1,
-                                                      g.kd, g.kh, g.kw));
-      if (tb.d1 > tb.d0 && tb.h1 > tb.h0 && tb.w1 > tb.w0)
-      switch (tb.w1 - tb.w0) {
-        case 1: mfma_rows<1, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
-        case 2: mfma_rows<2, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
-        case 3: mfma_rows<3, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
-        case 4: mfma_rows<4, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
-        case 5: mfma_rows<5, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
-        case 7: mfma_rows<7, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
-        default: mfma_rows<1, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, tb.w1 - tb.w0, tb); break;
-      }
+    const int ksteps = g.CC >> 2;
+    // taps that can hold non-zero weights for this block's output columns and this chunk's channels
+    const TapBox tb = box_intersect(nbox, box_union(g.c_box, g.c_groups, g.x.C, c0, min(c0 + g.CC, g.x.C) - 1,
+                                                    g.kd, g.kh, g.kw));
+    if (tb.d1 > tb.d0 && tb.h1 > tb.h0 && tb.w1 > tb.w0)
+    switch (tb.w1 - tb.w0) {
+      case 1: mfma_rows<1, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
+      case 2: mfma_rows<2, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
+      case 3: mfma_rows<3, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
+      case 4: mfma_rows<4, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
+      case 5: mfma_rows<5, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
+      case 7: mfma_rows<7, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, 1, tb); break;
+      default: mfma_rows<1, MSUB, NSUB>(acc, ldsA, ldsB, posbase, bbase, ksteps, g, tb.w1 - tb.w0, tb); break;
     }
   }
 
@@ -633,57 +624,6 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
       }
     }
   }
-  // mode 4: the split-K reduction without a second launch.  Every workgroup of a tile publishes its partial sums
-  // (release fence), takes a ticket, and the one that arrives last adds up all splits in a fixed order (split 0
-  // first: the result does not depend on who arrives last) and writes the real output.
-  // MEASURED AND NOT USED BY DEFAULT (env CRN_SPLITK_FUSED=1 turns it on): the agent-scope release / acquire fences
-  // every workgroup needs write back / invalidate the XCD's L2 (MI355X: 8 XCDs, L2 not coherent across them), which
-  // cost far more than the 66 reduction launches (0.48 ms) they save: 18.7 ms per training step instead of 10.5.
-  if (g.mode == 4) {
-    __threadfence();
-    int* s_last = reinterpret_cast<int*>(lds);            // the channel tables are dead by now
-    __syncthreads();
-    if (tid == 0) {
-      const int id = blockIdx.x + gridDim.x * blockIdx.y;
-      const int ticket = atomicAdd(g.counters + id, 1);
-      const int last = ticket == (int)gridDim.z - 1;
-      if (last) g.counters[id] = 0;                       // ready for the next call on this stream
-      *s_last = last;
-    }
-    __syncthreads();
-    if (!*s_last) return;
-    __threadfence();
-    const int64_t slab = (int64_t)g.x.B * g.y.sB;          // one split of the scratch tensor
-    const int nsplit = gridDim.z;
-    const float* sb = g.y.base + (int64_t)b * g.y.sB;
-    float* yr = g.yreal.base + (int64_t)b * g.yreal.sB;
-#pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns) {
-      const int n = n0 + ns * 16 + i16;
-      if (n >= g.y.C) continue;
-      const int64_t co = view_chan(g.y, n), cor = view_chan(g.yreal, n);
-#pragma unroll
-      for (int ms = 0; ms < MSUB; ++ms) {
-        int s = wave * MSUB + ms;
-        const int sw = s % g.nsw; s /= g.nsw;
-        const int sh = s % g.nsh; s /= g.nsh;
-        const int sd = s;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row_ = kk * 4 + r;
-          const int rr = row_ / g.mw, rc = row_ - rr * g.mw;
-          const int od = d0 + sd, oh = h0 + sh * g.mh + rr, ow = w0 + sw * g.mw + rc;
-          if (od < g.y.D && oh < g.y.H && ow < g.y.W) {
-            const float* src = sb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
-            float sum = 0.f;
-            for (int sp = 0; sp < nsplit; ++sp) sum += __builtin_nontemporal_load(src + sp * slab);
-            float* dst = yr + cor + (int64_t)od * g.yreal.sD + (int64_t)oh * g.yreal.sH + (int64_t)ow * g.yreal.sW;
-            *dst = g.accumulate_real ? *dst + sum : sum;
-          }
-        }
-      }
-    }
-  }
 }
 
 // ------------------------------ weight grad ---------------------------------
@@ -718,7 +658,7 @@ struct WgradGeom {
   int tps[8], sg[8], zoff[9];
   int dnunits, np4;        // 16-byte staging of dy: NB * npos/4 units, np4 = npos/4 per channel
   unsigned magic_NP4;
-  int dbg;                 // tuning aid (CRN_DBG_MODE): 1 = no MFMA loop, 2 = stage only the first tile
+  int dbg;                 // zero (kept so that the kernel's code stays as measured): 1 = no MFMA loop, 2 = stage only the first tile
 };
 
 // One tile's MFMAs: a (td,th) row of WS = TW/4 k-steps is straight-line code.
@@ -1088,7 +1028,6 @@ inline int launch_wgrad(const WgradGeom& g, dim3 grid, size_t lds_bytes, hipStre
 
 // split-K scratch + reduction shared by the fp32 and the bf16x3 engine (defined in conv_igemm.hip)
 float* crn_splitk_scratch(size_t floats, hipStream_t st);      // per (device, stream)
-int* crn_splitk_counters(size_t n);          // n zero-initialised arrival counters (self-resetting), or nullptr
 int crn_splitk_reduce(const crnView& y, const float* scratch, int splits, int accumulate, hipStream_t st);
 
 // launchers defined in conv_inst.hip (one object per configuration)

@@ -59,7 +59,6 @@ struct CtGeom {
   int tilesD, tilesH, tilesW;
   int nhalf;                                               // data gradient: 8-channel halves of Cout (1 or 2)
   int accumulate;
-  int xcd;                                                 // resident-weights kernels: XCD-aware tile ranges (CRN_CT_RES_XCD=0: off)
 };
 
 // step s of the walk: its slab (hi half, lo half; DH rows of 4 taps x 32 columns each) -> slab buffer `buf`, 1 KiB pieces
@@ -744,7 +743,7 @@ __global__ __launch_bounds__(kT) void convt_res_kernel(CtGeom g, int ntiles, int
   }
   // (XCD-aware: workgroup w runs on XCD w % 8; each XCD walks a contiguous eighth of the tiles so that the patch halos of the
   // workgroups that run side by side hit in ITS L2 -- 520 / 406 MB of fabric traffic per launch for 134 MB of tensors without it)
-  const int slot = g.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int slot = xcd_remap(blockIdx.x, gridDim.x);
   const int tbeg = min(slot * tiles_per_wg, ntiles), tend = min(tbeg + tiles_per_wg, ntiles);
   int b = 0, d0 = 0, h0 = 0, w0 = 0;
   auto tile_origin = [&](int tl) {
@@ -1030,14 +1029,11 @@ extern "C" int crn_convt_s2k7_wgrad_bf3(const float* x, int64_t x_sB, int B, int
   if (ntiles > 0x7fffffff) return CRN_EINVAL;
   g.ntiles = (int)ntiles;
   // One round of 256 workgroups (one per CU), dealt to the four (rd, rh) pairs in proportion to the cost of a tile: its multiplies
-  // (taps per wave x 8 waves: 40 / 48 / 48 / 64) plus the staging of the tile, which is the same for every pair (kStage, in taps:
-  // CRN_CT_WG_STAGE; 0 = by multiplies alone, CRN_CT_WG_EVEN=1 = the same number of tiles for every pair)
-  static const int kBlocks = getenv("CRN_CT_WG_BLOCKS") ? std::max(4, atoi(getenv("CRN_CT_WG_BLOCKS"))) : 256;
-  static const int kStage = getenv("CRN_CT_WG_STAGE") ? std::max(0, atoi(getenv("CRN_CT_WG_STAGE"))) : 24;
-  static const bool kEven = getenv("CRN_CT_WG_EVEN") != nullptr && atoi(getenv("CRN_CT_WG_EVEN")) != 0;
+  // (taps per wave x 8 waves: 40 / 48 / 48 / 64) plus the staging of the tile, which is the same for every pair (kStage, in taps)
+  constexpr int kBlocks = 256, kStage = 24;
   const int taps[4] = {40, 48, 48, 64};
   int cost[4], total = 0;
-  for (int p = 0; p < 4; ++p) { cost[p] = kEven ? 1 : taps[p] + kStage; total += cost[p]; }
+  for (int p = 0; p < 4; ++p) { cost[p] = taps[p] + kStage; total += cost[p]; }
   const int blocks = (int)std::min<int64_t>(kBlocks, 4 * ntiles);
   int wgs = 0;
   for (int p = 0; p < 4; ++p) {
@@ -1073,9 +1069,7 @@ extern "C" int crn_convt_s2k7_c2_fwd_bf3(const float* x, int64_t x_sB, int B, in
   g.tilesD = D / TD; g.tilesH = H / TH; g.tilesW = W / TW;
   const int64_t tiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
   if (tiles > 0x7fffffff) return CRN_EINVAL;
-  static const int kWgs = getenv("CRN_CT_RES_WGS") ? std::max(1, atoi(getenv("CRN_CT_RES_WGS"))) : 256;
-  static const bool kXcd = getenv("CRN_CT_RES_XCD") == nullptr || atoi(getenv("CRN_CT_RES_XCD")) != 0;
-  g.xcd = kXcd ? 1 : 0;
+  constexpr int kWgs = 256;
   const int per = crn_cdiv(tiles, std::min<int64_t>(tiles, kWgs)), wgs = crn_cdiv(tiles, per);
   static const bool attr = [] {
     return hipFuncSetAttribute((const void*)convt_res_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsRes) == hipSuccess;
@@ -1099,9 +1093,7 @@ extern "C" int crn_convt_s2k7_c2_dgrad_bf3(const float* dy, int64_t dy_sB, int64
   g.tilesD = D / TD; g.tilesH = H / TH; g.tilesW = W / TW;
   const int64_t tiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
   if (tiles > 0x7fffffff) return CRN_EINVAL;
-  static const int kWgs = getenv("CRN_CT_RES_WGS") ? std::max(1, atoi(getenv("CRN_CT_RES_WGS"))) : 256;
-  static const bool kXcd = getenv("CRN_CT_RES_XCD") == nullptr || atoi(getenv("CRN_CT_RES_XCD")) != 0;
-  g.xcd = kXcd ? 1 : 0;
+  constexpr int kWgs = 256;
   const int per = crn_cdiv(tiles, std::min<int64_t>(tiles, kWgs)), wgs = crn_cdiv(tiles, per);
   static const bool attr = [] {
     return hipFuncSetAttribute((const void*)convt_res_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsRes) == hipSuccess;

@@ -620,7 +620,7 @@ __global__ __launch_bounds__(1024) void fill_fused_kernel(const T* grid, T* out,
     // wave waits for its own stores to be acknowledged, the workgroup barrier collects the waves, and only then does
     // thread 0 announce the slab with ONE relaxed read-modify-write (arrival + vote in one word; separate count / flag words
     // cost two more memory round trips per round) and poll with relaxed loads.  The release / acquire form of the same
-    // protocol (CRN_FILL_RELAXED=0: buffer_wbl2 + buffer_inv at agent scope) writes back every dirty line this XCD's L2
+    // protocol (other devices: buffer_wbl2 + buffer_inv at agent scope) writes back every dirty line this XCD's L2
     // holds -- the previous call's output, other kernels' data -- before the arrival counts: 3.4 us per round against
     // 0.8 us, 62-64 us per call against 54-58 (12 x 128^3).
     // The words of round `it` are those of round it - kFusedIters, cleared long ago by that round's last leaver.
@@ -732,10 +732,9 @@ char* fill_control(const void* ws, size_t bytes, hipStream_t st) {
 // The cache-maintenance-free exchange (write-through stores, acknowledged, relaxed arrival) is outside what the HIP / LLVM memory
 // model promises; it rests on how gfx950 implements agent-scope atomics (written through / cache-bypassing) and on vmcnt covering
 // stores.  It is measured and tested on MI355X (bit-exact on every fixture incl. the serpentine grid's hundreds of rounds); on any
-// other device name the release / acquire form is used.  CRN_FILL_RELAXED=0 / 1 forces either.
+// other device name the release / acquire form is used.
 int fill_relaxed_default() {
   static const int v = [] {
-    if (const char* e = getenv("CRN_FILL_RELAXED")) return atoi(e) != 0 ? 1 : 0;
     int dev = 0; hipDeviceProp_t p;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
     return strncmp(p.gcnArchName, "gfx950", 6) == 0 ? 1 : 0;

@@ -442,20 +442,14 @@ int ray_scatter(const float* dout, int64_t dout_sB, int B, int C, int D, int H, 
       for (int b = 0; b < B; ++b) CRN_HIP(hipMemsetAsync(dmap + b * dmap_sB, 0, (size_t)C * h * w * 4, st));
     }
   }
-  // tuning aids (tools/ray_bwd_sweep.sh): CRN_RAY_ZSEG = planes per thread (8 or 16), CRN_RAY_CN = channels per thread (4 or 12),
-  // CRN_RAY_TX = tile width for grids >= 64 (32 or 64)
-  static const int zseg_env = getenv("CRN_RAY_ZSEG") ? atoi(getenv("CRN_RAY_ZSEG")) : 0;
-  static const int cn_env = getenv("CRN_RAY_CN") ? atoi(getenv("CRN_RAY_CN")) : 0;
-  static const int tx_env = getenv("CRN_RAY_TX") ? atoi(getenv("CRN_RAY_TX")) : 0;
   const bool det = crn_deterministic();
-  const int CN = (C % 12 == 0 && (cn_env == 12 || (det && !cn_env))) ? 12 : 4;
+  const int CN = (C % 12 == 0 && det) ? 12 : 4;
   // measured (profiles/r05_ray_sweep.txt, B = 4, us at 64^3 / 32^3): 4 channels x 8 planes 17.9 / 14.4, x 16 planes 26.5 / 16.1,
   // 12 channels x 8 planes 22.9 / 20.8; 64-wide tiles 17.4 / 14.4
-  const int ZS = CN == 4 && zseg_env == 16 ? 16 : 8;      // (12 channels x 16 planes: 255 registers)
-  const int zseg = std::min(D, ZS);
+  const int zseg = std::min(D, 8);
   const int nseg = (D + zseg - 1) / zseg;
   const bool big = W >= 64 && H >= 64;
-  const int kTX = big ? (tx_env == 64 ? 64 : 32) : 8, kTY = big ? 256 / kTX : 8;
+  const int kTX = big ? 32 : 8, kTY = big ? 256 / kTX : 8;
   const int tilesX = crn_cdiv(W, kTX), tilesY = crn_cdiv(H, kTY);
   // LDS window: the pixels a tile can reach when a voxel covers s pixels (s = map size / grid size, >= 1), with margins; a
   // tile that reaches further adds to HBM directly
@@ -489,15 +483,12 @@ int ray_scatter(const float* dout, int64_t dout_sB, int B, int C, int D, int H, 
     hipLaunchKernelGGL(ray_det_scale_kernel, dim3(1), dim3(1), 0, st, maxbits, scale, lg);
     a.detmap = detmap; a.scale_p = scale;
     if (CN == 12) hipLaunchKernelGGL((ray_scatter_kernel<12, 8, IT, true>), grid, block, 0, st, a);
-    else if (ZS == 8) hipLaunchKernelGGL((ray_scatter_kernel<4, 8, IT, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((ray_scatter_kernel<4, 16, IT, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((ray_scatter_kernel<4, 8, IT, true>), grid, block, 0, st, a);
     hipLaunchKernelGGL(ray_det_finish_kernel, dim3(256), dim3(256), 0, st, detmap, scale, dmap, dmap_sB, per_b, B);
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
-  if (CN == 12) hipLaunchKernelGGL((ray_scatter_kernel<12, 8, IT, false>), grid, block, lds, st, a);
-  else if (ZS == 8) hipLaunchKernelGGL((ray_scatter_kernel<4, 8, IT, false>), grid, block, lds, st, a);
-  else hipLaunchKernelGGL((ray_scatter_kernel<4, 16, IT, false>), grid, block, lds, st, a);
+  hipLaunchKernelGGL((ray_scatter_kernel<4, 8, IT, false>), grid, block, lds, st, a);     // (12 channels: deterministic mode only)
   CRN_CHECK_LAUNCH();
   return CRN_OK;
 }

@@ -277,8 +277,7 @@ extern "C" int crn_stem_conv_wgrad(const float* img, int B, int H, int W, const 
   if (crn_deterministic()) return CRN_EINVAL;        // (order-independent sums: the caller keeps crn_conv_wgrad)
   StemGeom g = stem_geom(B, H, W);
   g.img = img; g.dy = dy; g.dw = dw_packed;
-  static const int blocks_env = getenv("CRN_STEM_WG_BLOCKS") ? atoi(getenv("CRN_STEM_WG_BLOCKS")) : 256;
-  const int blocks = std::max(1, std::min(g.ntiles, blocks_env));
+  const int blocks = std::max(1, std::min(g.ntiles, 256));
   hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, g);
   CRN_CHECK_LAUNCH();
   return CRN_OK;

@@ -50,7 +50,6 @@ class CoreNetConfig:
     return cls(decoder=DecoderConfig(**dd))
 
 
-_EVAL_GRAPH = os.environ.get("CRN_EVAL_GRAPH", "1") != "0"      # inference forwards replay a captured HIP graph
 _LIVE_GRAPHS = []      # captured steps; released before interpreter teardown (graph destruction after the HIP
                        # runtime has started to unload faults)
 
@@ -286,7 +285,7 @@ class CoreNet(nn.Module):
         params = [self.get_parameter(k) for k in self._param_keys]
         return _CoreNetFn.apply(self, image, v2s, off, *params)
       plan = eng.plan(B, image.shape[2:])
-      if inference and image.is_cuda and _EVAL_GRAPH and plan.trace is None and plan.probes is None:
+      if inference and image.is_cuda and plan.trace is None and plan.probes is None:
         out = self._forward_eval_graph(plan, image, v2s, off)
       else:
         out = plan.forward(image, v2s, off, training=self.training).clone()
@@ -432,7 +431,7 @@ class CoreNet(nn.Module):
       if all_reduce is not None and getattr(all_reduce, "overlap", False):
         all_reduce.pushed.clear()
         step_buckets = (hasattr(all_reduce, "opt_stream") and plan.side is not None and plan.trace is None
-                        and os.environ.get("CRN_BUCKET_ADAM", "1") != "0" and all_reduce.opt_stream() is not None)
+                        and all_reduce.opt_stream() is not None)
         if step_buckets:
           # Adam per bucket behind its all-reduce, on the exchange's optimizer stream: the update runs under the rest of
           # backward on every rank, as it does without an exchange (adam_bucket_hook)

@@ -64,10 +64,8 @@ GRAD_BUCKET_LABELS = ("decoder.stage_3.", "decoder.stage_0.", "encoder.stage5.c.
 BF16X3_LAUNCHES = frozenset(
     [(f"decoder.stage_{k}.{l}.", d) for k in (3, 4, 5, 6) for l in ("c1", "t1") for d in ("fwd", "dgrad")] +
     [(f"decoder.stage_{k}.{l}.", "wgrad") for k in (3, 4, 5, 6) for l in ("c1", "t1")])
-# MEASUREMENT ONLY: bits 1 / 2 / 4 = the forward weight packs / the data-gradient weight pack / the gradient
-# un-packs are NOT launched -- the kernels then read stale packed weights and Adam steps on stale gradients, so every result is WRONG; it
-# prices what the step would gain without these copies (master weights kept in the kernels' layout).  Never set outside a timing run.
-_TIMING_ONLY_SKIP_COPIES = int(os.environ.get("CRN_TIMING_ONLY_SKIP_COPIES", "0"))
+# the parity-walk kernels of the logits layer (csrc/convt_par.hip) serve this many classes and more (Engine._build_ct_images)
+CT_PAR_MIN = 9
 LOSS_KINDS = {"iou_fgbg": 0, "xent_times_iou_agnostic": 1, "iou_agnostic": 2, "xent": 3,
               "xent_times_iou_fgbg": 4}
 
@@ -233,14 +231,7 @@ class Engine:
       raise ValueError(f"decoder_math must be 'fp32' or 'bf16x3', not {self.decoder_math!r}")
     # in bf16x3 mode the encoder's stride-1 1x1 / 3x3 convs (forward and data gradient) run on the encoder
     # engine (csrc/conv_e2d.hip: the same split-bf16 products, weights pre-arranged as MFMA operand blocks)
-    self.encoder_e2d = self.decoder_math == "bf16x3" and os.environ.get("CRN_E2D", "1") != "0"
-    self.wgrad_2d = os.environ.get("CRN_WG2D", "1") != "0"
-    self.defer_reduce = os.environ.get("CRN_DEFER_REDUCE", "1") != "0"
-    # decoder data gradients leave the two sums of the following BatchRenorm backward (crn_conv_fwd_bf3_slabs_bnbwd)
-    self.bn_bwd_fuse = os.environ.get("CRN_BN_BWD_FUSE", "1") != "0"
-    # ... except for these layers (measured per layer, profiles/r05_bn_bwd_fuse.txt; CRN_BN_BWD_FUSE_SKIP overrides, comma separated)
-    self.bn_bwd_fuse_skip = frozenset(x for x in os.environ.get("CRN_BN_BWD_FUSE_SKIP", "").split(",") if x)
-    self.fuse_tail = os.environ.get("CRN_FUSE_TAIL", "1") != "0"
+    self.encoder_e2d = self.decoder_math == "bf16x3"
     # fp32 is the only dtype of the HIP kernels; float64 exists so that the CPU
     # contract emulator (tests/) can check the host wiring far below fp32 noise.
     assert dtype == t.float32 or getattr(backend, "name", "") == "emu"
@@ -325,10 +316,10 @@ class Engine:
       self._capture = None
 
   def side_stream(self):
-    """The engine's second HIP stream (weight gradients, weight packs, gradient buckets) or None (CPU emulator,
-    CRN_SIDE_STREAM=0); one per engine, shared by the plans of all batch sizes."""
+    """The engine's second HIP stream (weight gradients, weight packs, gradient buckets) or None (CPU emulator);
+    one per engine, shared by the plans of all batch sizes."""
     if self._side is False:
-      use = self.device.type == "cuda" and os.environ.get("CRN_SIDE_STREAM", "1") != "0"
+      use = self.device.type == "cuda"
       self._side = t.cuda.Stream(device=self.device) if use else None
       if use:
         self._pack_ev, self._dgrad_packed = t.cuda.Event(), t.cuda.Event()
@@ -410,7 +401,7 @@ class Engine:
       if dgrad is not None:
         # a data-gradient layout that IS the reference layout (the 1x1 convolutions: [Cout][Cin], no padding -- 12 M of the 30 M
         # weights of the plain convolutions) is not packed at all: the kernels read the parameter slab (an empty part here)
-        alias = (os.environ.get("CRN_DGRAD_ALIAS", "1") != "0" and len(dgrad.index) == int(np.prod(s.off[name + "weight"][1]))
+        alias = (len(dgrad.index) == int(np.prod(s.off[name + "weight"][1]))
                  and np.array_equal(dgrad.index, np.arange(len(dgrad.index))))
         parts.append(np.zeros(0, np.int64) if alias else shift(dgrad.index, wo))
       idx_parts.append(parts)
@@ -479,19 +470,19 @@ class Engine:
     """Weight images of the parity-walk kernels of decoder stage_6.t1 (ConvTranspose3d 16 -> C, k 7, stride 2: csrc/convt_par.hip),
     gathered straight from the flat parameter slab after every weight pack (crn_bf3_gather_image).  Used with more than 8 classes
     (m7 / m9): the walk multiplies 16 columns per parity, with the 2 classes of h7 the generic engine's one 16-column block for
-    all 8 parities executes fewer MFMAs (CRN_CT_PAR=0 turns the kernels off, CRN_CT_PAR_MIN sets the class threshold)."""
+    all 8 parities executes fewer MFMAs (CT_PAR_MIN: the class threshold)."""
     self.ct_tables = {}
     name = "decoder.stage_6.t1."
-    if (self.decoder_math != "bf16x3" or self.device.type != "cuda" or os.environ.get("CRN_CT_PAR", "1") == "0"
+    if (self.decoder_math != "bf16x3" or self.device.type != "cuda"
         or name not in self.convs or not hasattr(self.be, "convt_par_fwd")):
       return
     shape = tuple(self.store.off[name + "weight"][1])
     if shape[0] != 16 or shape[1] > 16 or tuple(shape[2:]) != (7, 7, 7) or tuple(self.resolution) != (128, 128, 128):
       return
-    if shape[1] == 2 and os.environ.get("CRN_CT_RES", "1") != "0":
+    if shape[1] == 2:
       # two classes (h7): 8 parities x 2 classes are ONE 16-column block and the layer's weights stay resident in LDS
       kind_, tabs = "res", (G.convt_res_fwd_table, G.convt_res_dgrad_table)
-    elif shape[1] >= int(os.environ.get("CRN_CT_PAR_MIN", "9")):
+    elif shape[1] >= CT_PAR_MIN:
       kind_, tabs = "par", (G.convt_par_fwd_table, G.convt_par_dgrad_table)
     else:
       return
@@ -518,14 +509,13 @@ class Engine:
     # amplify any rounding difference ~400x (the fp32 engine itself sits 5.7e-4 from the reference there); the
     # forward pass of stages 2-3 in split-bf16 would raise that to 1.2e-3, stages 4-5 leave it where it is, and
     # the data gradient does not enter the logits at all.  The 1x1 layers gain nothing over the fp32 pointwise
-    # kernel yet (13 vs 14 us) and stay there.  CRN_E2D_KINDS=all / CRN_E2D_FWD_STAGES=2345: tuning aids.
-    kinds = os.environ.get("CRN_E2D_KINDS", "3x3")
+    # kernel yet (13 vs 14 us) and stay there.
     for (name, fwd, dgrad, repeat, nref), parts in zip(reg, idx_parts):
       src_f = po; po += len(parts[0]) + len(parts[1])
       src_d = po
       if dgrad is not None:
         po += len(parts[2])
-      if (name, "fwd") in BF16X3_LAUNCHES and os.environ.get("CRN_BF3_SLABS", "1") != "0":
+      if (name, "fwd") in BF16X3_LAUNCHES:
         # decoder bf16x3 layers: slab images of the forward and the data-gradient weights
         groups["dec"].append((src_f, eo, fwd, True))
         slices.append((name, "wop_f", eo, G.slab_entries(fwd))); eo += G.slab_entries(fwd)
@@ -536,11 +526,9 @@ class Engine:
       if not self.encoder_e2d or not name.startswith("encoder.") or name.startswith("encoder.stage1"):
         continue
       self.convs[name].wop_kind = "e2d"
-      only_dgrad = kinds == "3x3+dgrad1x1" and fwd.window != (1, 3, 3)      # tuning aid
-      if kinds == "3x3" and fwd.window != (1, 3, 3):
+      if fwd.window != (1, 3, 3):
         continue
-      fwd_stages = os.environ.get("CRN_E2D_FWD_STAGES", "45")
-      if G.operand_eligible(fwd) and name[len("encoder.stage")] in fwd_stages and not only_dgrad:
+      if G.operand_eligible(fwd) and name[len("encoder.stage")] in "45":
         groups["enc_early" if name.startswith("encoder.stage2") else "enc_late"].append((src_f, eo, fwd))
         slices.append((name, "wop_f", eo, G.operand_entries(fwd))); eo += G.operand_entries(fwd)
       if dgrad is not None and len(parts[2]) and G.operand_eligible(dgrad):     # (not the layers whose data-gradient layout is the slab's)
@@ -566,10 +554,8 @@ class Engine:
 
   def _tiles_dev(self, parts):
     """Device tables of one pack / un-pack: the parts that are plain transposes as LDS blocks (conv_geometry.mat_index,
-    crn_copy_mats_f32: runs of 64+ floats on both sides), the rest as 8x8 tiles (tile_index).  CRN_COPY_MATS=0: tiles
-    only (the round-2 copies)."""
-    mats, rest = (G.mat_index(parts) if os.environ.get("CRN_COPY_MATS", "1") != "0" else
-                  (np.zeros((0, 16), np.int32), parts))
+    crn_copy_mats_f32: runs of 64+ floats on both sides), the rest as 8x8 tiles (tile_index)."""
+    mats, rest = G.mat_index(parts)
     tl = G.tile_index(rest)
     return (t.as_tensor(tl[0], device=self.device), t.as_tensor(tl[1].view(np.int64), device=self.device),
             t.as_tensor(tl[2] if tl[2].size else np.zeros(1, np.int32), device=self.device),
@@ -594,8 +580,7 @@ class Engine:
     """flat parameter slab -> packed forward weights and biases ("enc" / "dec": one of the two pieces)."""
     tiles = {"all": self.pack_tiles, "enc": self.pack_tiles_enc, "dec": self.pack_tiles_dec,
              "enc_early": self.pack_tiles_enc_early, "enc_late": self.pack_tiles_enc_late}[part]
-    if not _TIMING_ONLY_SKIP_COPIES & 1:
-      self.be.copy_tiles(self.store.params, self.packed, tiles)
+    self.be.copy_tiles(self.store.params, self.packed, tiles)
     self._operands(*{"all": ("enc_early", "enc_late", "dec"), "enc": ("enc_early", "enc_late"), "dec": ("dec",),
                      "enc_early": ("enc_early",), "enc_late": ("enc_late",)}[part])
     if part in ("all", "dec"):
@@ -603,8 +588,7 @@ class Engine:
 
   def pack_dgrad_weights(self):
     """flat parameter slab -> packed data-gradient weights (1 launch; backward only)."""
-    if not _TIMING_ONLY_SKIP_COPIES & 2:
-      self.be.copy_tiles(self.store.params, self.packed, self.pack_tiles_bwd)
+    self.be.copy_tiles(self.store.params, self.packed, self.pack_tiles_bwd)
     self._operands("bwd")
     self.dgrad_dirty = False
 
@@ -673,18 +657,17 @@ class Plan:
     H, W = check_image_hw(hw)
     self.hw = (H, W)
     self.stem_hw = (H // 2, W // 2)          # after the 7x7 / 2 stem (resnet50.py:122-124)
-    # the stem's own kernels (csrc/stem_conv.hip: H even, W a multiple of 8, <= 4096 workgroup partial sums); CRN_STEM=0: the
-    # generic engine on the space-to-depth view, as before round 5
+    # the stem's own kernels (csrc/stem_conv.hip: H even, W a multiple of 8, <= 4096 workgroup partial sums); otherwise the
+    # generic engine on the space-to-depth view
     parts = int(eng.be.lib.crn_stem_conv_parts(B, H, W)) if hasattr(eng.be, "stem_conv_fwd") else 0
-    self.stem_fast = os.environ.get("CRN_STEM", "1") != "0" and 0 < parts <= 4096
-    self.dec_stats_fused = os.environ.get("CRN_DEC_STATS_FUSE", "1") != "0" and hasattr(eng.be, "conv_fwd_stats")
+    self.stem_fast = 0 < parts <= 4096
+    self.dec_stats_fused = hasattr(eng.be, "conv_fwd_stats")
     self.pool_hw = (H // 4, W // 4)          # after the 3x3 / 2 max-pool (:128-131): stage 2 runs here
     self.be = eng.be
     self.generation = 0            # bumped by every forward: CoreNet's autograd node checks it in backward
     self.graphs = {}               # captured training steps (CoreNet.train_step): loss name -> CUDAGraph
     self.eager_steps = 0           # fused steps run eagerly on this plan (the first one also sizes every workspace)
     self.eval_graph = None         # captured eval-mode forward (CoreNet._forward_eval_graph)
-    self.ray_side = os.environ.get("CRN_RAY_SIDE", "1") != "0"      # the ray scatters of the backward on the side stream
     self.eval_eager = 0
     self._views = {}
     dev = eng.device
@@ -759,8 +742,7 @@ class Plan:
     # the saved index tensors of the ray-sample backward (autograd keeps them in the reference: ray_traced_skip_connection.py:
     # 118-135): one uint16 per voxel of the 8^3 ... 64^3 skip grids, written by the training-mode gather, read by the scatter
     self.ray_idx = ({k: t.zeros(B, (2 * self.dec[k]["r"]) ** 3, dtype=t.int16, device=dev) for k in sk}
-                    if hasattr(self.be, "ray_sample_fwd_idx") and os.environ.get("CRN_RAY_IDX", "1") != "0" and
-                    max(h * w for h, w in self.skip_hw.values()) < 65535 else None)
+                    if hasattr(self.be, "ray_sample_fwd_idx") and max(h * w for h, w in self.skip_hw.values()) < 65535 else None)
     gs_n = {k: B * sk[k] * self.skip_hw[k][0] * self.skip_hw[k][1] for k in sk}
     self.gsmap_slab = f(sum(gs_n.values()))
     self.gsmap, o = {}, 0
@@ -785,22 +767,17 @@ class Plan:
     # Every hand-over to the side stream costs the data-gradient chain an event record (a marker packet between two dependent
     # launches: ~3.5 us).  The encoder's weight gradients are therefore handed over one bottleneck at a time (3-4 convolutions behind
     # ONE event) and a gradient bucket's un-pack rides on the hand-over in front of it: 7.58 -> 7.44 ms per step
-    # (profiles/r05_wgrad_handover.txt; per conv 0, per 1 / 2 / 3 / 6 blocks, per bucket 99; CRN_WG_BATCH_DEC=1: decoder stages too)
-    self.wg_batch = int(os.environ.get("CRN_WG_BATCH", "1")) if use_side else 0      # bottlenecks per hand-over (0: per conv)
-    self.wg_batch_dec = os.environ.get("CRN_WG_BATCH_DEC", "0") == "1"
+    # (profiles/r05_wgrad_handover.txt; per conv 0, per 1 / 2 / 3 / 6 blocks, per bucket 99)
     self._handed_over = False
     self._g_compact = None
     self._wg_pending = []
-    self._wg_blocks = 0
     # the ray-traced skip path (offset channels -> 1x1 compress -> ray sample; backward: scatter -> compress gradients)
     # hangs off the encoder's stage outputs and joins the main chain only at the consuming decoder stage (backward: at the
     # start of the encoder's backward pass): it runs on the side stream beside the encoder / decoder chain
-    self.async_skip = use_side and os.environ.get("CRN_ASYNC_SKIP", "1") != "0"
     self._skip_ev = {k: (t.cuda.Event(), t.cuda.Event()) for k in (2, 3, 4, 5)} if use_side else None
     self._skip_bwd_ev = {k: t.cuda.Event() for k in (2, 3, 4, 5)} if use_side else None
     self._skip_bwd_done = t.cuda.Event() if use_side else None
     self._skip_async_live = False
-    self._bucket_ev = [t.cuda.Event() for _ in GRAD_BUCKET_LABELS] if use_side else None
 
   # ------------------------------------------------------------------ cached views
   def _cached(self, key, fn):
@@ -912,17 +889,15 @@ class Plan:
     (its sums came out of the conv launch, crn_conv_fwd_bf3_slabs_bnbwd); False: g is written, the caller runs bn_bwd."""
     eng, be = self.eng, self.be
     gvw = self.vw(g)
-    fusable = (eng.bn_bwd_fuse and hasattr(be, "conv_dgrad_bn_bwd") and cv.wop_kind == "slab" and cv.wop_d is not None
-               and self._math(cv, "dgrad") == "bf16x3" and cv.name not in eng.bn_bwd_fuse_skip)
+    fusable = (hasattr(be, "conv_dgrad_bn_bwd") and cv.wop_kind == "slab" and cv.wop_d is not None
+               and self._math(cv, "dgrad") == "bf16x3")
     if not fusable:
-      if eng.defer_reduce:
-        be.splitk_defer()                        # g is read next by the norm's backward, which adds up the splits
+      be.splitk_defer()                          # g is read next by the norm's backward, which adds up the splits
       self._dgrad(cv, dy, gvw)
       return False
     gd = cv.dgrad
     done = [False]
-    if eng.defer_reduce:
-      be.splitk_defer()                          # (a launch that splits cannot fuse: its sum goes to the norm's own first pass)
+    be.splitk_defer()                            # (a launch that splits cannot fuse: its sum goes to the norm's own first pass)
     def run():
       done[0] = be.conv_dgrad_bn_bwd(dy, cv.wop_d, gd.npad, gvw, g, gd.window, gd.pad_lo, (gd.n_boxes, gd.c_boxes),
                                      x, Cn * S, self.B, Cn, S, True, b.gamma, b.scale, b.shift, b.saved, dx, Cn * S,
@@ -938,7 +913,7 @@ class Plan:
     math = self._math(cv, "wgrad")
     if self.stem_fast and cv.name == "encoder.stage1.conv.":
       math = "stem"               # (falls back to the generic engine by itself where it does not apply)
-    if (self.eng.encoder_e2d and self.eng.wgrad_2d and g.window in ((1, 1, 1), (1, 3, 3)) and self._wg2d_shape_ok(dy, g.window)
+    if (self.eng.encoder_e2d and g.window in ((1, 1, 1), (1, 3, 3)) and self._wg2d_shape_ok(dy, g.window)
         and (cv.name.startswith("encoder.stage") and not cv.name.startswith("encoder.stage1")
              or cv.name.startswith("decoder.rt_skip"))):
       math = "bf16x3_2d"          # both operands straight from HBM, K = positions (csrc/conv_e2d.hip)
@@ -948,7 +923,7 @@ class Plan:
       self._timed("wgrad " + cv.name, lambda: self.be.conv_wgrad(
           x, tr, dy, cv.gwf, g.npad, g.window, g.pad_lo, False, boxes=(g.n_boxes, g.c_boxes), math=math, **self._ximg_kw(math)))
       return
-    if self.wg_batch and (cv.name.startswith("encoder.") or self.wg_batch_dec):
+    if cv.name.startswith("encoder."):
       # the encoder's small weight gradients are handed to the side stream one bottleneck at a time (_flush_wgrads): ONE event on
       # the data-gradient chain per block instead of one per convolution
       self._wg_pending.append((cv, x, tr, dy, math, self._ximg_kw(math)))
@@ -996,7 +971,6 @@ class Plan:
       if then is not None:
         then()
     self._wg_pending = []
-    self._wg_blocks = 0
 
   def _join_side(self):
     """Main stream waits for every weight gradient issued on the side stream."""
@@ -1011,7 +985,7 @@ class Plan:
 
   # ------------------------------------------------------------------ forward
   def forward(self, image_u8: t.Tensor, v2s: t.Tensor, offset: t.Tensor, training: bool) -> t.Tensor:
-    self._skip_async_live = bool(training and self.async_skip and self.trace is None)
+    self._skip_async_live = bool(training and self.side is not None and self.trace is None)
     if self._skip_async_live:
       self._decoder_inputs(v2s, offset)            # the skip path starts inside the encoder: it needs them now
     self.forward_encoder(image_u8, training)
@@ -1164,7 +1138,7 @@ class Plan:
         # LAST one -- the 8^3 skip into this stage -- covers all four; one marker on the decoder's chain instead of four
         t.cuda.current_stream().wait_event(self._skip_ev[2][1])
       self._stats(b1_, d["u"], S, d["cin"] * S, True, training)
-      if training and eng.defer_reduce:
+      if training:
         be.splitk_defer()                      # (stages 2-4 split K: the statistics below add the partial sums up)
       cc = cv[p + "c1."]
       parts = [0]
@@ -1228,7 +1202,7 @@ class Plan:
     ba, bb, bc = bn[p + "op_a.bn."], bn[p + "op_b.bn."], bn[p + "op_c.bn."]
     # (training: every conv is followed directly by the statistics of its norm, which can add up the partial sums of
     # a split-K conv itself: crn_splitk_defer)
-    defer = be.splitk_defer if training and self.eng.defer_reduce else (lambda: None)
+    defer = be.splitk_defer if training else (lambda: None)
     defer()
     self._conv(cv[p + "op_a.conv."], xin, None, self.vw(blk["ya"]))
     self._stats(ba, blk["ya"], S, f1 * S, False, training)
@@ -1242,7 +1216,7 @@ class Plan:
       pre, sB_pre = None, 0
     # training on the HIP backend: the statistics of op_c's norm and the block tail (norm + shortcut + ReLU) are one
     # launch (crn_batch_renorm_stats_tail) -- so the shortcut branch of a down-sampling block goes before op_c
-    fused_tail = training and hasattr(be, "bn_stats_tail") and self.eng.fuse_tail
+    fused_tail = training and hasattr(be, "bn_stats_tail")
     res, rsc, rsh = cur, None, None
     def shortcut():
       bs = bn[p + "shortcut.bn."]
@@ -1256,7 +1230,7 @@ class Plan:
     self._conv(cv[p + "op_c.conv."], self.vw(blk["yb"]), Transform(bb.scale, bb.shift, post_relu=True),
                self.vw(blk["yc"]))
     if fused_tail:
-      nxt = blk.get("xs_next") if os.environ.get("CRN_FUSE_GATHER", "1") != "0" else None
+      nxt = blk.get("xs_next")
       with _lib.roctx_range("bn_stats_tail C%d S%d" % (bc.C, S)):
         be.bn_stats_tail(blk["yc"], B, f3, S, f3 * S, bc.gamma, bc.beta, bc.rmean, bc.rvar, bc.nbt, BN_EPS, BN_MOMENTUM,
                          True, bc.scale, bc.shift, bc.saved, res, rsc, rsh, f3 * S, pre, sB_pre, blk["out"], f3 * S, True,
@@ -1285,17 +1259,12 @@ class Plan:
     _, lo, hi = eng.grad_buckets[i]
     tiles = eng.bucket_unpack_tiles(i)
     def run():
-      if (tiles[0].numel() or tiles[3].numel()) and not _TIMING_ONLY_SKIP_COPIES & 4:
+      if tiles[0].numel() or tiles[3].numel():
         self.be.copy_tiles(eng.gpacked, eng.store.grads, tiles, reverse=True)
       hook(eng.store.grads[lo:hi])
     if self.side is None or self.trace is not None:
       return run()
-    if self.wg_batch:
-      return self._flush_wgrads(then=run)          # (its event also covers the bucket's bias / norm gradients on the main stream)
-    self._bucket_ev[i].record()                  # bias / norm gradients of the bucket are written on the main stream
-    with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
-      self.side.wait_event(self._bucket_ev[i])
-      run()
+    return self._flush_wgrads(then=run)            # (its event also covers the bucket's bias / norm gradients on the main stream)
 
   def backward(self, glogits: t.Tensor, grad_hook=None):
     """Fills eng.store.grads with d loss / d params given d loss / d logits.  With `grad_hook`, finished
@@ -1311,7 +1280,7 @@ class Plan:
     if not eng._gpacked_zeroed:
       be.zero(eng.gpacked)
     eng._gpacked_zeroed = False
-    skips_on_side = self.async_skip and self.side is not None and self.trace is None and self.ray_side
+    skips_on_side = self.side is not None and self.trace is None
     if skips_on_side:
       # the four skip-map gradients are written and read on the side stream only (scatter -> compress gradients): zeroed there,
       # off the step's chain (a memset is a launch of its own)
@@ -1331,23 +1300,18 @@ class Plan:
       b1_, b2_ = bn[p + "b1."], bn[p + "b2."]
       ctot = g_out.shape[1]
       if k < 6:    # ray-traced skip: scatter-add, compress conv grads
-        skip_bwd_async = self.async_skip and self.side is not None and self.trace is None
-        if skip_bwd_async:
+        if skips_on_side:
           # off the data-gradient chain: the feature-map gradients are only needed when the encoder's backward starts.
-          # The scatter goes with it (CRN_RAY_SIDE=0 keeps it on the main stream: +0.07 ms per step).  Beside the split-bf16
+          # The scatter goes with it (on the main stream it costs +0.07 ms per step).  Beside the split-bf16
           # convolutions of round 3 its sums differed from run to run by 1e-2 ... 1e-1 of the map's range: three dependent
           # MFMAs of a neighbour wave with idle cycles between them made VALU results of the scatter's waves go missing
           # (tools/mfma_neighbour.py).  The convolutions issue their three products as one block of adjacent
           # MFMAs now (mfma3, csrc/conv_bf3.hip): beside them the scatter is exact in 82 of 82 steps and in 660 of 660
           # two-kernel runs; test_run_to_run_gradient_spread_default_mode watches it.  (Round 5: the scatter has no projection left.)
-          ray_side = self.ray_side
-          if not ray_side:
-            self._ray_bwd(k, g_out)
           self._skip_bwd_ev[k].record()             # (also the hand-over event of this stage's transposed-conv weight gradient below)
           with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
             self.side.wait_event(self._skip_bwd_ev[k])
-            if ray_side:
-              self._ray_bwd(k, g_out)
+            self._ray_bwd(k, g_out)
             self._skip_bwd(k, g_out, on_side=True)
             if k == 2:
               self._skip_bwd_done.record(self.side)
@@ -1360,7 +1324,7 @@ class Plan:
       self._wgrad(ct, self.vw(d["w"]), tr2, gv)
       self._handed_over = False
       if k == 6:   # gradient of the logits comes from the loss kernel; below it is a bn_bwd output
-        if (self.side is not None and self.trace is None and not self.wg_batch_dec and os.environ.get("CRN_BIAS_GRAD_SIDE", "1") != "0"):
+        if self.side is not None and self.trace is None:
           # one pass over the loss gradient (470 MB at 14 classes) whose result is only read by the bucket's un-pack: it follows the
           # layer's weight gradient on the side stream (ordered behind the same hand-over event) instead of sitting in front of the
           # data-gradient chain
@@ -1392,8 +1356,6 @@ class Plan:
                   b1_.gamma, b1_.scale, b1_.shift, b1_.saved, d["gu"], d["cin"] * S, b1_.dgamma, b1_.dbeta,
                   dsum=cprev.dbias, ndsum=cprev.n_ref)
       g_out = d["gu"]
-      if self.wg_batch_dec:
-        self._flush_wgrads()
       if k == 3:
         self._grads_ready("decoder.stage_3.", grad_hook)
     # stage_1 / stage_0
@@ -1410,7 +1372,7 @@ class Plan:
                   s.view("decoder.stage_0.weight", grad=True), s.view("decoder.stage_0.bias", grad=True))
     self._grads_ready("decoder.stage_0.", grad_hook)
     # encoder
-    if self.async_skip and self.side is not None and self.trace is None:
+    if skips_on_side:
       t.cuda.current_stream().wait_event(self._skip_bwd_done)          # gfeat of all four stages
     f5, g5 = self.feat["stage5"], self.gfeat["stage5"]
     last = self.blocks[-1]
@@ -1421,9 +1383,7 @@ class Plan:
     g_in = None          # gradient wrt the block's output (post-ReLU), None for the last block
     for blk in reversed(self.blocks):
       g_in = self._block_bwd(blk, g_in)
-      self._wg_blocks += 1
-      if self._wg_blocks >= self.wg_batch:
-        self._flush_wgrads()
+      self._flush_wgrads()
       if blk["prefix"] in GRAD_BUCKET_LABELS:
         self._grads_ready(blk["prefix"], grad_hook)
     # stem: g_in = d p1
@@ -1465,7 +1425,7 @@ class Plan:
     ft = self.feat[self.skip_src[k]]
     if on_side:                                 # already on the weight-gradient stream: no hand-over event
       g = cs.fwd
-      math = ("bf16x3_2d" if (eng.encoder_e2d and eng.wgrad_2d and self._wg2d_shape_ok(self.vw(self.gsmap[k]), g.window))
+      math = ("bf16x3_2d" if (eng.encoder_e2d and self._wg2d_shape_ok(self.vw(self.gsmap[k]), g.window))
               else self._math(cs, "wgrad"))
       with _lib.roctx_range("wgrad " + cs.name):
         be.conv_wgrad(self.vw(ft), None, self.vw(self.gsmap[k]), cs.gwf, g.npad, g.window, g.pad_lo, False,
@@ -1487,7 +1447,7 @@ class Plan:
     # d pre = (out > 0 ? g_out : 0) [+ the gradient that arrived through the skip connection]: formed by the backward launch of
     # op_c's norm itself on the HIP backend (crn_batch_renorm_bwd_head), by a launch of its own otherwise
     # (g_out None: gpre already holds d pre -- last block of the encoder)
-    fused_head = g_out is not None and hasattr(be, "bn_bwd_head") and eng.fuse_tail
+    fused_head = g_out is not None and hasattr(be, "bn_bwd_head")
     # g_out may still be in the compact form the down-sampling block behind this one left it in (below): the fused head reads
     # it from there, anything else gets it expanded first
     gc, self._g_compact = self._g_compact, None
@@ -1512,14 +1472,12 @@ class Plan:
     trb = Transform(bb.scale, bb.shift, post_relu=True)
     tra = Transform(ba.scale, ba.shift, post_relu=True)
     self._wgrad(cc, self.vw(blk["yb"]), trb, self.vw(blk["gyc"]))
-    if self.eng.defer_reduce:
-      be.splitk_defer()                       # the norm's backward below is the only reader of gab: it adds up the splits
+    be.splitk_defer()                         # the norm's backward below is the only reader of gab: it adds up the splits
     self._dgrad(cc, self.vw(blk["gyc"]), self.vw(blk["gab"]))
     be.bn_bwd(blk["yb"], f2 * S, blk["gab"], f2 * S, B, f2, S, False, True, bb.gamma, bb.scale, bb.shift,
               bb.saved, blk["gyb"], f2 * S, bb.dgamma, bb.dbeta, dsum=cb.dbias, ndsum=cb.n_ref)
     self._wgrad(cb, self.vw(blk["ya"]), tra, self.vw(blk["gyb"]))
-    if self.eng.defer_reduce:
-      be.splitk_defer()
+    be.splitk_defer()
     self._dgrad(cb, self.vw(blk["gyb"]), self.vw(blk["gaa"]))
     be.bn_bwd(blk["ya"], f1 * S, blk["gaa"], f1 * S, B, f1, S, False, True, ba.gamma, ba.scale, ba.shift,
               ba.saved, blk["gya"], f1 * S, ba.dgamma, ba.dbeta, dsum=ca.dbias, ndsum=ca.n_ref)
@@ -1537,7 +1495,7 @@ class Plan:
       self._dgrad(ca, self.vw(blk["gya"]), gv)
       self._dgrad(csn, self.vw(blk["gys"]), gv, accumulate=True)
       if blk["stride"] == 2:
-        if hasattr(be, "bn_bwd_head") and eng.fuse_tail and os.environ.get("CRN_FUSE_GATHER", "1") != "0":
+        if hasattr(be, "bn_bwd_head"):
           self._g_compact = blk["gxs"]                # expanded by its reader: the norm backward at the head of the block in front
         else:
           be.stride2_scatter(blk["gxs"], gin)         # every element of gin is written (zeros between the samples)

@@ -311,7 +311,7 @@ def test_convt_parity_walk_fwd_dgrad(be, cout, dims, B):
   assert e <= 2e-5, ("wgrad", e)
   assert float(t.where(real, t.zeros(()), dwg.cpu()).abs().max()) == 0.0             # structural zeros of the packed layout stay zero
   # the two ways the workgroups get T(x): the operand image made ahead by the caller (crn_convt_s2k7_ximage, what the engine does
-  # under the forward pass) and the fused transform + split of the fp32 input (CRN_CT_XIMG=0) -- same contract
+  # under the forward pass) and the fused transform + split of the fp32 input (the C entry with a null image) -- same contract
   img = be.convt_ximage(xg, trg)
   assert img is not None
   # ... the image itself, bit for bit: entry [b][chunk * 2 + (hi, lo)][position] = the 8 channels of the chunk of T(x) as bf16, hi = the
@@ -321,17 +321,18 @@ def test_convt_parity_walk_fwd_dgrad(be, cout, dims, B):
   want_img = t.stack([hi[:, :8], lo[:, :8], hi[:, 8:], lo[:, 8:]], 1).reshape(B, 4, 8, -1).permute(0, 1, 3, 2).contiguous()   # [B][4][S][8]
   got_img = img[:want_img.numel() * 2].view(t.bfloat16).view(B, 4, -1, 8).cpu()
   assert t.equal(got_img.view(t.int16), want_img.view(t.int16)), "operand image differs from bf16 hi / lo of T(x)"
-  for label, kw, env in (("image made ahead", {"ximg": img}, None), ("fused staging", {}, "0")):
-    old_env = os.environ.get("CRN_CT_XIMG")
-    if env is not None:
-      os.environ["CRN_CT_XIMG"] = env
-    try:
-      dwg3 = t.full((fwd.index.size,), 3.0, device=DEV)
-      be.conv_wgrad(V.view_of(xg), trg, yv(dyg), dwg3, fwd.npad, fwd.window, fwd.pad_lo, True, boxes=(fwd.n_boxes, fwd.c_boxes), math="ct_par", **kw)
-    finally:
-      if env is not None:
-        if old_env is None: os.environ.pop("CRN_CT_XIMG")
-        else: os.environ["CRN_CT_XIMG"] = old_env
+  from corenet_amd import _lib
+  from corenet_amd.backend import _ctr
+  for label in ("image made ahead", "fused staging"):
+    dwg3 = t.full((fwd.index.size,), 3.0, device=DEV)
+    if label == "fused staging":
+      xv, dv = V.view_of(xg), yv(dyg)
+      rc = be.lib._crn_convt_s2k7_wgrad_bf3(xg.data_ptr(), xv.sB, xv.B, xv.D, xv.H, xv.W, _ctr(trg), dyg.data_ptr(), dyg.stride(0),
+                                            dyg.stride(1), dv.C // 8, dwg3.data_ptr(), fwd.npad, 1, None, _lib.stream())
+      assert rc == 0, rc
+    else:
+      be.conv_wgrad(V.view_of(xg), trg, yv(dyg), dwg3, fwd.npad, fwd.window, fwd.pad_lo, True, boxes=(fwd.n_boxes, fwd.c_boxes),
+                    math="ct_par", ximg=img)
     e3 = float((t.where(real, dwg3.cpu(), t.zeros(())) - want).abs().max() / want.abs().max())
     print(f"parity walk cout {cout} {dims} wgrad ({label}): max-abs-err/max = {e3:.2e}")
     assert e3 <= 2e-5, ("wgrad", label, e3)

@@ -57,7 +57,7 @@ tr = Transform(sc, shf, pre_relu=True)
 yv = V.space_to_depth_view(V.view_of(y), (2, 2, 2), parity_major=True) if kind == "convT" else V.view_of(y)
 dw = t.zeros(wf.numel()).cuda()
 sf = sd = None
-if MATH == "bf16x3" and os.environ.get("CRN_BF3_SLABS", "1") != "0":      # weights pre-arranged as slab images
+if MATH == "bf16x3":      # weights pre-arranged as slab images
   nsf, nsd = G.slab_entries(fwd), G.slab_entries(dgr)
   desc, blocks = G.operand_table([(0, 0, fwd, True), (wf.numel(), nsf, dgr, True)])
   slabs = t.zeros((nsf + nsd) * 32, dtype=t.uint8, device="cuda")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the encoder engine (crn_conv2d_bf3, csrc/conv_e2d.hip) on the encoder's layer shapes at batch 4:
 HIP events around `iters` back-to-back calls (kernel + split-K reduction when one is used), forward form (fused
-transform + bias).  usage: bench_e2d.py [iters]      tuning knobs: CRN_E2D_FILL, CRN_E2D_SPLITS"""
+transform + bias).  usage: bench_e2d.py [iters]"""
 import os, sys
 if os.environ.get("CRN_E2D_DBG"):
   os.environ.setdefault("CRN_TOOLS_LIB", "1")        # the stamp read-back exists only in the tools build of the library

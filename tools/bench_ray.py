@@ -2,8 +2,7 @@
 """Ray-sample kernels alone at the four decoder scales in the plan's layouts (B = 4): gather, gather + saved index tensor,
 projection alone, scatter from the saved indices, plain scatter (projection launch + scatter).  The gradient is the tail
 channels of the stage's concat-buffer gradient (batch stride (cout + skip) * S), the map gradient is zeroed by the caller.
-Tuning aids of the scatter: CRN_RAY_CN (4 | 12), CRN_RAY_ZSEG (8 | 16), CRN_RAY_TX (32 | 64); with the tools build
-(CRN_TOOLS_LIB=1) CRN_RAY_DBG ablations: 1 no LDS adds, 2 no window write-out, 4 every plane = the segment's first."""
+With the tools build (CRN_TOOLS_LIB=1) CRN_RAY_DBG ablations: 1 no LDS adds, 2 no window write-out, 4 every plane = the segment's first."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("CRN_RAY_DBG"):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The stem convolution (ZeroPad2d(3) + Conv2d 7x7 stride 2, 3 -> 64 on 256^2 images, resnet50.py:122-131) through the
 C ABI the way the engine calls it (2x2 space-to-depth view of the image, 4x4 window over 12 channels).
-usage: bench_stem.py [iters]     knobs: CRN_FWD_FORCE=M,N  CRN_FWD_SPLITS"""
+usage: bench_stem.py [iters]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch as t
@@ -23,7 +23,7 @@ t.cuda.synchronize(); a, b = t.cuda.Event(enable_timing=True), t.cuda.Event(enab
 a.record()
 for _ in range(iters): run()
 b.record(); t.cuda.synchronize()
-print(f"stem fwd {os.environ.get('CRN_FWD_FORCE')} splits {os.environ.get('CRN_FWD_SPLITS')}: {a.elapsed_time(b) / iters * 1e3:.1f} us")
+print(f"stem fwd: {a.elapsed_time(b) / iters * 1e3:.1f} us")
 # the stem's own kernels (csrc/stem_conv.hip)
 def timeit(fn, label):
   for _ in range(3): fn()
@@ -37,4 +37,4 @@ timeit(lambda: be.stem_conv_fwd(img, wf, bias, y, True), "stem_conv_fwd + BatchR
 dy = t.randn(4, 64, 128, 128).cuda(); dw = t.zeros(wf.numel()).cuda()
 timeit(lambda: be.conv_wgrad(xv, None, V.view_of(dy), dw, g.npad, g.window, g.pad_lo, False), "generic wgrad")
 timeit(lambda: be.conv_wgrad(xv, None, V.view_of(dy), dw, g.npad, g.window, g.pad_lo, False, math="stem"),
-       f"stem_conv_wgrad (CRN_STEM_WG_BLOCKS={os.environ.get('CRN_STEM_WG_BLOCKS')})")
+       "stem_conv_wgrad")

@@ -14,4 +14,4 @@ for tag, nc, nbt, B in (("h7_train_b1", 2, 0, 1), ("h7_train_b2_nbt30k", 2, 3000
   image, v2s, off, grid = O.synthetic_batch(B, 0, nc)
   with t.no_grad():
     logits = m(image.cuda(), v2s.cuda(), off.cuda())
-  print(os.environ.get("CRN_E2D_KINDS"), os.environ.get("CRN_E2D_FWD_STAGES"), tag, f"{relerr(logits[:, :, ::16, ::16, ::16], z['logits_sub']):.2e}", flush=True)
+  print(tag, f"{relerr(logits[:, :, ::16, ::16, ::16], z['logits_sub']):.2e}", flush=True)

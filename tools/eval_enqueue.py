@@ -2,7 +2,6 @@
 """Eval-mode forward: host enqueue time vs total time per batch (is serving host-bound?), launch by launch and as a captured HIP
 graph of the plan's forward (the graph path is an experiment of this tool, not of the product)."""
 import os, sys, time
-os.environ["CRN_EVAL_GRAPH"] = "0"          # the launch-by-launch leg below must be the launch-by-launch forward
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch as t, bench
 from corenet_amd import _lib
@@ -12,15 +11,17 @@ m = CoreNet(CoreNetConfig(DecoderConfig((128, 128, 128), 2, 2, 64, 0.75)), devic
 image, v2s, off, grid = [x.cuda() for x in bench.synthetic_batch(B, 0, 2)]
 m.eval()
 with t.no_grad():
-  for _ in range(3): m(image, v2s, off)
+  m(image, v2s, off)                          # packs the weights
+  plan = m.engine.plan(B)
+  fwd = lambda: plan.forward(image, v2s, off, training=False)      # launch by launch (CoreNet's eval forward replays a graph)
+  for _ in range(3): fwd()
   t.cuda.synchronize()
   n = 20
   t0 = time.perf_counter()
-  for _ in range(n): out = m(image, v2s, off)
+  for _ in range(n): out = fwd()
   t1 = time.perf_counter(); t.cuda.synchronize(); t2 = time.perf_counter()
   print(f"eval forward B={B}, launch by launch: enqueue {1e3 * (t1 - t0) / n:.2f} ms, total {1e3 * (t2 - t0) / n:.2f} ms per batch")
   ref = out.clone()
-  plan = m.engine.plan(B)
   plan.in_image.copy_(image); plan.in_v2s.copy_(v2s); plan.in_off.copy_(off)
   g = t.cuda.CUDAGraph(); cap = t.cuda.Stream()
   m.engine.be.splitk_reserve(cap)

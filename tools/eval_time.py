@@ -12,4 +12,4 @@ with t.no_grad():
   a.record()
   for _ in range(20): m(image, v2s, off)
   b.record(); t.cuda.synchronize()
-print(os.environ.get("M", "bf16x3"), os.environ.get("CRN_E2D"), os.environ.get("CRN_BF3_SLABS"), f"eval forward {a.elapsed_time(b)/20:.3f} ms/batch")
+print(os.environ.get("M", "bf16x3"), f"eval forward {a.elapsed_time(b)/20:.3f} ms/batch")

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: pmc4.sh <mode> <layer> "<counters>"   (honours CRN_DBG_MODE etc. from the environment)
+# usage: pmc4.sh <mode> <layer> "<counters>"
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/pm4
