@@ -8,7 +8,6 @@ an executable specification of each kernel's contract (test-only).
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import torch as t
@@ -451,7 +450,6 @@ class HipBackend:
       self.lib.crn_fill_voxels(ptr(grid), ptr(out), _DTYPE_CODE[grid.dtype], N, D, H, W, ptr(ws), n,
                                _lib.stream())
     else:      # strided views on either side (the reference's packed accessors, fill_voxels_gpu.cu:146-163)
-      import ctypes as C
       gs = (C.c_int64 * 4)(*grid.stride())
       os_ = (C.c_int64 * 4)(*out.stride())
       self.lib.crn_fill_voxels_strided(ptr(grid), gs, ptr(out), os_, _DTYPE_CODE[grid.dtype], N, D, H, W,

@@ -22,7 +22,7 @@ import torch as t
 from torch import nn
 
 from corenet_amd import _lib
-from corenet_amd.model.engine import Engine, IMAGE_HW, check_image_hw
+from corenet_amd.model.engine import Engine, LOSS_KINDS, check_image_hw, on_stream
 
 
 @dataclasses.dataclass(frozen=True)
@@ -61,7 +61,6 @@ def _release_graphs():
     except Exception:
       pass
   try:                                # graphs of models the garbage collector dropped (Engine.orphan_graph_resources)
-    from corenet_amd.model.engine import Engine
     Engine.drain_orphans()
   except Exception:
     pass
@@ -397,7 +396,6 @@ class CoreNet(nn.Module):
     walks the ~650 kernel nodes on the host (3.6 ms per step vs 6.5 ms launch by launch through ctypes) and the
     replay loses the overlap of the weight-gradient stream with the data-gradient chain (15.2 vs 13.5 ms per
     step), so launch by launch stays the default while the GPU needs more than the host's 6.5 ms per step."""
-    from corenet_amd.model.engine import LOSS_KINDS
     eng = self.engine
     self._check_image(image)
     B, C = image.shape[0], eng.num_classes
@@ -430,14 +428,13 @@ class CoreNet(nn.Module):
                           plan.glogits, 1.0)
       if all_reduce is not None and getattr(all_reduce, "overlap", False):
         all_reduce.pushed.clear()
-        step_buckets = (hasattr(all_reduce, "opt_stream") and plan.side is not None and plan.trace is None
-                        and all_reduce.opt_stream() is not None)
+        step_buckets = hasattr(all_reduce, "opt_stream") and plan.overlap and all_reduce.opt_stream() is not None
         if step_buckets:
           # Adam per bucket behind its all-reduce, on the exchange's optimizer stream: the update runs under the rest of
           # backward on every rank, as it does without an exchange (adam_bucket_hook)
           ost = all_reduce.opt_stream()
           ost.wait_stream(t.cuda.current_stream())                # (first step: the moments are allocated on this stream)
-          with t.cuda.stream(ost), _lib.pinned_stream(ost):
+          with on_stream(ost):
             eng.adam_step_graphable(lr, adam_eps, grad_scale=1.0 / world_size, launch=False)
           all_reduce.after_bucket = eng.adam_bucket_hook()
         plan.backward(plan.glogits, grad_hook=all_reduce.push)   # buckets are reduced while backward runs
@@ -446,10 +443,10 @@ class CoreNet(nn.Module):
           all_reduce.after_bucket = None
           eng.weights_dirty = True
           return plan.loss
-      elif all_reduce is None and plan.side is not None and plan.trace is None:
+      elif all_reduce is None and plan.overlap:
         # no exchange: every finished bucket of the grad slab is un-packed AND stepped on the side stream
         # (the step's Adam scalars are written on the stream that runs the bucket updates: one launch off the main chain)
-        with t.cuda.stream(plan.side), _lib.pinned_stream(plan.side):
+        with plan._on_side():
           eng.adam_step_graphable(lr, adam_eps, grad_scale=1.0 / world_size, launch=False)
         plan.backward(plan.glogits, grad_hook=eng.adam_bucket_hook())
         eng.weights_dirty = True
@@ -463,7 +460,6 @@ class CoreNet(nn.Module):
 
   def _step_body(self, plan, loss: str):
     """The static part of a fused step on the plan's own input buffers (what the graph captures)."""
-    from corenet_amd.model.engine import LOSS_KINDS
     eng = self.engine
     eng.weights_dirty = True                   # the step starts by packing the (just stepped) parameters
     plan.forward(plan.in_image, plan.in_v2s, plan.in_off, training=True)

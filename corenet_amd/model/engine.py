@@ -20,10 +20,8 @@ Dataflow choices (MI355X-first):
 """
 from __future__ import annotations
 
-import os
-
 import dataclasses
-import math
+import os
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -202,6 +200,53 @@ class Conv:
   ct_kind: str = ""                  # "par": the parity walk (> 8 classes, also the weight gradient); "res": resident weights (2 classes)
 
 
+@dataclasses.dataclass(slots=True, eq=False)
+class EncBlock:
+  """One ResNet bottleneck of a plan: geometry, buffers, and the state a step leaves between its launches."""
+  prefix: str; stage: str; cin: int; f: Tuple[int, int, int]; stride: int; h: int; w: int
+  down: bool                           # block "a" of a stage: has the shortcut conv (ys, gys, gin)
+  final: bool                          # last block of a stage: its pre-ReLU output is Plan.feat[stage]
+  ya: t.Tensor; yb: t.Tensor; yc: t.Tensor; ys: Optional[t.Tensor]; out: t.Tensor       # conv outputs (pre-norm), block output
+  gpre: t.Tensor; gyc: t.Tensor; gab: t.Tensor; gyb: t.Tensor; gaa: t.Tensor; gya: t.Tensor
+  gys: Optional[t.Tensor]; gin: Optional[t.Tensor]
+  # the stride-2 1x1 convs (op_a and the shortcut, resnet50.py:94-97) read a compacted copy of the sub-sampled block input, and
+  # their data gradients meet in a compact buffer before they are scattered back: plain tensors -> the pointwise kernel
+  # instead of strided views
+  xs: Optional[t.Tensor]; gxs: Optional[t.Tensor]
+  xs_next: Optional["EncBlock"] = None   # the stride-2 block behind this one: this block's tail launch writes its xs
+  inp: Optional[t.Tensor] = None         # per step: the block's input, kept by forward for backward
+  xs_filled: bool = False                # per step: xs was written by the tail launch of the block in front
+
+
+@dataclasses.dataclass(slots=True, eq=False)
+class DecStage:
+  """One decoder stage of a plan: concat buffer u (the stage's input), mid tensor w, and their gradients."""
+  cin: int; cmid: int; cout: int; r: int
+  u: t.Tensor; gu: t.Tensor; w: t.Tensor; gw: t.Tensor; gv1: t.Tensor; gv2: t.Tensor
+
+  def __getitem__(self, field: str):     # bench.py reads plan.dec[6]["u"] and ["gu"]: the benchmark is not edited
+    return getattr(self, field)
+
+
+class on_stream:
+  """with on_stream(s, after=ev): torch ops and library calls of the block go to stream `s` (torch's current stream and the
+  pinned library stream), behind event `ev` when one is given.  A plain class: a step enters some 30 of these."""
+  __slots__ = ("stream", "after", "_torch", "_pin")
+
+  def __init__(self, stream, after=None):
+    self.stream, self.after = stream, after
+    self._torch, self._pin = t.cuda.stream(stream), _lib.pinned_stream(stream)
+
+  def __enter__(self):
+    self._torch.__enter__(); self._pin.__enter__()
+    if self.after is not None:
+      self.stream.wait_event(self.after)
+
+  def __exit__(self, *exc):
+    self._pin.__exit__(*exc); self._torch.__exit__(*exc)
+
+
+_NO_KW = {}
 _ORPHANS = []      # (backend, graphs, capture stream) of engines dropped by the garbage collector: Engine.orphan_graph_resources
 
 
@@ -492,7 +537,7 @@ class Engine:
       tab, nbytes = fn(shape, wofs)
       img = t.zeros(nbytes, dtype=t.uint8, device=self.device)
       setattr(self.convs[name], field, img)
-      self.ct_tables[kind] = (t.as_tensor(tab, device=self.device), img, None)
+      self.ct_tables[kind] = (t.as_tensor(tab, device=self.device), img)
 
   def _build_operands(self, reg, idx_parts):
     """Operand blocks of the encoder engine: which layers, where in eng.wop, and the layer tables of the
@@ -549,8 +594,7 @@ class Engine:
       if k in self.op_tables:
         self.be.bf3_operands(self.packed, self.op_tables[k], self.wop)
       if k in self.ct_tables:
-        tab, img, _ = self.ct_tables[k]
-        self.be.bf3_gather_image(self.store.params, tab, img)
+        self.be.bf3_gather_image(self.store.params, *self.ct_tables[k])
 
   def _tiles_dev(self, parts):
     """Device tables of one pack / un-pack: the parts that are plain transposes as LDS blocks (conv_geometry.mat_index,
@@ -690,26 +734,15 @@ class Plan:
       for bl in blocks:
         st = stride if bl == "a" else 1
         ho, wo = (hi + st - 1) // st, (wi + st - 1) // st        # 1x1 stride-2 conv without padding: ceil (resnet50.py:94-97)
-        blk = dict(prefix=f"encoder.{name}.{bl}.", cin=cin, f=filt, stride=st, hin=hi, win=wi, h=ho, w=wo,
-                   down=(bl == "a"), final=(bl == blocks[-1]), stage=name)
-        blk["ya"] = f(B, filt[0], ho, wo); blk["yb"] = f(B, filt[1], ho, wo); blk["yc"] = f(B, filt[2], ho, wo)
-        if blk["down"]:
-          blk["ys"] = f(B, filt[2], ho, wo)
-        blk["out"] = f(B, filt[2], ho, wo)
-        # gradients
-        blk["gpre"] = f(B, filt[2], ho, wo); blk["gyc"] = f(B, filt[2], ho, wo)
-        blk["gab"] = f(B, filt[1], ho, wo); blk["gyb"] = f(B, filt[1], ho, wo)
-        blk["gaa"] = f(B, filt[0], ho, wo); blk["gya"] = f(B, filt[0], ho, wo)
-        if blk["down"]:
-          blk["gys"] = f(B, filt[2], ho, wo)
-          blk["gin"] = f(B, cin, hi, wi)
-          if st == 2:
-            # the stride-2 1x1 convs (op_a and the shortcut, resnet50.py:94-97) read a compacted copy of the
-            # sub-sampled block input, and their data gradients meet in a compact buffer before they are
-            # scattered back: plain tensors -> the pointwise kernel instead of strided views
-            blk["xs"] = f(B, cin, ho, wo); blk["gxs"] = f(B, cin, ho, wo)
-        if st == 2 and self.blocks:
-          self.blocks[-1]["xs_next"] = blk          # the block in front writes this block's compacted input with its tail
+        z = lambda c: f(B, c, ho, wo)
+        s2 = st == 2
+        blk = EncBlock(prefix=f"encoder.{name}.{bl}.", stage=name, cin=cin, f=filt, stride=st, h=ho, w=wo, down=(bl == "a"),
+                       final=(bl == blocks[-1]), ya=z(filt[0]), yb=z(filt[1]), yc=z(filt[2]), ys=z(filt[2]) if bl == "a" else None,
+                       out=z(filt[2]), gpre=z(filt[2]), gyc=z(filt[2]), gab=z(filt[1]), gyb=z(filt[1]), gaa=z(filt[0]), gya=z(filt[0]),
+                       gys=z(filt[2]) if bl == "a" else None, gin=f(B, cin, hi, wi) if bl == "a" else None,
+                       xs=z(cin) if s2 else None, gxs=z(cin) if s2 else None)
+        if s2 and self.blocks:
+          self.blocks[-1].xs_next = blk
         self.blocks.append(blk)
         cin, hi, wi = filt[2], ho, wo
       stage_hw[name] = (hi, wi)
@@ -724,14 +757,11 @@ class Plan:
     # decoder: concat buffers U_k (input of stage k), mid tensors W_k
     C = eng.num_classes
     sk = eng.skip_ch
-    self.dec = {2: dict(cin=256, cmid=256, cout=128, r=4), 3: dict(cin=128 + sk[2], cmid=128, cout=64, r=8),
-                4: dict(cin=64 + sk[3], cmid=64, cout=32, r=16), 5: dict(cin=32 + sk[4], cmid=32, cout=16, r=32),
-                6: dict(cin=16 + sk[5], cmid=16, cout=C, r=64)}
-    for k, d in self.dec.items():
-      r = d["r"]
-      d["u"] = f(B, d["cin"], r, r, r); d["gu"] = f(B, d["cin"], r, r, r)
-      d["w"] = f(B, d["cmid"], r, r, r); d["gw"] = f(B, d["cmid"], r, r, r)
-      d["gv1"] = f(B, d["cin"], r, r, r); d["gv2"] = f(B, d["cmid"], r, r, r)
+    self.dec = {}
+    for k, (ci, cm, co, r) in {2: (256, 256, 128, 4), 3: (128 + sk[2], 128, 64, 8), 4: (64 + sk[3], 64, 32, 16),
+                               5: (32 + sk[4], 32, 16, 32), 6: (16 + sk[5], 16, C, 64)}.items():
+      self.dec[k] = DecStage(ci, cm, co, r, u=f(B, ci, r, r, r), gu=f(B, ci, r, r, r), w=f(B, cm, r, r, r), gw=f(B, cm, r, r, r),
+                             gv1=f(B, ci, r, r, r), gv2=f(B, cm, r, r, r))
     self.logits = f(B, C, 128, 128, 128)
     self.glogits = f(B, C, 128, 128, 128)
     self.skip_src = {2: "stage5", 3: "stage4", 4: "stage3", 5: "stage2"}
@@ -741,7 +771,7 @@ class Plan:
     self.smap = {k: f(B, self.skip_hw[k][0], self.skip_hw[k][1], sk[k]) for k in sk}
     # the saved index tensors of the ray-sample backward (autograd keeps them in the reference: ray_traced_skip_connection.py:
     # 118-135): one uint16 per voxel of the 8^3 ... 64^3 skip grids, written by the training-mode gather, read by the scatter
-    self.ray_idx = ({k: t.zeros(B, (2 * self.dec[k]["r"]) ** 3, dtype=t.int16, device=dev) for k in sk}
+    self.ray_idx = ({k: t.zeros(B, (2 * self.dec[k].r) ** 3, dtype=t.int16, device=dev) for k in sk}
                     if hasattr(self.be, "ray_sample_fwd_idx") and max(h * w for h, w in self.skip_hw.values()) < 65535 else None)
     gs_n = {k: B * sk[k] * self.skip_hw[k][0] * self.skip_hw[k][1] for k in sk}
     self.gsmap_slab = f(sum(gs_n.values()))
@@ -749,8 +779,8 @@ class Plan:
     for k in sk:
       self.gsmap[k] = self.gsmap_slab[o:o + gs_n[k]].view(B, sk[k], *self.skip_hw[k]); o += gs_n[k]
     self.layer_mats = f(4, B, 16)
-    self._layer_scale_list = [128.0 / (2 * self.dec[k]["r"]) for k in (2, 3, 4, 5)]
-    self.layer_scales = t.tensor([[128.0 / (2 * self.dec[k]["r"])] * 3 + [1.0] for k in (2, 3, 4, 5)],
+    self._layer_scale_list = [128.0 / (2 * self.dec[k].r) for k in (2, 3, 4, 5)]
+    self.layer_scales = t.tensor([[128.0 / (2 * self.dec[k].r)] * 3 + [1.0] for k in (2, 3, 4, 5)],
                                  dtype=eng.dtype, device=dev).reshape(4, 1, 1, 4)
     self.offset = f(B, 3)
     self.loss = f(1)
@@ -800,9 +830,6 @@ class Plan:
   def flat(self, x: t.Tensor) -> V.View:
     return self._cached(("flat", x.data_ptr(), tuple(x.shape)), lambda: V.flat_channel_view(self.vw(x)))
 
-  def strided(self, x: t.Tensor, step) -> V.View:
-    return self._cached(("str", x.data_ptr(), tuple(x.shape), step), lambda: V.strided_view(self.vw(x), step))
-
   # ------------------------------------------------------------------ helpers
   probes = None     # bench.py: {name: [(start_event, end_event), ...]} around selected launches
 
@@ -810,18 +837,46 @@ class Plan:
     if self.probes is None or name not in self.probes:
       return fn()
     a, b = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
-    a.record(); fn(); b.record()
+    a.record(); r = fn(); b.record()
     self.probes[name].append((a, b))
+    return r
+
+  @property
+  def overlap(self) -> bool:
+    """Does this plan hand work to the side stream?  Not on the CPU emulator (no side stream) and not while tools/layer_times.py times
+    every launch (trace).  THE test of everything that has a side-stream and an in-line form."""
+    return self.side is not None and self.trace is None
+
+  def _on_side(self, after=None):
+    """with self._on_side(after=ev): the block runs on the side stream, behind `ev` when one is given."""
+    return on_stream(self.side, after)
+
+  def _next_handover_event(self):
+    """The next event of the backward pass's hand-over pool, recorded on the current stream (_join_side gives the pool back)."""
+    if self._side_i == len(self._side_ev):
+      self._side_ev.append(t.cuda.Event())
+    ev = self._side_ev[self._side_i]; self._side_i += 1
+    ev.record()
+    return ev
 
   def _stats(self, bn: BN, x: t.Tensor, S: int, sB: int, pre_relu: bool, training: bool):
     if not training:
       return            # eval mode: forward_encoder filled every scale / shift already (Engine.bn_eval_affine)
     with _lib.roctx_range("bn_stats C%d S%d" % (bn.C, S)):
-      self._bn_stats(bn, x, S, sB, pre_relu, training)
+      self.be.bn_stats(x, self.B, bn.C, S, sB, pre_relu, bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.nbt,
+                       BN_EPS, BN_MOMENTUM, True, bn.scale, bn.shift, bn.saved)
 
-  def _bn_stats(self, bn: BN, x: t.Tensor, S: int, sB: int, pre_relu: bool, training: bool):
-    self.be.bn_stats(x, self.B, bn.C, S, sB, pre_relu, bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.nbt,
-                     BN_EPS, BN_MOMENTUM, training, bn.scale, bn.shift, bn.saved)
+  def _bn_finalize(self, b: BN, parts: int, count: int):
+    """Second half of _stats from the partial sums the producing conv launch left (stem_conv_fwd / conv_fwd_stats)."""
+    self.be.bn_finalize(parts, b.C, count, b.gamma, b.beta, b.rmean, b.rvar, b.nbt, BN_EPS, BN_MOMENTUM, b.scale, b.shift, b.saved)
+
+  def _bn_bwd(self, b: BN, x: t.Tensor, dy: t.Tensor, dx: t.Tensor, S: int, pre_relu: bool, post_relu: bool, bias_of: Optional[Conv] = None):
+    """Backward of BatchRenorm `b` over dense [B][b.C][S] tensors: input x, output gradient dy -> input gradient dx, dgamma, dbeta.
+    bias_of: the conv that produced x -- its bias gradient is sum(dx), which the same launch leaves (dsum) instead of a second
+    pass over dx."""
+    n = b.C * S
+    self.be.bn_bwd(x, n, dy, n, self.B, b.C, S, pre_relu, post_relu, b.gamma, b.scale, b.shift, b.saved, dx, n, b.dgamma, b.dbeta,
+                   dsum=None if bias_of is None else bias_of.dbias, ndsum=0 if bias_of is None else bias_of.n_ref)
 
   trace = None      # tools/layer_times.py: list of (label, start_event, end_event) for every conv launch
 
@@ -832,8 +887,9 @@ class Plan:
     if self.trace is None:
       return fn()
     a, b = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
-    a.record(); fn(); b.record()
+    a.record(); r = fn(); b.record()
     self.trace.append((label, a, b))
+    return r
 
   def _math(self, cv: Conv, direction: str) -> str:
     if cv.wop_kind == "e2d" and (direction == "fwd" and cv.wop_f is not None or
@@ -841,7 +897,7 @@ class Plan:
       return "e2d"
     return "bf16x3" if self.eng.decoder_math == "bf16x3" and (cv.name, direction) in BF16X3_LAUNCHES else "fp32"
 
-  conv_positions = None     # tools/layer_times.py: {layer name: logical output positions per sample} when tracing
+  conv_positions = None     # tools/layer_times.py: {layer name: logical output positions per sample}, filled while it traces
 
   @staticmethod
   def _e2d_shape_ok(v: V.View, window) -> bool:
@@ -863,7 +919,7 @@ class Plan:
 
   def _conv(self, cv: Conv, x: V.View, tr, y: V.View, accumulate=False):
     g = cv.fwd
-    if self.trace is not None and self.conv_positions is not None:
+    if self.conv_positions is not None:
       self.conv_positions[cv.name] = y.D * y.H * y.W
     if cv.wop_f is not None and cv.wop_kind == "e2d" and self._e2d_shape_ok(y, g.window):
       self._timed("fwd   " + cv.name, lambda: self.be.conv2d_bf3(
@@ -887,7 +943,7 @@ class Plan:
     """Data gradient g of decoder conv `cv` + backward of the BatchRenorm `b` in front of it (input x, output gradient g,
     input gradient dx; dsum = the bias gradient of the conv `cprev` that produced x).  True: the norm's backward is done
     (its sums came out of the conv launch, crn_conv_fwd_bf3_slabs_bnbwd); False: g is written, the caller runs bn_bwd."""
-    eng, be = self.eng, self.be
+    be = self.be
     gvw = self.vw(g)
     fusable = (hasattr(be, "conv_dgrad_bn_bwd") and cv.wop_kind == "slab" and cv.wop_d is not None
                and self._math(cv, "dgrad") == "bf16x3")
@@ -896,19 +952,13 @@ class Plan:
       self._dgrad(cv, dy, gvw)
       return False
     gd = cv.dgrad
-    done = [False]
     be.splitk_defer()                            # (a launch that splits cannot fuse: its sum goes to the norm's own first pass)
-    def run():
-      done[0] = be.conv_dgrad_bn_bwd(dy, cv.wop_d, gd.npad, gvw, g, gd.window, gd.pad_lo, (gd.n_boxes, gd.c_boxes),
-                                     x, Cn * S, self.B, Cn, S, True, b.gamma, b.scale, b.shift, b.saved, dx, Cn * S,
-                                     b.dgamma, b.dbeta, dsum=cprev.dbias, ndsum=cprev.n_ref)
-    self._timed("dgrad " + cv.name, run)
-    return done[0]
+    return self._timed("dgrad " + cv.name, lambda: be.conv_dgrad_bn_bwd(
+        dy, cv.wop_d, gd.npad, gvw, g, gd.window, gd.pad_lo, (gd.n_boxes, gd.c_boxes), x, Cn * S, self.B, Cn, S, True, b.gamma,
+        b.scale, b.shift, b.saved, dx, Cn * S, b.dgamma, b.dbeta, dsum=cprev.dbias, ndsum=cprev.n_ref))
 
-  def _wgrad(self, cv: Conv, x: V.View, tr, dy: V.View):
-    """Weight gradient of one conv.  On the GPU it goes to a second HIP stream: it only reads
-    (saved activation, dy) and writes its own slice of the packed gradient slab, so it can run
-    beside the data-gradient chain; most layers below 32^3 / 64^2 cannot fill 256 CUs alone."""
+  def _wgrad_math(self, cv: Conv, dy: V.View) -> str:
+    """The engine of one weight gradient (backend.conv_wgrad's `math`)."""
     g = cv.fwd
     math = self._math(cv, "wgrad")
     if self.stem_fast and cv.name == "encoder.stage1.conv.":
@@ -919,37 +969,45 @@ class Plan:
       math = "bf16x3_2d"          # both operands straight from HBM, K = positions (csrc/conv_e2d.hip)
     if cv.ct_kind == "par" and math == "bf16x3":
       math = "ct_par"             # the logits layer with > 8 classes: parity-walk kernel (csrc/convt_par.hip; generic engine in deterministic mode)
-    if self.side is None or self.trace is not None:
-      self._timed("wgrad " + cv.name, lambda: self.be.conv_wgrad(
-          x, tr, dy, cv.gwf, g.npad, g.window, g.pad_lo, False, boxes=(g.n_boxes, g.c_boxes), math=math, **self._ximg_kw(math)))
-      return
+    return math
+
+  def _launch_wgrad(self, cv: Conv, x: V.View, tr, dy: V.View, math: str, kw: dict):
+    """THE weight-gradient launch, on the current stream: into the layer's slice of the packed gradient slab."""
+    g = cv.fwd
+    with _lib.roctx_range("wgrad " + cv.name):
+      self.be.conv_wgrad(x, tr, dy, cv.gwf, g.npad, g.window, g.pad_lo, False, boxes=(g.n_boxes, g.c_boxes), math=math, **kw)
+
+  def _wgrad(self, cv: Conv, x: V.View, tr, dy: V.View, here: bool = False):
+    """Weight gradient of one conv.  On the GPU it goes to a second HIP stream: it only reads
+    (saved activation, dy) and writes its own slice of the packed gradient slab, so it can run
+    beside the data-gradient chain; most layers below 32^3 / 64^2 cannot fill 256 CUs alone.
+    here: the caller is on the side stream already (the skip path): launch in place."""
+    math = self._wgrad_math(cv, dy)
+    kw = self._ximg_kw(math)
+    if here:
+      return self._launch_wgrad(cv, x, tr, dy, math, kw)
+    if not self.overlap:
+      return self._timed("wgrad " + cv.name, lambda: self._launch_wgrad(cv, x, tr, dy, math, kw))
     if cv.name.startswith("encoder."):
       # the encoder's small weight gradients are handed to the side stream one bottleneck at a time (_flush_wgrads): ONE event on
       # the data-gradient chain per block instead of one per convolution
-      self._wg_pending.append((cv, x, tr, dy, math, self._ximg_kw(math)))
+      self._wg_pending.append((cv, x, tr, dy, math, kw))
       return
     if self._handed_over:
       # the side stream already waits for an event recorded after dy became final (the skip path's hand-over, just before this
       # call, with nothing launched on the main stream in between): no second marker on the data-gradient chain
       self._handed_over = False
       self._side_i = max(self._side_i, 1)
-      with t.cuda.stream(self.side), _lib.pinned_stream(self.side), _lib.roctx_range("wgrad " + cv.name):
-        self.be.conv_wgrad(x, tr, dy, cv.gwf, g.npad, g.window, g.pad_lo, False, boxes=(g.n_boxes, g.c_boxes), math=math,
-                           **self._ximg_kw(math))
-      return
-    if self._side_i == len(self._side_ev):
-      self._side_ev.append(t.cuda.Event())
-    ev = self._side_ev[self._side_i]; self._side_i += 1
-    ev.record()                                   # dy (and the zeroed slab) are ready on the main stream
-    with t.cuda.stream(self.side), _lib.pinned_stream(self.side), _lib.roctx_range("wgrad " + cv.name):
-      self.side.wait_event(ev)
-      self.be.conv_wgrad(x, tr, dy, cv.gwf, g.npad, g.window, g.pad_lo, False, boxes=(g.n_boxes, g.c_boxes), math=math,
-                         **self._ximg_kw(math))
+      ev = None
+    else:
+      ev = self._next_handover_event()            # dy (and the zeroed slab) are ready on the main stream
+    with self._on_side(after=ev):
+      self._launch_wgrad(cv, x, tr, dy, math, kw)
 
   def _ximg_kw(self, math: str) -> dict:
     """The operand image the forward pass left for the parity-walk weight gradient (forward_decoder), consumed once."""
     if math != "ct_par" or self._ct_ximg is None:
-      return {}
+      return _NO_KW
     img, self._ct_ximg = self._ct_ximg, None
     return {"ximg": img}
 
@@ -958,16 +1016,9 @@ class Plan:
     `then` (a gradient bucket's un-pack + hook) runs behind them in the same hand-over."""
     if not self._wg_pending and then is None:
       return
-    if self._side_i == len(self._side_ev):
-      self._side_ev.append(t.cuda.Event())
-    ev = self._side_ev[self._side_i]; self._side_i += 1
-    ev.record()
-    with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
-      self.side.wait_event(ev)
-      for cv, x, tr, dy, math, kw in self._wg_pending:
-        g = cv.fwd
-        with _lib.roctx_range("wgrad " + cv.name):
-          self.be.conv_wgrad(x, tr, dy, cv.gwf, g.npad, g.window, g.pad_lo, False, boxes=(g.n_boxes, g.c_boxes), math=math, **kw)
+    with self._on_side(after=self._next_handover_event()):
+      for args in self._wg_pending:
+        self._launch_wgrad(*args)
       if then is not None:
         then()
     self._wg_pending = []
@@ -975,7 +1026,7 @@ class Plan:
   def _join_side(self):
     """Main stream waits for every weight gradient issued on the side stream."""
     self._flush_wgrads()
-    if self.side is not None and self._side_i:
+    if self._side_i:
       self._side_done.record(self.side)
       t.cuda.current_stream().wait_event(self._side_done)
       self._side_i = 0
@@ -985,7 +1036,7 @@ class Plan:
 
   # ------------------------------------------------------------------ forward
   def forward(self, image_u8: t.Tensor, v2s: t.Tensor, offset: t.Tensor, training: bool) -> t.Tensor:
-    self._skip_async_live = bool(training and self.side is not None and self.trace is None)
+    self._skip_async_live = bool(training and self.overlap)
     if self._skip_async_live:
       self._decoder_inputs(v2s, offset)            # the skip path starts inside the encoder: it needs them now
     self.forward_encoder(image_u8, training)
@@ -1010,28 +1061,27 @@ class Plan:
     straight into the skip channels of the stage's concat buffer."""
     eng, be, B = self.eng, self.be, self.B
     d = self.dec[k]
-    out = self.dec[k + 1]["u"]
+    out = self.dec[k + 1].u
     ft = self.feat[self.skip_src[k]]
-    (hh, ww), ro = self.skip_hw[k], 2 * d["r"]
+    (hh, ww), ro = self.skip_hw[k], 2 * d.r
     be.fill_offset_channels(ft, B, ft.stride(0), ft.shape[2] * ft.shape[3], ft.shape[1] - 3, self.offset)
     self._conv(eng.convs[f"decoder.rt_skip_{k}.compress_channels."], self.vw(ft), None,
                self.vw(self.smap[k].permute(0, 3, 1, 2)))
     if self.ray_idx is not None and self.training:
       self._probe(f"ray_sample_fwd_{ro}", lambda: be.ray_sample_fwd_idx(
           self.smap[k], self.smap[k].stride(0), B, eng.skip_ch[k], hh, ww, self.layer_mats[k - 2],
-          self.offset, out[:, d["cout"]:], out.stride(0), ro, ro, ro, self.ray_idx[k], map_sC=1, map_sP=eng.skip_ch[k]))
+          self.offset, out[:, d.cout:], out.stride(0), ro, ro, ro, self.ray_idx[k], map_sC=1, map_sP=eng.skip_ch[k]))
     else:
       self._probe(f"ray_sample_fwd_{ro}", lambda: be.ray_sample_fwd(
           self.smap[k], self.smap[k].stride(0), B, eng.skip_ch[k], hh, ww, self.layer_mats[k - 2],
-          self.offset, out[:, d["cout"]:], out.stride(0), ro, ro, ro, map_sC=1, map_sP=eng.skip_ch[k]))
+          self.offset, out[:, d.cout:], out.stride(0), ro, ro, ro, map_sC=1, map_sP=eng.skip_ch[k]))
 
   def _skip_fwd_async(self, stage: str):
     """The stage's pre-ReLU feature map is final on the main stream: its skip path goes to the side stream."""
     k = {v: kk for kk, v in self.skip_src.items()}[stage]
     ready, done = self._skip_ev[k]
     ready.record()
-    with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
-      self.side.wait_event(ready)
+    with self._on_side(after=ready):
       self._skip_fwd(k)
       done.record(self.side)
 
@@ -1044,7 +1094,7 @@ class Plan:
     self.generation += 1
     # (_dgrad_pack_pending / _gpacked_zeroed stay set until a backward consumes them: a second forward before
     # the backward must not forget that the side stream still owes it the data-gradient weights)
-    if training and self.side is not None and (eng.dgrad_dirty or eng.weights_dirty):
+    if training and self.side is not None and (eng.dgrad_dirty or eng.weights_dirty):     # (also while tracing: no timed layer in it)
       # work that nothing on the main stream needs yet goes to the side stream, under the encoder: the decoder's
       # forward weights (needed ~1.4 ms later), the data-gradient weights and the zeroing of the packed gradient
       # slab (needed by backward)
@@ -1052,8 +1102,7 @@ class Plan:
       if dec_later:
         eng.pack_weights("enc_early")             # stem + stage2 (0.2 M weights): needed at once
       eng._pack_ev.record()                      # the parameters are final on the main stream
-      with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
-        self.side.wait_event(eng._pack_ev)
+      with self._on_side(after=eng._pack_ev):
         if dec_later:
           eng.pack_weights("enc_late")            # stage3-5 (23 M): needed ~0.5 ms into the encoder
           eng._enc_late_packed.record(self.side)
@@ -1080,27 +1129,23 @@ class Plan:
     H1, W1 = self.stem_hw
     if self.stem_fast:
       # the stem on its own kernel (csrc/stem_conv.hip); in training the partial sums of its norm come out of the same launch
-      parts = [0]
-      if self.trace is not None and self.conv_positions is not None:
+      if self.conv_positions is not None:
         self.conv_positions[c1.name] = H1 * W1
-      def stem():
-        parts[0] = be.stem_conv_fwd(self.img, c1.wf, c1.bias, self.y1, training)
-      self._timed("fwd   " + c1.name, stem)
+      parts = self._timed("fwd   " + c1.name, lambda: be.stem_conv_fwd(self.img, c1.wf, c1.bias, self.y1, training))
       if training:
-        be.bn_finalize(parts[0], 64, B * H1 * W1, b1.gamma, b1.beta, b1.rmean, b1.rvar, b1.nbt, BN_EPS, BN_MOMENTUM,
-                       b1.scale, b1.shift, b1.saved)
+        self._bn_finalize(b1, parts, B * H1 * W1)
     else:
       self._conv(c1, self.s2d(self.img, 3, (1, 2, 2)), None, self.vw(self.y1))
       self._stats(b1, self.y1, H1 * W1, 64 * H1 * W1, False, training)
     be.maxpool_fwd(self.y1, b1.scale, b1.shift, B, 64, H1, W1, self.p1, self.p1_arg)
     cur = self.p1
     for blk in self.blocks:
-      if eng._enc_late_pending and blk["stage"] != "stage2":
+      if eng._enc_late_pending and blk.stage != "stage2":
         t.cuda.current_stream().wait_event(eng._enc_late_packed)
         eng._enc_late_pending = False
       cur = self._block_fwd(blk, cur, training)
-      if blk["final"] and self._skip_async_live:
-        self._skip_fwd_async(blk["stage"])
+      if blk.final and self._skip_async_live:
+        self._skip_fwd_async(blk.stage)
     f5 = self.feat["stage5"]
     S5 = f5.shape[2] * f5.shape[3]
     be.relu_mean_fwd(f5, B, 2048, S5, f5.stride(0), self.avg)
@@ -1113,90 +1158,82 @@ class Plan:
     if eng._dec_pack_pending:
       t.cuda.current_stream().wait_event(eng._dec_packed)
       eng._dec_pack_pending = False
-    skip_async = self._skip_async_live
+    skip_async = self._skip_async_live           # (forward(): the skip paths already run on the side stream)
     if not skip_async:
       self._decoder_inputs(v2s, offset)
     # decoder (reconstruction_decoder.py:136-151)
     L = eng.latent
     s = eng.store
-    be.linear_fwd(self.avg, s.view("decoder.stage_0.weight"), s.view("decoder.stage_0.bias"),
-                  B, 2048, L, self.z0, L + 3)
+    be.linear_fwd(self.avg, s.view("decoder.stage_0.weight"), s.view("decoder.stage_0.bias"), B, 2048, L, self.z0, L + 3)
     be.fill_offset_channels(self.z0, B, L + 3, 1, L, self.offset)
     b = bn["decoder.stage_1.b1."]
     self._stats(b, self.z0, 1, L + 3, True, training)
     zv = self.vw(self.z0.view(B, L + 3, 1, 1, 1))
-    u2 = self.dec[2]["u"]
-    self._conv(cv["decoder.stage_1.t1."], zv, Transform(b.scale, b.shift, pre_relu=True),
-               self.flat(u2))
+    self._conv(cv["decoder.stage_1.t1."], zv, Transform(b.scale, b.shift, pre_relu=True), self.flat(self.dec[2].u))
     for k in range(2, 7):
       d = self.dec[k]
-      r, S = d["r"], d["r"] ** 3
+      S = d.r ** 3
       p = f"decoder.stage_{k}."
       b1_, b2_ = bn[p + "b1."], bn[p + "b2."]
+      tr1, tr2 = Transform(b1_.scale, b1_.shift, pre_relu=True), Transform(b2_.scale, b2_.shift, pre_relu=True)
       if skip_async and k == 3:
         # the skip paths run on the side stream in the order of the encoder's stages (64^3 first, 8^3 last): the event behind the
         # LAST one -- the 8^3 skip into this stage -- covers all four; one marker on the decoder's chain instead of four
         t.cuda.current_stream().wait_event(self._skip_ev[2][1])
-      self._stats(b1_, d["u"], S, d["cin"] * S, True, training)
+      self._stats(b1_, d.u, S, d.cin * S, True, training)
       if training:
         be.splitk_defer()                      # (stages 2-4 split K: the statistics below add the partial sums up)
       cc = cv[p + "c1."]
-      parts = [0]
       if (training and self.dec_stats_fused and cc.wop_kind == "slab" and cc.wop_f is not None and self._math(cc, "fwd") == "bf16x3"
           and self.trace is None):
         # the partial sums of the norm behind c1 come out of c1's launch where it does not split its reduction (stages 5-6 at the
         # bench batch): crn_conv_fwd_bf3_slabs_stats + crn_batch_renorm_finalize instead of a statistics pass over w
         gq = cc.fwd
-        def c1_stats():
-          parts[0] = be.conv_fwd_stats(self.vw(d["u"]), Transform(b1_.scale, b1_.shift, pre_relu=True), cc.wop_f, gq.npad, cc.bias, 0,
-                                       self.vw(d["w"]), gq.window, gq.pad_lo, (gq.n_boxes, gq.c_boxes), d["cmid"], True)
-        self._probe(f"conv3d_stage{k}_c1_fwd", lambda: self._timed("fwd   " + cc.name, c1_stats))
+        parts = self._probe(f"conv3d_stage{k}_c1_fwd", lambda: self._timed("fwd   " + cc.name, lambda: be.conv_fwd_stats(
+            self.vw(d.u), tr1, cc.wop_f, gq.npad, cc.bias, 0, self.vw(d.w), gq.window, gq.pad_lo, (gq.n_boxes, gq.c_boxes), d.cmid, True)))
       else:
-        self._probe(f"conv3d_stage{k}_c1_fwd", lambda: self._conv(
-            cc, self.vw(d["u"]), Transform(b1_.scale, b1_.shift, pre_relu=True), self.vw(d["w"])))
-      if parts[0] > 0:
-        be.bn_finalize(parts[0], d["cmid"], B * S, b2_.gamma, b2_.beta, b2_.rmean, b2_.rvar, b2_.nbt, BN_EPS, BN_MOMENTUM,
-                       b2_.scale, b2_.shift, b2_.saved)
+        parts = 0
+        self._probe(f"conv3d_stage{k}_c1_fwd", lambda: self._conv(cc, self.vw(d.u), tr1, self.vw(d.w)))
+      if parts > 0:
+        self._bn_finalize(b2_, parts, B * S)
       else:
-        self._stats(b2_, d["w"], S, d["cmid"] * S, True, training)
-      out = self.dec[k + 1]["u"] if k < 6 else self.logits
+        self._stats(b2_, d.w, S, d.cmid * S, True, training)
+      out = self.dec[k + 1].u if k < 6 else self.logits
       ct = cv[p + "t1."]
       self._ct_ximg = None
-      if (training and ct.ct_kind == "par" and self.side is not None and self.trace is None and hasattr(be, "convt_ximage")
-          and self._math(ct, "wgrad") == "bf16x3"):
+      if training and self.overlap and ct.ct_kind == "par" and hasattr(be, "convt_ximage") and self._math(ct, "wgrad") == "bf16x3":
         # the parity-walk weight gradient of the logits layer reads T(w) as an operand image (crn_convt_s2k7_ximage): made here on the
         # side stream, which is idle under the decoder's forward pass -- the norm's scale / shift are final, backward finds it ready
         self._ximg_ev.record()
-        with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
-          self.side.wait_event(self._ximg_ev)
-          self._ct_ximg_buf = be.convt_ximage(d["w"], Transform(b2_.scale, b2_.shift, pre_relu=True), self._ct_ximg_buf)   # (this plan's own buffer)
-          self._ct_ximg = self._ct_ximg_buf
+        with self._on_side(after=self._ximg_ev):
+          self._ct_ximg = self._ct_ximg_buf = be.convt_ximage(d.w, tr2, self._ct_ximg_buf)   # (this plan's own buffer)
       if ct.ct_f is not None and self._math(ct, "fwd") == "bf16x3":
         # the logits layer with > 8 classes: parity-walk kernel (csrc/convt_par.hip)
-        if self.trace is not None and self.conv_positions is not None:
+        if self.conv_positions is not None:
           self.conv_positions[ct.name] = S
         self._probe(f"conv3d_stage{k}_t1_fwd", lambda: self._timed("fwd   " + ct.name, lambda: be.convt_par_fwd(
-            d["w"], Transform(b2_.scale, b2_.shift, pre_relu=True), ct.ct_f, ct.bias, out, d["cout"],
-            host_table=eng.ct_tables["dec"][2], resident=ct.ct_kind == "res")))
+            d.w, tr2, ct.ct_f, ct.bias, out, d.cout, resident=ct.ct_kind == "res")))
       else:
-        ov = self.s2d(out, d["cout"], (2, 2, 2))
-        self._probe(f"conv3d_stage{k}_t1_fwd", lambda: self._conv(ct, self.vw(d["w"]), Transform(b2_.scale, b2_.shift, pre_relu=True), ov))
+        ov = self.s2d(out, d.cout, (2, 2, 2))
+        self._probe(f"conv3d_stage{k}_t1_fwd", lambda: self._conv(ct, self.vw(d.w), tr2, ov))
       if k < 6 and not skip_async:
         self._skip_fwd(k)
     if training:
       be.add_i64(eng.store.nbt, eng.store.nbt.numel(), 1)     # batch_renorm.py:57
     return self.logits
 
-  def _block_fwd(self, blk, cur: t.Tensor, training: bool) -> t.Tensor:
+  def _block_fwd(self, blk: EncBlock, cur: t.Tensor, training: bool) -> t.Tensor:
     eng, be, B = self.eng, self.be, self.B
     cv, bn = eng.convs, eng.bns
-    p = blk["prefix"]
-    h = blk["h"]; S = h * blk["w"]
-    f1, f2, f3 = blk["f"]
-    if blk["stride"] == 2:
-      if not blk.pop("xs_filled", False):            # (filled by the tail launch of the block in front: crn_batch_renorm_stats_tail)
-        be.stride2_gather(cur, blk["xs"])
-      xin = self.vw(blk["xs"])
+    p = blk.prefix
+    S = blk.h * blk.w
+    f1, f2, f3 = blk.f
+    if blk.stride == 2:
+      if blk.xs_filled:                              # (by the tail launch of the block in front: crn_batch_renorm_stats_tail)
+        blk.xs_filled = False
+      else:
+        be.stride2_gather(cur, blk.xs)
+      xin = self.vw(blk.xs)
     else:
       xin = self.vw(cur)
     ba, bb, bc = bn[p + "op_a.bn."], bn[p + "op_b.bn."], bn[p + "op_c.bn."]
@@ -1204,14 +1241,13 @@ class Plan:
     # a split-K conv itself: crn_splitk_defer)
     defer = be.splitk_defer if training else (lambda: None)
     defer()
-    self._conv(cv[p + "op_a.conv."], xin, None, self.vw(blk["ya"]))
-    self._stats(ba, blk["ya"], S, f1 * S, False, training)
+    self._conv(cv[p + "op_a.conv."], xin, None, self.vw(blk.ya))
+    self._stats(ba, blk.ya, S, f1 * S, False, training)
     defer()
-    self._conv(cv[p + "op_b.conv."], self.vw(blk["ya"]), Transform(ba.scale, ba.shift, post_relu=True),
-               self.vw(blk["yb"]))
-    self._stats(bb, blk["yb"], S, f2 * S, False, training)
-    if blk["final"]:
-      pre, sB_pre = self.feat[blk["stage"]], self.feat[blk["stage"]].stride(0)
+    self._conv(cv[p + "op_b.conv."], self.vw(blk.ya), Transform(ba.scale, ba.shift, post_relu=True), self.vw(blk.yb))
+    self._stats(bb, blk.yb, S, f2 * S, False, training)
+    if blk.final:
+      pre, sB_pre = self.feat[blk.stage], self.feat[blk.stage].stride(0)
     else:
       pre, sB_pre = None, 0
     # training on the HIP backend: the statistics of op_c's norm and the block tail (norm + shortcut + ReLU) are one
@@ -1221,30 +1257,28 @@ class Plan:
     def shortcut():
       bs = bn[p + "shortcut.bn."]
       defer()
-      self._conv(cv[p + "shortcut.conv."], xin, None, self.vw(blk["ys"]))
-      self._stats(bs, blk["ys"], S, f3 * S, False, training)
-      return blk["ys"], bs.scale, bs.shift
-    if blk["down"] and fused_tail:
+      self._conv(cv[p + "shortcut.conv."], xin, None, self.vw(blk.ys))
+      self._stats(bs, blk.ys, S, f3 * S, False, training)
+      return blk.ys, bs.scale, bs.shift
+    if blk.down and fused_tail:
       res, rsc, rsh = shortcut()
     defer()
-    self._conv(cv[p + "op_c.conv."], self.vw(blk["yb"]), Transform(bb.scale, bb.shift, post_relu=True),
-               self.vw(blk["yc"]))
+    self._conv(cv[p + "op_c.conv."], self.vw(blk.yb), Transform(bb.scale, bb.shift, post_relu=True), self.vw(blk.yc))
     if fused_tail:
-      nxt = blk.get("xs_next")
+      nxt = blk.xs_next
       with _lib.roctx_range("bn_stats_tail C%d S%d" % (bc.C, S)):
-        be.bn_stats_tail(blk["yc"], B, f3, S, f3 * S, bc.gamma, bc.beta, bc.rmean, bc.rvar, bc.nbt, BN_EPS, BN_MOMENTUM,
-                         True, bc.scale, bc.shift, bc.saved, res, rsc, rsh, f3 * S, pre, sB_pre, blk["out"], f3 * S, True,
-                         y2=nxt["xs"] if nxt is not None else None, W=blk["w"])
+        be.bn_stats_tail(blk.yc, B, f3, S, f3 * S, bc.gamma, bc.beta, bc.rmean, bc.rvar, bc.nbt, BN_EPS, BN_MOMENTUM,
+                         True, bc.scale, bc.shift, bc.saved, res, rsc, rsh, f3 * S, pre, sB_pre, blk.out, f3 * S, True,
+                         y2=nxt.xs if nxt is not None else None, W=blk.w)
       if nxt is not None:
-        nxt["xs_filled"] = True
+        nxt.xs_filled = True
     else:
-      self._stats(bc, blk["yc"], S, f3 * S, False, training)
-      if blk["down"]:
+      self._stats(bc, blk.yc, S, f3 * S, False, training)
+      if blk.down:
         res, rsc, rsh = shortcut()
-      be.affine_add_relu(blk["yc"], bc.scale, bc.shift, res, rsc, rsh, B, f3, S,
-                         f3 * S, f3 * S, pre, sB_pre, blk["out"], f3 * S, True)
-    blk["in"] = cur
-    return blk["out"]
+      be.affine_add_relu(blk.yc, bc.scale, bc.shift, res, rsc, rsh, B, f3, S, f3 * S, f3 * S, pre, sB_pre, blk.out, f3 * S, True)
+    blk.inp = cur
+    return blk.out
 
   # ------------------------------------------------------------------ backward
   def _grads_ready(self, label: str, hook):
@@ -1262,7 +1296,7 @@ class Plan:
       if tiles[0].numel() or tiles[3].numel():
         self.be.copy_tiles(eng.gpacked, eng.store.grads, tiles, reverse=True)
       hook(eng.store.grads[lo:hi])
-    if self.side is None or self.trace is not None:
+    if not self.overlap:
       return run()
     return self._flush_wgrads(then=run)            # (its event also covers the bucket's bias / norm gradients on the main stream)
 
@@ -1280,27 +1314,26 @@ class Plan:
     if not eng._gpacked_zeroed:
       be.zero(eng.gpacked)
     eng._gpacked_zeroed = False
-    skips_on_side = self.side is not None and self.trace is None
-    if skips_on_side:
+    overlap = self.overlap
+    if overlap:
       # the four skip-map gradients are written and read on the side stream only (scatter -> compress gradients): zeroed there,
       # off the step's chain (a memset is a launch of its own)
-      with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
+      with self._on_side():
         be.zero(self.gsmap_slab)
+      if grad_hook is None:
+        grad_hook = _no_exchange                   # un-pack the finished buckets on the side stream all the same
     else:
       be.zero(self.gsmap_slab)                     # the four skip-map gradients: one launch instead of four memsets
-    if grad_hook is None and self.side is not None and self.trace is None:
-      grad_hook = _no_exchange                     # un-pack the finished buckets on the side stream all the same
     L = eng.latent
     g_out = glogits
     for k in range(6, 1, -1):
       d = self.dec[k]
-      r, S = d["r"], d["r"] ** 3
-      ro, So = 2 * r, (2 * r) ** 3
+      S, So = d.r ** 3, (2 * d.r) ** 3
       p = f"decoder.stage_{k}."
       b1_, b2_ = bn[p + "b1."], bn[p + "b2."]
       ctot = g_out.shape[1]
       if k < 6:    # ray-traced skip: scatter-add, compress conv grads
-        if skips_on_side:
+        if overlap:
           # off the data-gradient chain: the feature-map gradients are only needed when the encoder's backward starts.
           # The scatter goes with it (on the main stream it costs +0.07 ms per step).  Beside the split-bf16
           # convolutions of round 3 its sums differed from run to run by 1e-2 ... 1e-1 of the map's range: three dependent
@@ -1309,9 +1342,7 @@ class Plan:
           # MFMAs now (mfma3, csrc/conv_bf3.hip): beside them the scatter is exact in 82 of 82 steps and in 660 of 660
           # two-kernel runs; test_run_to_run_gradient_spread_default_mode watches it.  (Round 5: the scatter has no projection left.)
           self._skip_bwd_ev[k].record()             # (also the hand-over event of this stage's transposed-conv weight gradient below)
-          with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
-            self.side.wait_event(self._skip_bwd_ev[k])
-            self._ray_bwd(k, g_out)
+          with self._on_side(after=self._skip_bwd_ev[k]):
             self._skip_bwd(k, g_out, on_side=True)
             if k == 2:
               self._skip_bwd_done.record(self.side)
@@ -1319,16 +1350,16 @@ class Plan:
         else:
           self._skip_bwd(k, g_out, on_side=False)
       ct = cv[p + "t1."]
-      gv = self.s2d(g_out, d["cout"], (2, 2, 2))
+      gv = self.s2d(g_out, d.cout, (2, 2, 2))
       tr2 = Transform(b2_.scale, b2_.shift, pre_relu=True)
-      self._wgrad(ct, self.vw(d["w"]), tr2, gv)
+      self._wgrad(ct, self.vw(d.w), tr2, gv)
       self._handed_over = False
       if k == 6:   # gradient of the logits comes from the loss kernel; below it is a bn_bwd output
-        if self.side is not None and self.trace is None:
+        if overlap:
           # one pass over the loss gradient (470 MB at 14 classes) whose result is only read by the bucket's un-pack: it follows the
           # layer's weight gradient on the side stream (ordered behind the same hand-over event) instead of sitting in front of the
           # data-gradient chain
-          with t.cuda.stream(self.side), _lib.pinned_stream(self.side):
+          with self._on_side():
             self._bias_grad(ct, g_out, So, ctot * So)
         else:
           self._bias_grad(ct, g_out, So, ctot * So)
@@ -1339,23 +1370,18 @@ class Plan:
       # reduction (stages 5-6 at the bench batch) it also leaves that norm's two backward sums, and the norm's backward
       # is its second pass alone (_dgrad_bn_bwd)
       if ct.ct_d is not None and self._math(ct, "dgrad") == "bf16x3":
-        self._timed("dgrad " + ct.name, lambda: be.convt_par_dgrad(g_out, d["cout"], ct.ct_d, d["gv2"], False,
-                                                                     host_table=eng.ct_tables["bwd"][2], resident=ct.ct_kind == "res"))
+        self._timed("dgrad " + ct.name, lambda: be.convt_par_dgrad(g_out, d.cout, ct.ct_d, d.gv2, False, resident=ct.ct_kind == "res"))
         ct_done = False
       else:
-        ct_done = self._dgrad_bn_bwd(ct, gv, d["gv2"], d["w"], d["cmid"], S, b2_, d["gw"], cc)
+        ct_done = self._dgrad_bn_bwd(ct, gv, d.gv2, d.w, d.cmid, S, b2_, d.gw, cc)
       if not ct_done:
-        be.bn_bwd(d["w"], d["cmid"] * S, d["gv2"], d["cmid"] * S, B, d["cmid"], S, True, False,
-                  b2_.gamma, b2_.scale, b2_.shift, b2_.saved, d["gw"], d["cmid"] * S, b2_.dgamma, b2_.dbeta,
-                  dsum=cc.dbias, ndsum=cc.n_ref)
+        self._bn_bwd(b2_, d.w, d.gv2, d.gw, S, True, False, bias_of=cc)
       tr1 = Transform(b1_.scale, b1_.shift, pre_relu=True)
-      self._wgrad(cc, self.vw(d["u"]), tr1, self.vw(d["gw"]))
+      self._wgrad(cc, self.vw(d.u), tr1, self.vw(d.gw))
       cprev = cv[f"decoder.stage_{k - 1}.t1."]        # produced this stage's input (first n_ref channels)
-      if not self._dgrad_bn_bwd(cc, self.vw(d["gw"]), d["gv1"], d["u"], d["cin"], S, b1_, d["gu"], cprev):
-        be.bn_bwd(d["u"], d["cin"] * S, d["gv1"], d["cin"] * S, B, d["cin"], S, True, False,
-                  b1_.gamma, b1_.scale, b1_.shift, b1_.saved, d["gu"], d["cin"] * S, b1_.dgamma, b1_.dbeta,
-                  dsum=cprev.dbias, ndsum=cprev.n_ref)
-      g_out = d["gu"]
+      if not self._dgrad_bn_bwd(cc, self.vw(d.gw), d.gv1, d.u, d.cin, S, b1_, d.gu, cprev):
+        self._bn_bwd(b1_, d.u, d.gv1, d.gu, S, True, False, bias_of=cprev)
+      g_out = d.gu
       if k == 3:
         self._grads_ready("decoder.stage_3.", grad_hook)
     # stage_1 / stage_0
@@ -1365,84 +1391,68 @@ class Plan:
     gv = self.flat(g_out)
     self._wgrad(c1, zv, Transform(b.scale, b.shift, pre_relu=True), gv)
     self._dgrad(c1, gv, self.vw(self.gv0.view(B, L + 3, 1, 1, 1)))
-    be.bn_bwd(self.z0, L + 3, self.gv0, L + 3, B, L + 3, 1, True, False, b.gamma, b.scale, b.shift,
-              b.saved, self.gz0, L + 3, b.dgamma, b.dbeta)
+    self._bn_bwd(b, self.z0, self.gv0, self.gz0, 1, True, False)
     s = eng.store
     be.linear_bwd(self.avg, s.view("decoder.stage_0.weight"), self.gz0, L + 3, B, 2048, L, self.gavg,
                   s.view("decoder.stage_0.weight", grad=True), s.view("decoder.stage_0.bias", grad=True))
     self._grads_ready("decoder.stage_0.", grad_hook)
     # encoder
-    if skips_on_side:
+    if overlap:
       t.cuda.current_stream().wait_event(self._skip_bwd_done)          # gfeat of all four stages
     f5, g5 = self.feat["stage5"], self.gfeat["stage5"]
     last = self.blocks[-1]
     S5 = f5.shape[2] * f5.shape[3]
-    be.relu_mean_bwd(f5, self.gavg, B, 2048, S5, f5.stride(0), last["gpre"], 2048 * S5, False)
-    be.affine_add_relu(last["gpre"], None, None, g5, None, None, B, 2048, S5, 2048 * S5, g5.stride(0),
-                       None, 0, last["gpre"], 2048 * S5, False)
+    be.relu_mean_bwd(f5, self.gavg, B, 2048, S5, f5.stride(0), last.gpre, 2048 * S5, False)
+    be.affine_add_relu(last.gpre, None, None, g5, None, None, B, 2048, S5, 2048 * S5, g5.stride(0),
+                       None, 0, last.gpre, 2048 * S5, False)
     g_in = None          # gradient wrt the block's output (post-ReLU), None for the last block
     for blk in reversed(self.blocks):
       g_in = self._block_bwd(blk, g_in)
       self._flush_wgrads()
-      if blk["prefix"] in GRAD_BUCKET_LABELS:
-        self._grads_ready(blk["prefix"], grad_hook)
+      if blk.prefix in GRAD_BUCKET_LABELS:
+        self._grads_ready(blk.prefix, grad_hook)
     # stem: g_in = d p1
     b1 = bn["encoder.stage1_part2.bn."]
     H1, W1 = self.stem_hw
     be.maxpool_bwd(g_in, self.p1_arg, B, 64, H1, W1, self.gy1)
-    S1 = H1 * W1
     cs = cv["encoder.stage1.conv."]
-    be.bn_bwd(self.y1, 64 * S1, self.gy1, 64 * S1, B, 64, S1, False, False, b1.gamma, b1.scale, b1.shift,
-              b1.saved, self.gy1b, 64 * S1, b1.dgamma, b1.dbeta, dsum=cs.dbias, ndsum=cs.n_ref)
+    self._bn_bwd(b1, self.y1, self.gy1, self.gy1b, H1 * W1, False, False, bias_of=cs)
     self._wgrad(cs, self.s2d(self.img, 3, (1, 2, 2)), None, self.vw(self.gy1b))
     # packed weight grads -> reference layout inside the flat grad slab (1 launch)
-    if grad_hook is not None:
-      self._grads_ready("", grad_hook)
-      self._join_side()
-      return
+    self._grads_ready("", grad_hook)                # (the last bucket; without a hook: the pending weight gradients)
     self._join_side()
-    be.copy_tiles(eng.gpacked, eng.store.grads, eng.unpack_tiles, reverse=True)
+    if grad_hook is None:
+      be.copy_tiles(eng.gpacked, eng.store.grads, eng.unpack_tiles, reverse=True)
 
   def _ray_bwd(self, k: int, g_out: t.Tensor):
     """Scatter-add of the skip channels' gradient into the 2-D map gradient (ray_traced_skip_connection.py:135, autograd)."""
-    d = self.dec[k]
-    ro, (hh, ww) = 2 * d["r"], self.skip_hw[k]
+    d, gm = self.dec[k], self.gsmap[k]
+    ro, (hh, ww) = 2 * d.r, self.skip_hw[k]
     if self.ray_idx is not None:
-      self.be.ray_sample_bwd_idx(g_out[:, d["cout"]:], g_out.stride(0), self.B, self.eng.skip_ch[k], ro, ro, ro,
-                                 self.ray_idx[k], self.gsmap[k], self.gsmap[k].stride(0), hh, ww, False)
+      self.be.ray_sample_bwd_idx(g_out[:, d.cout:], g_out.stride(0), self.B, self.eng.skip_ch[k], ro, ro, ro,
+                                 self.ray_idx[k], gm, gm.stride(0), hh, ww, False)
       return
-    self.be.ray_sample_bwd(g_out[:, d["cout"]:], g_out.stride(0), self.B, self.eng.skip_ch[k], ro, ro, ro,
-                           self.layer_mats[k - 2], self.offset, self.gsmap[k], self.gsmap[k].stride(0), hh, ww, False)
+    self.be.ray_sample_bwd(g_out[:, d.cout:], g_out.stride(0), self.B, self.eng.skip_ch[k], ro, ro, ro,
+                           self.layer_mats[k - 2], self.offset, gm, gm.stride(0), hh, ww, False)
 
   def _skip_bwd(self, k: int, g_out: t.Tensor, on_side: bool):
-    """Backward of the skip connection into decoder stage k+1 (g_out = gradient of that stage's concat buffer)."""
-    eng, be, B = self.eng, self.be, self.B
-    d = self.dec[k]
-    (hh, ww), ns = self.skip_hw[k], eng.skip_ch[k]
-    if not on_side:                             # (asynchronous skip path: the caller ran the scatter on the main stream)
-      self._ray_bwd(k, g_out)
-    cs = eng.convs[f"decoder.rt_skip_{k}.compress_channels."]
-    ft = self.feat[self.skip_src[k]]
-    if on_side:                                 # already on the weight-gradient stream: no hand-over event
-      g = cs.fwd
-      math = ("bf16x3_2d" if (eng.encoder_e2d and self._wg2d_shape_ok(self.vw(self.gsmap[k]), g.window))
-              else self._math(cs, "wgrad"))
-      with _lib.roctx_range("wgrad " + cs.name):
-        be.conv_wgrad(self.vw(ft), None, self.vw(self.gsmap[k]), cs.gwf, g.npad, g.window, g.pad_lo, False,
-                      boxes=(g.n_boxes, g.c_boxes), math=math)
-    else:
-      self._wgrad(cs, self.vw(ft), None, self.vw(self.gsmap[k]))
-    self._bias_grad(cs, self.gsmap[k], hh * ww, ns * hh * ww)
-    self._dgrad(cs, self.vw(self.gsmap[k]), self.vw(self.gfeat[self.skip_src[k]]))
+    """Backward of the skip connection into decoder stage k+1 (g_out = gradient of that stage's concat buffer).
+    on_side: the caller is on the weight-gradient stream already -- no hand-over event for the compress conv's weight gradient."""
+    (hh, ww), ns, gm = self.skip_hw[k], self.eng.skip_ch[k], self.gsmap[k]
+    self._ray_bwd(k, g_out)
+    cs = self.eng.convs[f"decoder.rt_skip_{k}.compress_channels."]
+    self._wgrad(cs, self.vw(self.feat[self.skip_src[k]]), None, self.vw(gm), here=on_side)
+    self._bias_grad(cs, gm, hh * ww, ns * hh * ww)
+    self._dgrad(cs, self.vw(gm), self.vw(self.gfeat[self.skip_src[k]]))
 
-  def _block_bwd(self, blk, g_out: Optional[t.Tensor]) -> t.Tensor:
+  def _block_bwd(self, blk: EncBlock, g_out: Optional[t.Tensor]) -> t.Tensor:
     eng, be, B = self.eng, self.be, self.B
     cv, bn = eng.convs, eng.bns
-    p = blk["prefix"]
-    h = blk["h"]; S = h * blk["w"]
-    f1, f2, f3 = blk["f"]
+    p = blk.prefix
+    S = blk.h * blk.w
+    f1, f2, f3 = blk.f
     ba, bb, bc = bn[p + "op_a.bn."], bn[p + "op_b.bn."], bn[p + "op_c.bn."]
-    gpre = blk["gpre"]
+    gpre = blk.gpre
     cc, cb, ca = cv[p + "op_c.conv."], cv[p + "op_b.conv."], cv[p + "op_a.conv."]
     # d pre = (out > 0 ? g_out : 0) [+ the gradient that arrived through the skip connection]: formed by the backward launch of
     # op_c's norm itself on the HIP backend (crn_batch_renorm_bwd_head), by a launch of its own otherwise
@@ -1454,52 +1464,47 @@ class Plan:
     if gc is not None and not fused_head:
       be.stride2_scatter(gc, g_out)
       gc = None
-    if blk["final"]:
-      act, sB_act, g2, sB_g2 = (self.feat[blk["stage"]], self.feat[blk["stage"]].stride(0),
-                                self.gfeat[blk["stage"]], self.gfeat[blk["stage"]].stride(0))
+    if blk.final:
+      act, sB_act, g2, sB_g2 = (self.feat[blk.stage], self.feat[blk.stage].stride(0),
+                                self.gfeat[blk.stage], self.gfeat[blk.stage].stride(0))
     else:
-      act, sB_act, g2, sB_g2 = blk["out"], f3 * S, None, 0
+      act, sB_act, g2, sB_g2 = blk.out, f3 * S, None, 0
     # conv bias gradients = sum(dx) of the following norm, fused into bn_bwd (dsum)
     if fused_head:
-      be.bn_bwd_head(blk["yc"], f3 * S, gpre, f3 * S, g_out, f3 * S, act, sB_act, g2, sB_g2, B, f3, S, bc.gamma, bc.scale,
-                     bc.shift, bc.saved, blk["gyc"], f3 * S, bc.dgamma, bc.dbeta, dsum=cc.dbias, ndsum=cc.n_ref,
-                     g_compact=gc, W=blk["w"])
+      be.bn_bwd_head(blk.yc, f3 * S, gpre, f3 * S, g_out, f3 * S, act, sB_act, g2, sB_g2, B, f3, S, bc.gamma, bc.scale,
+                     bc.shift, bc.saved, blk.gyc, f3 * S, bc.dgamma, bc.dbeta, dsum=cc.dbias, ndsum=cc.n_ref,
+                     g_compact=gc, W=blk.w)
     else:
       if g_out is not None:
         be.relu_bwd_add(g_out, act, g2, B, f3, S, f3 * S, sB_act, sB_g2, gpre, f3 * S)
-      be.bn_bwd(blk["yc"], f3 * S, gpre, f3 * S, B, f3, S, False, False, bc.gamma, bc.scale, bc.shift,
-                bc.saved, blk["gyc"], f3 * S, bc.dgamma, bc.dbeta, dsum=cc.dbias, ndsum=cc.n_ref)
+      self._bn_bwd(bc, blk.yc, gpre, blk.gyc, S, False, False, bias_of=cc)
     trb = Transform(bb.scale, bb.shift, post_relu=True)
     tra = Transform(ba.scale, ba.shift, post_relu=True)
-    self._wgrad(cc, self.vw(blk["yb"]), trb, self.vw(blk["gyc"]))
+    self._wgrad(cc, self.vw(blk.yb), trb, self.vw(blk.gyc))
     be.splitk_defer()                         # the norm's backward below is the only reader of gab: it adds up the splits
-    self._dgrad(cc, self.vw(blk["gyc"]), self.vw(blk["gab"]))
-    be.bn_bwd(blk["yb"], f2 * S, blk["gab"], f2 * S, B, f2, S, False, True, bb.gamma, bb.scale, bb.shift,
-              bb.saved, blk["gyb"], f2 * S, bb.dgamma, bb.dbeta, dsum=cb.dbias, ndsum=cb.n_ref)
-    self._wgrad(cb, self.vw(blk["ya"]), tra, self.vw(blk["gyb"]))
+    self._dgrad(cc, self.vw(blk.gyc), self.vw(blk.gab))
+    self._bn_bwd(bb, blk.yb, blk.gab, blk.gyb, S, False, True, bias_of=cb)
+    self._wgrad(cb, self.vw(blk.ya), tra, self.vw(blk.gyb))
     be.splitk_defer()
-    self._dgrad(cb, self.vw(blk["gyb"]), self.vw(blk["gaa"]))
-    be.bn_bwd(blk["ya"], f1 * S, blk["gaa"], f1 * S, B, f1, S, False, True, ba.gamma, ba.scale, ba.shift,
-              ba.saved, blk["gya"], f1 * S, ba.dgamma, ba.dbeta, dsum=ca.dbias, ndsum=ca.n_ref)
-    cur = blk["in"]
-    xin = self.vw(blk["xs"]) if blk["stride"] == 2 else self.vw(cur)
-    self._wgrad(ca, xin, None, self.vw(blk["gya"]))
-    if blk["down"]:
+    self._dgrad(cb, self.vw(blk.gyb), self.vw(blk.gaa))
+    self._bn_bwd(ba, blk.ya, blk.gaa, blk.gya, S, False, True, bias_of=ca)
+    xin = self.vw(blk.xs) if blk.stride == 2 else self.vw(blk.inp)
+    self._wgrad(ca, xin, None, self.vw(blk.gya))
+    if blk.down:
       bs = bn[p + "shortcut.bn."]
       csn = cv[p + "shortcut.conv."]
-      be.bn_bwd(blk["ys"], f3 * S, gpre, f3 * S, B, f3, S, False, False, bs.gamma, bs.scale, bs.shift,
-                bs.saved, blk["gys"], f3 * S, bs.dgamma, bs.dbeta, dsum=csn.dbias, ndsum=csn.n_ref)
-      self._wgrad(csn, xin, None, self.vw(blk["gys"]))
-      gin = blk["gin"]
-      gv = self.vw(blk["gxs"]) if blk["stride"] == 2 else self.vw(gin)
-      self._dgrad(ca, self.vw(blk["gya"]), gv)
-      self._dgrad(csn, self.vw(blk["gys"]), gv, accumulate=True)
-      if blk["stride"] == 2:
+      self._bn_bwd(bs, blk.ys, gpre, blk.gys, S, False, False, bias_of=csn)
+      self._wgrad(csn, xin, None, self.vw(blk.gys))
+      gin = blk.gin
+      gv = self.vw(blk.gxs) if blk.stride == 2 else self.vw(gin)
+      self._dgrad(ca, self.vw(blk.gya), gv)
+      self._dgrad(csn, self.vw(blk.gys), gv, accumulate=True)
+      if blk.stride == 2:
         if hasattr(be, "bn_bwd_head"):
-          self._g_compact = blk["gxs"]                # expanded by its reader: the norm backward at the head of the block in front
+          self._g_compact = blk.gxs                   # expanded by its reader: the norm backward at the head of the block in front
         else:
-          be.stride2_scatter(blk["gxs"], gin)         # every element of gin is written (zeros between the samples)
+          be.stride2_scatter(blk.gxs, gin)            # every element of gin is written (zeros between the samples)
       return gin
     # identity block: d in = d pre + dgrad(op_a)
-    self._dgrad(ca, self.vw(blk["gya"]), self.vw(gpre), accumulate=True)
+    self._dgrad(ca, self.vw(blk.gya), self.vw(gpre), accumulate=True)
     return gpre

@@ -48,7 +48,7 @@ for math in ("fp32", "bf16x3"):
     for k in (5, 4):
       ga, gb_ = pa.gsmap[k], pb.gsmap[k]
       dch = (ga - gb_).abs().amax((0, 2, 3)) / ga.abs().max()
-      gu_a, gu_b = pa.dec[k + 1]["gu"], pb.dec[k + 1]["gu"]
+      gu_a, gu_b = pa.dec[k + 1].gu, pb.dec[k + 1].gu
       print(f"   gsmap[{k}] final per-channel diff: " + " ".join(f"{float(v):.0e}" for v in dch) +
             f" | gu[{k + 1}] diff {float((gu_a - gu_b).abs().max() / gu_a.abs().max()):.1e}")
     lg = float((ms[0].engine.plan(B).logits - ms[1].engine.plan(B).logits).abs().max())

@@ -17,7 +17,7 @@ for rep in range(3):
   p = m.engine.plan(B)
   got = p.gsmap[5].clone()
   p.gsmap[5].zero_()
-  p._ray_bwd(5, p.dec[6]["gu"])
+  p._ray_bwd(5, p.dec[6].gu)
   t.cuda.synchronize()
   ref = p.gsmap[5].clone()
   d = (got - ref).abs()
