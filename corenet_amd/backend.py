@@ -14,7 +14,7 @@ import torch as t
 
 from corenet_amd import _lib
 from corenet_amd._lib import CrnInTransform, CrnView, ptr
-from corenet_amd.views import View
+from corenet_amd.views import View, space_to_depth_view, view_of
 
 _DTYPE_CODE = {t.float32: 0, t.uint8: 1, t.int32: 2, t.float64: 3, t.int64: 4, t.int16: 5, t.int8: 6}
 
@@ -194,6 +194,14 @@ class HipBackend:
     self.lib.crn_conv2d_bf3(C.byref(_cview(x)), _ctr(tr), ptr(wop), npad, ptr(bias), bias_sB, C.byref(_cview(y)),
                             window[1], window[2], pad_lo[1], pad_lo[2], int(accumulate), _lib.stream())
 
+  def _ximage(self, xp: int, sB: int, B: int, D: int, H: int, W: int, tr: Optional[Transform], alloc) -> t.Tensor:
+    """T(x) transformed and split once (crn_convt_s2k7_ximage) instead of in every workgroup of the four parity pairs of the
+    weight gradient; xp: address of x [B,16,D,H,W], dense inside a sample; alloc(bytes) -> the uint8 buffer of the image."""
+    nb = self.lib.crn_convt_s2k7_ximage_bytes(B, D, H, W)
+    img = alloc(nb)
+    self.lib.crn_convt_s2k7_ximage(xp, sB, B, D, H, W, _ctr(tr), ptr(img), nb, _lib.stream())
+    return img
+
   def convt_ximage(self, x: t.Tensor, tr: Optional[Transform], img: Optional[t.Tensor] = None) -> Optional[t.Tensor]:
     """Operand image of T(x) for the parity-walk weight gradient (crn_convt_s2k7_ximage): x [B,16,D,H,W] dense inside a sample.
     Returns the image (`img` when it is large enough, else a fresh buffer the caller should keep) or None in deterministic mode."""
@@ -201,11 +209,31 @@ class HipBackend:
       return None
     B, cin, D, H, W = x.shape
     assert cin == 16 and x[0].is_contiguous()
-    nb = self.lib.crn_convt_s2k7_ximage_bytes(B, D, H, W)
-    if img is None or img.numel() < nb:
-      img = t.empty(nb, dtype=t.uint8, device=x.device)
-    self.lib.crn_convt_s2k7_ximage(ptr(x), x.stride(0), B, D, H, W, _ctr(tr), ptr(img), nb, _lib.stream())
-    return img
+    return self._ximage(ptr(x), x.stride(0), B, D, H, W, tr,
+                        lambda nb: img if img is not None and img.numel() >= nb else t.empty(nb, dtype=t.uint8, device=x.device))
+
+  def _wgrad_ct_par(self, x: View, tr: Optional[Transform], dy: View, dw: t.Tensor, npad: int, zero_first: bool,
+                    ximg: Optional[t.Tensor]) -> bool:
+    """The parity-walk weight gradient of decoder stage_6.t1 with > 8 classes (crn_convt_s2k7_wgrad_bf3).  x: the plain view of the
+    layer's input, dy: the space-to-depth view of the output gradient tensor, ximg: the operand image of T(x) when the caller made
+    it earlier (convt_ximage, e.g. under the forward pass on its side stream).  False: deterministic mode or a shape the kernel
+    does not cover (CRN_EINVAL), nothing was written -- the caller takes the generic split-bf16 engine."""
+    # the C entry takes bare pointers and batch / channel strides: x dense inside a sample, dy the parity-major 2x2x2 view of
+    # channels [0, C) of its own storage (the offset table of such a view is cached: views.space_to_depth_view gives the same object)
+    assert x.chan_off is None and x.C == 16 and x.sW == 1 and x.sH == x.W and x.sD == x.H * x.W and x.sC == x.D * x.H * x.W, x
+    ds, C8 = dy.storage, dy.C // 8
+    assert ds.dim() == 5 and dy.C == 8 * C8 and tuple(ds.shape[2:]) == (2 * x.D, 2 * x.H, 2 * x.W) and ds[0, 0].is_contiguous(), dy
+    ref = space_to_depth_view(view_of(ds).channels(0, C8), (2, 2, 2), parity_major=True)
+    assert all(getattr(dy, f) == getattr(ref, f) for f in ("offset", "B", "C", "D", "H", "W", "sB", "sC", "sD", "sH", "sW")), dy
+    assert dy.chan_off is ref.chan_off, "dy is not the parity-major view"
+    xp = x.storage.data_ptr() + 4 * (x.offset - x.storage.storage_offset())
+    if ximg is None and not self._deterministic:
+      ximg = self._ximage(xp, x.sB, x.B, x.D, x.H, x.W, tr, lambda nb: self.workspace("ct_ximg", nb, ds.device))
+    rc = self.lib._crn_convt_s2k7_wgrad_bf3(xp, x.sB, x.B, x.D, x.H, x.W, _ctr(tr), ds.data_ptr(), ds.stride(0), ds.stride(1), C8,
+                                            ptr(dw), npad, int(zero_first), ptr(ximg), _lib.stream())
+    if rc not in (0, -1):          # (a HIP error of the launch, the raised LDS limit included: never taken for "not covered")
+      raise _lib.HipError(f"crn_convt_s2k7_wgrad_bf3 failed with status {rc}")
+    return rc == 0
 
   def conv_wgrad(self, x: View, tr: Optional[Transform], dy: View, dw: t.Tensor, npad: int,
                  window, pad_lo, zero_first: bool = True, boxes=None, math: str = "fp32", ximg: Optional[t.Tensor] = None):
@@ -217,22 +245,9 @@ class HipBackend:
       self.lib.crn_conv_wgrad_2d_bf3(C.byref(_cview(x)), _ctr(tr), C.byref(_cview(dy)), ptr(dw), npad, window[1],
                                      window[2], pad_lo[1], pad_lo[2], int(zero_first), _lib.stream())
       return
-    if math == "ct_par":           # decoder stage_6.t1 with > 8 classes: the parity-walk weight gradient (csrc/convt_par.hip); x: the plain view
-      xs, ds = x.storage, dy.storage     # of the layer's input, dy: the space-to-depth view of the output gradient tensor
-      xp = xs.data_ptr() + 4 * (x.offset - xs.storage_offset())
-      img = ximg                   # (the caller made it earlier, e.g. under the forward pass on its side stream)
-      if img is None and not self._deterministic:
-        # T(x) transformed and split once (crn_convt_s2k7_ximage) instead of in every workgroup of the four parity pairs
-        nb = self.lib.crn_convt_s2k7_ximage_bytes(x.B, x.D, x.H, x.W)
-        img = self.workspace("ct_ximg", nb, xs.device)
-        self.lib.crn_convt_s2k7_ximage(xp, x.sB, x.B, x.D, x.H, x.W, _ctr(tr), ptr(img), nb, _lib.stream())
-      rc = self.lib._crn_convt_s2k7_wgrad_bf3(xp, x.sB, x.B, x.D, x.H, x.W, _ctr(tr),
-                                              ds.data_ptr(), ds.stride(0), ds.stride(1), dy.C // 8, ptr(dw), npad, int(zero_first),
-                                              ptr(img), _lib.stream())
-      if rc == 0:
+    if math == "ct_par":           # (csrc/convt_par.hip)
+      if self._wgrad_ct_par(x, tr, dy, dw, npad, zero_first, ximg):
         return
-      if rc != -1:                 # CRN_EINVAL: deterministic mode or a shape it does not cover -> the generic split-bf16 engine
-        raise _lib.HipError(f"crn_convt_s2k7_wgrad_bf3 failed with status {rc}")
       math = "bf16x3"
     if math == "bf16x3":
       self.lib.crn_conv_wgrad_bf3_boxes(C.byref(_cview(x)), _ctr(tr), C.byref(_cview(dy)), ptr(dw), npad,

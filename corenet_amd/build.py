@@ -27,7 +27,7 @@ def _stale(obj, src):
   if not os.path.exists(obj):
     return True
   m = os.path.getmtime(obj)
-  deps = [src, os.path.join(CSRC, "crn_common.h"), os.path.join(CSRC, "conv_kernels.h"),
+  deps = [src, os.path.join(CSRC, "crn_common.h"), os.path.join(CSRC, "conv_kernels.h"), os.path.join(CSRC, "bf3_common.h"),
           os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "marching_cubes_common.h"),
           os.path.join(CSRC, "render_common.h"),
           os.path.join(HERE, "..", "include", "corenet_hip.h")]

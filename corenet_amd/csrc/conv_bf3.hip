@@ -25,6 +25,7 @@
 //    BatchRenorm-apply + ReLU of the producer fused into the patch staging like in the fp32 engine.
 //  * register-staged pipeline: global loads of the next slab / next chunk's patch fly under the MFMAs.
 #include "conv_kernels.h"
+#include "bf3_common.h"
 #include <algorithm>
 #include <cstring>
 #include <cstdio>
@@ -34,7 +35,6 @@
 namespace {
 using namespace crnk;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -136,27 +136,6 @@ template <int N, typename VT, int A>
 __device__ __forceinline__ void wait_loads1d_n(VT (&v)[A]) {
 #pragma unroll
   for (int i = 0; i < A; ++i) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v[i]) : "n"(N));
-}
-
-// x = hi + lo with hi = bf16(x) (round to nearest even), lo = bf16(x - hi)
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(v[i] - (float)h);
-  }
-}
-
-
-// The three products of one accumulator -- hi*hi, hi*lo, lo*hi -- as ONE block of three adjacent MFMAs.  Left to the compiler they
-// come out as two adjacent MFMAs and a third one behind LDS reads and address arithmetic; three dependent MFMAs with idle cycles
-// between them make VALU results of OTHER waves on the SIMD go missing (the ray scatter beside these kernels, DESIGN section 3e,
-// tools/mfma_neighbour.py: crn_mfma_probe mode 48 does it in 29 of 30 runs, mode 32 -- this shape -- never).  Same additions in the
-// same order: results are bit-identical.
-__device__ __forceinline__ void mfma3(f32x4& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl) {
-  asm("v_mfma_f32_16x16x32_bf16 %0, %1, %3, %0\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %4, %0\n\tv_mfma_f32_16x16x32_bf16 %0, %2, %3, %0"
-               : "+v"(acc) : "v"(ah), "v"(al), "v"(bh), "v"(bl));
 }
 
 template <int XM> struct XLoad;
@@ -1371,10 +1350,7 @@ int launch_bf3_wgrad(const Bf3WgGeom& g, dim3 grid, size_t lds, hipStream_t st) 
   // software-pipelined LDS reads: measured per variant (profiles/r03_wgrad_pipe_ab.txt)
   constexpr bool pipe = NSUB == 1 || (TPW == 8 && TWT == 16);
   auto k = conv_bf3_wgrad_kernel<NSUB, DM, TPW, TWT, pipe>;
-  if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, grid, dim3(kThreads), lds, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(k, grid, dim3(kThreads), lds, st, g);
 }
 
 unsigned magic20b(int d) { return (unsigned)(((1u << 20) + d - 1) / d); }
@@ -1384,19 +1360,12 @@ int launch_bf3(const Bf3Geom& g, dim3 grid, size_t lds, hipStream_t st) {
   auto k = g.wslab ? conv_bf3_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_kernel<NSUB, XM, NG, ZS, false>;
   if constexpr (NSUB == 1 && XM == 1 && ZS == 1)         // (instantiated where a model layer needs it: stage_6.c1, 28 channels)
     if (g.half_last && g.PW == 20 && g.mw == 16 && g.mh == 1 && g.nsw == 1 && g.nsh == 8) k = g.wslab ? conv_bf3_half_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_half_kernel<NSUB, XM, NG, ZS, false>;
-  if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, grid, dim3(kThreads), lds, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(k, grid, dim3(kThreads), lds, st, g);
 }
 
 template <int NSUB, int XM, int NG>
 int launch_bf3_ws(const Bf3Geom& g, dim3 grid, size_t lds, hipStream_t st) {
-  auto k = conv_bf3_ws_kernel<NSUB, XM, NG>;
-  if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, grid, dim3(kWsThreads), lds, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(conv_bf3_ws_kernel<NSUB, XM, NG>, grid, dim3(kWsThreads), lds, st, g);
 }
 
 // The producers' timetable, run on the host: every plane a step reads was written (by an earlier iteration) and still

@@ -27,13 +27,12 @@
 // pass and the data gradient (packed data-gradient weights).  Numerics: hi*hi + hi*lo + lo*hi with fp32
 // accumulation, ~2^-16 relative per product, as conv_bf3.hip.
 #include "conv_kernels.h"
+#include "bf3_common.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 using namespace crnk;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct E2dGeom {
   crnView x, y;
@@ -57,15 +56,6 @@ struct E2dGeom {
 // entry of the layer in the output, Cin, T, Npad, first workgroup of the layer, KHW: 0 = MFMA operand blocks of the
 // encoder engine below; kh*kw > 0 = slab order of conv_bf3.hip, [chunk of 8 channels][zd][tap slot][n])
 constexpr int kOpFields = 7;
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(v[i] - (float)h);
-  }
-}
 
 // packed fp32 weights -> operand blocks.  entry (kg, ntile, lane = kk*16 + i16): the 8 channels
 // c = 32*(kg / T) + 8*kk + j of tap kg % T for output column 16*ntile + i16, as 8 hi and 8 lo bf16.
@@ -732,15 +722,7 @@ namespace {
 long long* g_stamps = nullptr;
 template <int T, int CB, int TW>
 int launch_e2d(const E2dGeom& g, dim3 grid, size_t lds, hipStream_t st) {
-  static bool attr_done = false;                      // > 64 KiB of dynamic LDS needs the attribute (once per kernel)
-  if (!attr_done) {
-    CRN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_e2d_kernel<T, CB, TW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_e2d_kernel<T, CB, TW>), grid, dim3(256), lds, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(conv_e2d_kernel<T, CB, TW>, grid, dim3(256), lds, st, g);
 }
 }  // namespace
 

@@ -1006,22 +1006,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
 
 template <int MSUB, int NSUB, int XV>
 inline int launch_fwd(const ConvGeom& g, dim3 grid, size_t lds_bytes, hipStream_t st) {
-  auto k = conv_fwd_kernel<MSUB, NSUB, XV>;
-  if (lds_bytes > 65536)
-    CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL(k, grid, dim3(256), lds_bytes, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(conv_fwd_kernel<MSUB, NSUB, XV>, grid, dim3(256), lds_bytes, st, g);
 }
 
 template <int RSUB, int NSUB, bool XV, int DV>
 inline int launch_wgrad(const WgradGeom& g, dim3 grid, size_t lds_bytes, hipStream_t st) {
-  auto k = conv_wgrad_kernel<RSUB, NSUB, XV, DV>;
-  if (lds_bytes > 65536)
-    CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL(k, grid, dim3(256), lds_bytes, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(conv_wgrad_kernel<RSUB, NSUB, XV, DV>, grid, dim3(256), lds_bytes, st, g);
 }
 
 }  // namespace crnk

@@ -18,6 +18,7 @@
 // Weights arrive as an IMAGE in step order, built by crn_bf3_gather_image from the flat parameter slab with a host-made
 // index table (conv_geometry.convt_par_*_table): per step hi[rows][4 taps][32 columns] then lo[...], entries of 8 bf16.
 #include "conv_kernels.h"
+#include "bf3_common.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -26,29 +27,12 @@
 namespace {
 using namespace crnk;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kT = 512;                       // 8 waves: 32 sub-tiles of 16 W positions, 4 per wave
 constexpr int TD = 4, TH = 8, TW = 16;        // tile (positions of the coarse grid)
 constexpr int PD = TD + 3, PH = TH + 3, PW = 20, PHW = PH * PW, NP = PD * PHW;   // patch: origin (d0 - 1, h0 - 1, w0 - 1)
 constexpr int kSlabHalf = 4 * 4 * 32;         // entries (16 B) of the hi (or lo) half of a step's slab: <= 4 rows x 4 taps x 32 columns
 constexpr int kLdsTab = 256;                  // scale / shift of the 16 input channels
 constexpr size_t kLdsFwd = kLdsTab + (size_t)4 * NP * 16 + (size_t)2 * 2 * kSlabHalf * 16;
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(v[i] - (float)h);
-  }
-}
-
-// the three products of an accumulator as one block of adjacent MFMAs (conv_bf3.hip)
-__device__ __forceinline__ void mfma3(f32x4& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl) {
-  asm("v_mfma_f32_16x16x32_bf16 %0, %1, %3, %0\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %4, %0\n\tv_mfma_f32_16x16x32_bf16 %0, %2, %3, %0"
-      : "+v"(acc) : "v"(ah), "v"(al), "v"(bh), "v"(bl));
-}
 
 struct CtGeom {
   const float* x; long long x_sB; int B, D, H, W;          // forward: input [B][16][D][H][W]; data gradient: dx (output)
@@ -940,51 +924,86 @@ extern "C" int crn_bf3_gather_image(const float* src, const int32_t* table, int 
   return CRN_OK;
 }
 
-extern "C" int crn_convt_s2k7_fwd_bf3(const float* x, int64_t x_sB, int B, int D, int H, int W, const crnInTransform* tr,
-                                      const void* wimg, const float* bias, float* y, int64_t y_sB, int64_t y_sC, int Cout,
-                                      crnStream stream) {
+namespace {
+
+// What every entry fills the same way in its CtGeom / CtWgGeom: the 16-channel tensor on the coarse grid, the input transform and
+// the tiling of the grid (td x TH x TW positions) -> tiles of the whole batch (the caller rejects more than kMaxTiles), -1: no whole
+// number of tiles
+constexpr int64_t kMaxTiles = 0x7fffffff;
+template <typename Geom>
+int64_t ct_grid(Geom& g, const float* x, int64_t x_sB, int B, int D, int H, int W, int td, const crnInTransform* tr) {
+  if (D % td || H % TH || W % TW) return -1;
+  g.x = x; g.x_sB = x_sB; g.B = B; g.D = D; g.H = H; g.W = W;
+  if (tr && tr->scale) { g.scale = tr->scale; g.shift = tr->shift; g.pre_relu = tr->pre_relu; g.post_relu = tr->post_relu; }
+  g.tilesD = D / td; g.tilesH = H / TH; g.tilesW = W / TW;
+  return (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
+}
+
+// the resident-weights kernels: one persistent workgroup per CU, each walks `per` tiles
+template <bool DGRAD>
+int launch_res(const CtGeom& g, int64_t tiles, hipStream_t st) {
+  constexpr int kWgs = 256;
+  const int per = crn_cdiv(tiles, std::min<int64_t>(tiles, kWgs)), wgs = crn_cdiv(tiles, per);
+  return crn_launch(convt_res_kernel<DGRAD>, dim3((unsigned)wgs), dim3(kT), kLdsRes, st, g, (int)tiles, per);
+}
+
+// crn_convt_s2k7_fwd_bf3 (1..16 classes) and, `resident`, crn_convt_s2k7_c2_fwd_bf3 (exactly 2)
+int ct_forward(bool resident, const float* x, int64_t x_sB, int B, int D, int H, int W, const crnInTransform* tr, const void* wimg,
+               const float* bias, float* y, int64_t y_sB, int64_t y_sC, int Cout, crnStream stream) {
   CRN_ENTRY(stream);
-  if (!x || !wimg || !y || B < 1 || Cout < 1 || Cout > 16) return CRN_EINVAL;
-  if (D % TD || H % TH || W % TW || D < TD || (W & 3)) return CRN_EINVAL;
+  if (!x || !wimg || !y || B < 1) return CRN_EINVAL;
+  if (resident ? Cout != 2 : (Cout < 1 || Cout > 16 || D < TD)) return CRN_EINVAL;
   if ((int64_t)16 * D * H * W >= ((int64_t)1 << 29)) return CRN_EINVAL;          // 32-bit byte offsets inside a sample
   if ((((uintptr_t)x) & 15) || (x_sB & 3) || (((uintptr_t)y) & 15) || (y_sB & 3) || (y_sC & 3)) return CRN_EINVAL;
   CtGeom g{};
-  g.x = x; g.x_sB = x_sB; g.B = B; g.D = D; g.H = H; g.W = W;
-  if (tr && tr->scale) { g.scale = tr->scale; g.shift = tr->shift; g.pre_relu = tr->pre_relu; g.post_relu = tr->post_relu; }
+  const int64_t tiles = ct_grid(g, x, x_sB, B, D, H, W, TD, tr);
+  if (tiles < 0 || tiles > kMaxTiles) return CRN_EINVAL;
   g.wimg = wimg; g.bias = bias; g.y = y; g.y_sB = y_sB; g.y_sC = y_sC; g.Cout = Cout;
-  g.tilesD = D / TD; g.tilesH = H / TH; g.tilesW = W / TW;
-  const int64_t tiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
-  if (tiles > 0x7fffffff) return CRN_EINVAL;
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void*)convt_par_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsFwd) == hipSuccess;
-  }();
-  if (!attr) return CRN_EINVAL;
-  hipLaunchKernelGGL(convt_par_fwd_kernel, dim3((unsigned)tiles), dim3(kT), kLdsFwd, (hipStream_t)stream, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  if (resident) return launch_res<false>(g, tiles, (hipStream_t)stream);
+  return crn_launch(convt_par_fwd_kernel, dim3((unsigned)tiles), dim3(kT), kLdsFwd, (hipStream_t)stream, g);
+}
+
+// crn_convt_s2k7_dgrad_bf3 (1..16 classes, in 8-channel halves; dy channels at least one output volume apart) and, `resident`,
+// crn_convt_s2k7_c2_dgrad_bf3 (1 or 2 classes)
+int ct_dgrad(bool resident, const float* dy, int64_t dy_sB, int64_t dy_sC, int Cout, int B, int D, int H, int W, const void* wimg,
+             float* dx, int64_t dx_sB, int accumulate, crnStream stream) {
+  CRN_ENTRY(stream);
+  if (!dy || !wimg || !dx || B < 1 || Cout < 1 || Cout > (resident ? 2 : 16)) return CRN_EINVAL;
+  if (!resident && (D < TD || dy_sC < (int64_t)8 * D * H * W)) return CRN_EINVAL;
+  if ((int64_t)Cout * dy_sC >= ((int64_t)1 << 29)) return CRN_EINVAL;            // 32-bit byte offsets
+  if ((((uintptr_t)dy) & 15) || (dy_sB & 3) || (dy_sC & 3) || (((uintptr_t)dx) & 15) || (dx_sB & 3)) return CRN_EINVAL;
+  CtGeom g{};
+  const int64_t tiles = ct_grid(g, dx, dx_sB, B, D, H, W, TD, nullptr);
+  if (tiles < 0 || tiles > kMaxTiles) return CRN_EINVAL;
+  g.wimg = wimg; g.y = const_cast<float*>(dy); g.y_sB = dy_sB; g.y_sC = dy_sC; g.Cout = Cout; g.accumulate = accumulate ? 1 : 0;
+  if (resident) return launch_res<true>(g, tiles, (hipStream_t)stream);
+  g.nhalf = (Cout + 7) / 8;
+  return crn_launch(convt_par_dgrad_kernel, dim3((unsigned)tiles), dim3(kT), kLdsFwd, (hipStream_t)stream, g);
+}
+
+}  // namespace
+
+extern "C" int crn_convt_s2k7_fwd_bf3(const float* x, int64_t x_sB, int B, int D, int H, int W, const crnInTransform* tr,
+                                      const void* wimg, const float* bias, float* y, int64_t y_sB, int64_t y_sC, int Cout,
+                                      crnStream stream) {
+  return ct_forward(false, x, x_sB, B, D, H, W, tr, wimg, bias, y, y_sB, y_sC, Cout, stream);
 }
 
 extern "C" int crn_convt_s2k7_dgrad_bf3(const float* dy, int64_t dy_sB, int64_t dy_sC, int Cout, int B, int D, int H, int W,
                                         const void* wimg, float* dx, int64_t dx_sB, int accumulate, crnStream stream) {
-  CRN_ENTRY(stream);
-  if (!dy || !wimg || !dx || B < 1 || Cout < 1 || Cout > 16) return CRN_EINVAL;
-  if (D % TD || H % TH || W % TW || D < TD) return CRN_EINVAL;
-  if ((int64_t)Cout * dy_sC >= ((int64_t)1 << 29) || dy_sC < (int64_t)8 * D * H * W) return CRN_EINVAL;   // 32-bit byte offsets
-  if ((((uintptr_t)dy) & 15) || (dy_sB & 3) || (dy_sC & 3) || (((uintptr_t)dx) & 15) || (dx_sB & 3)) return CRN_EINVAL;
-  CtGeom g{};
-  g.x = dx; g.x_sB = dx_sB; g.B = B; g.D = D; g.H = H; g.W = W;
-  g.wimg = wimg; g.y = const_cast<float*>(dy); g.y_sB = dy_sB; g.y_sC = dy_sC; g.Cout = Cout;
-  g.nhalf = (Cout + 7) / 8; g.accumulate = accumulate ? 1 : 0;
-  g.tilesD = D / TD; g.tilesH = H / TH; g.tilesW = W / TW;
-  const int64_t tiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
-  if (tiles > 0x7fffffff) return CRN_EINVAL;
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void*)convt_par_dgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsFwd) == hipSuccess;
-  }();
-  if (!attr) return CRN_EINVAL;
-  hipLaunchKernelGGL(convt_par_dgrad_kernel, dim3((unsigned)tiles), dim3(kT), kLdsFwd, (hipStream_t)stream, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return ct_dgrad(false, dy, dy_sB, dy_sC, Cout, B, D, H, W, wimg, dx, dx_sB, accumulate, stream);
+}
+
+// Two classes (h7): the resident-weights kernels (see convt_res_kernel).  wimg: conv_geometry.convt_res_fwd_table / _dgrad_table.
+extern "C" int crn_convt_s2k7_c2_fwd_bf3(const float* x, int64_t x_sB, int B, int D, int H, int W, const crnInTransform* tr,
+                                         const void* wimg, const float* bias, float* y, int64_t y_sB, int64_t y_sC, int Cout,
+                                         crnStream stream) {
+  return ct_forward(true, x, x_sB, B, D, H, W, tr, wimg, bias, y, y_sB, y_sC, Cout, stream);
+}
+
+extern "C" int crn_convt_s2k7_c2_dgrad_bf3(const float* dy, int64_t dy_sB, int64_t dy_sC, int Cout, int B, int D, int H, int W,
+                                           const void* wimg, float* dx, int64_t dx_sB, int accumulate, crnStream stream) {
+  return ct_dgrad(true, dy, dy_sB, dy_sC, Cout, B, D, H, W, wimg, dx, dx_sB, accumulate, stream);
 }
 
 extern "C" size_t crn_convt_s2k7_ximage_bytes(int B, int D, int H, int W) {
@@ -1013,20 +1032,17 @@ extern "C" int crn_convt_s2k7_wgrad_bf3(const float* x, int64_t x_sB, int B, int
   CRN_ENTRY(stream);
   if (!x || !dy || !dw || B < 1 || Cout < 1 || Cout > 16 || Npad < 8 * Cout) return CRN_EINVAL;
   if (ximg && (((uintptr_t)ximg) & 15)) return CRN_EINVAL;
-  if (D % WTD || H % TH || W % TW) return CRN_EINVAL;
   if (crn_deterministic()) return CRN_EINVAL;                 // (split sums with atomics: the caller takes the generic engine)
   if ((int64_t)16 * D * H * W >= ((int64_t)1 << 29) || (int64_t)Cout * dy_sC >= ((int64_t)1 << 29)) return CRN_EINVAL;
   if ((((uintptr_t)x) & 15) || (x_sB & 3) || (((uintptr_t)dy) & 15) || (dy_sB & 3) || (dy_sC & 3)) return CRN_EINVAL;
+  CtWgGeom g{};
+  const int64_t ntiles = ct_grid(g, x, x_sB, B, D, H, W, WTD, tr);
+  if (ntiles < 0) return CRN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)16 * 64 * Npad * sizeof(float), st));
-  CtWgGeom g{};
-  g.x = x; g.x_sB = x_sB; g.B = B; g.D = D; g.H = H; g.W = W;
-  if (tr && tr->scale) { g.scale = tr->scale; g.shift = tr->shift; g.pre_relu = tr->pre_relu; g.post_relu = tr->post_relu; }
+  if (ntiles > kMaxTiles) return CRN_EINVAL;
   g.dy = dy; g.dy_sB = dy_sB; g.dy_sC = dy_sC; g.Cout = Cout; g.dw = dw; g.Npad = Npad;
   g.ximg = reinterpret_cast<const float*>(ximg); g.ximg_sB = (long long)16 * D * H * W;      // (floats per sample: 4 regions x 4 floats per entry)
-  g.tilesD = D / WTD; g.tilesH = H / TH; g.tilesW = W / TW;
-  const int64_t ntiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
-  if (ntiles > 0x7fffffff) return CRN_EINVAL;
   g.ntiles = (int)ntiles;
   // One round of 256 workgroups (one per CU), dealt to the four (rd, rh) pairs in proportion to the cost of a tile: its multiplies
   // (taps per wave x 8 waves: 40 / 48 / 48 / 64) plus the staging of the tile, which is the same for every pair (kStage, in taps)
@@ -1044,62 +1060,5 @@ extern "C" int crn_convt_s2k7_wgrad_bf3(const float* x, int64_t x_sB, int B, int
     wgs += n;
     g.wg_end[p] = wgs;
   }
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void*)convt_par_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWg) == hipSuccess;
-  }();
-  if (!attr) return CRN_EINVAL;
-  hipLaunchKernelGGL(convt_par_wgrad_kernel, dim3((unsigned)wgs), dim3(kT), kLdsWg, st, g);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
-}
-
-// Two classes (h7): the resident-weights kernels (see convt_res_kernel).  wimg: conv_geometry.convt_res_fwd_table / _dgrad_table.
-extern "C" int crn_convt_s2k7_c2_fwd_bf3(const float* x, int64_t x_sB, int B, int D, int H, int W, const crnInTransform* tr,
-                                         const void* wimg, const float* bias, float* y, int64_t y_sB, int64_t y_sC, int Cout,
-                                         crnStream stream) {
-  CRN_ENTRY(stream);
-  if (!x || !wimg || !y || B < 1 || Cout != 2) return CRN_EINVAL;
-  if (D % TD || H % TH || W % TW) return CRN_EINVAL;
-  if ((int64_t)16 * D * H * W >= ((int64_t)1 << 29)) return CRN_EINVAL;
-  if ((((uintptr_t)x) & 15) || (x_sB & 3) || (((uintptr_t)y) & 15) || (y_sB & 3) || (y_sC & 3)) return CRN_EINVAL;
-  CtGeom g{};
-  g.x = x; g.x_sB = x_sB; g.B = B; g.D = D; g.H = H; g.W = W;
-  if (tr && tr->scale) { g.scale = tr->scale; g.shift = tr->shift; g.pre_relu = tr->pre_relu; g.post_relu = tr->post_relu; }
-  g.wimg = wimg; g.bias = bias; g.y = y; g.y_sB = y_sB; g.y_sC = y_sC; g.Cout = Cout;
-  g.tilesD = D / TD; g.tilesH = H / TH; g.tilesW = W / TW;
-  const int64_t tiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
-  if (tiles > 0x7fffffff) return CRN_EINVAL;
-  constexpr int kWgs = 256;
-  const int per = crn_cdiv(tiles, std::min<int64_t>(tiles, kWgs)), wgs = crn_cdiv(tiles, per);
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void*)convt_res_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsRes) == hipSuccess;
-  }();
-  if (!attr) return CRN_EINVAL;
-  hipLaunchKernelGGL(convt_res_kernel<false>, dim3((unsigned)wgs), dim3(kT), kLdsRes, (hipStream_t)stream, g, (int)tiles, per);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
-}
-
-extern "C" int crn_convt_s2k7_c2_dgrad_bf3(const float* dy, int64_t dy_sB, int64_t dy_sC, int Cout, int B, int D, int H, int W,
-                                           const void* wimg, float* dx, int64_t dx_sB, int accumulate, crnStream stream) {
-  CRN_ENTRY(stream);
-  if (!dy || !wimg || !dx || B < 1 || Cout < 1 || Cout > 2) return CRN_EINVAL;
-  if (D % TD || H % TH || W % TW) return CRN_EINVAL;
-  if ((int64_t)Cout * dy_sC >= ((int64_t)1 << 29)) return CRN_EINVAL;
-  if ((((uintptr_t)dy) & 15) || (dy_sB & 3) || (dy_sC & 3) || (((uintptr_t)dx) & 15) || (dx_sB & 3)) return CRN_EINVAL;
-  CtGeom g{};
-  g.x = dx; g.x_sB = dx_sB; g.B = B; g.D = D; g.H = H; g.W = W;
-  g.wimg = wimg; g.y = const_cast<float*>(dy); g.y_sB = dy_sB; g.y_sC = dy_sC; g.Cout = Cout; g.accumulate = accumulate ? 1 : 0;
-  g.tilesD = D / TD; g.tilesH = H / TH; g.tilesW = W / TW;
-  const int64_t tiles = (int64_t)B * g.tilesD * g.tilesH * g.tilesW;
-  if (tiles > 0x7fffffff) return CRN_EINVAL;
-  constexpr int kWgs = 256;
-  const int per = crn_cdiv(tiles, std::min<int64_t>(tiles, kWgs)), wgs = crn_cdiv(tiles, per);
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void*)convt_res_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsRes) == hipSuccess;
-  }();
-  if (!attr) return CRN_EINVAL;
-  hipLaunchKernelGGL(convt_res_kernel<true>, dim3((unsigned)wgs), dim3(kT), kLdsRes, (hipStream_t)stream, g, (int)tiles, per);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(convt_par_wgrad_kernel, dim3((unsigned)wgs), dim3(kT), kLdsWg, st, g);
 }

@@ -16,6 +16,17 @@
     if (_e != hipSuccess) return (int)_e;        \
   } while (0)
 
+// Launch `kernel` with `lds_bytes` of dynamic LDS -> hipSuccess (= CRN_OK) or the HIP error code (positive, never CRN_EINVAL).
+// More than 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize raised first: done on every such launch, for the size of
+// that launch, and a failure is reported by the call it happened in.
+template <typename... P, typename... A>
+inline int crn_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const A&... args) {
+  if (lds_bytes > 65536)
+    CRN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, static_cast<P>(args)...);
+  return (int)hipGetLastError();
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int crn_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -748,12 +748,8 @@ inline size_t fused_offset(int64_t nwords) { return 2 * align256((size_t)nwords 
 template <typename T, int WX, bool SV>
 int launch_fused(const T* grid, T* out, int G, int D, int H, int W, int zs, int nslabs, size_t lds, u64* halo,
                  FusedCtl* ctl, u64* E, u64* R, int max_rounds, int relaxed, hipStream_t st, FillView vi, FillView vo) {
-  auto k = fill_fused_kernel<T, WX, SV>;
-  if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(G * nslabs), dim3(1024), lds, st, grid, out, D, H, W, zs, nslabs, halo, ctl, E, R, max_rounds, relaxed,
-                     vi, vo);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(fill_fused_kernel<T, WX, SV>, dim3(G * nslabs), dim3(1024), lds, st, grid, out, D, H, W, zs, nslabs, halo, ctl, E, R,
+                    max_rounds, relaxed, vi, vo);
 }
 
 template <typename T, int WX, bool SV>
@@ -764,11 +760,7 @@ int launch_rescue(const T* grid, T* out, u64* E, u64* R, int N, int D, int H, in
   const int nslabs = (D + zs - 1) / zs;
   zs = (D + nslabs - 1) / nslabs;
   const size_t lds = (size_t)(2 * zs + 2) * plane;
-  auto k = fill_rescue_kernel<T, WX, SV>;
-  if (lds > 65536) CRN_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(N), dim3(512), lds, st, grid, out, E, R, D, H, W, zs, nslabs, vi, vo);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(fill_rescue_kernel<T, WX, SV>, dim3(N), dim3(512), lds, st, grid, out, E, R, D, H, W, zs, nslabs, vi, vo);
 }
 
 // ONE launch per call (per G grids): the single-launch kernel carries its own rescue path (its last workgroup out);

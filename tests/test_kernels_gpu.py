@@ -417,6 +417,101 @@ def test_convt_resident_weights_two_classes(be, dims, B):
     print(f"resident weights B {B} {nm}: {a.elapsed_time(b_) / 5 * 1e3:.0f} us")
 
 
+def test_convt_entries_accept_reject_contract(be):
+  """What the six C entries of csrc/convt_par.hip accept and reject (crn_convt_s2k7_{fwd,dgrad,c2_fwd,c2_dgrad,wgrad}_bf3 and
+  crn_convt_s2k7_ximage), called raw (no status check) at B 1, 4 x 8 x 16, two classes: every row is the good call with exactly ONE
+  thing wrong, its literal status is asserted, and no output buffer may be touched (a rejected call launches nothing).  The entries
+  differ on purpose: the generic ones take 1..16 classes, c2_fwd exactly 2, c2_dgrad 1 or 2 (that row is a GOOD call: checked against
+  the contract emulator, 2e-5 of the range like test_convt_resident_weights_two_classes); only the generic data gradient wants
+  dy_sC >= 8 D H W; the weight gradient tiles D by 2 and steps aside in deterministic mode.  Every buffer has one sample + 64 bytes of
+  slack behind its real size (and dy / y 18 channels, dw the 17-class size) so that a call accepted by mistake stays inside it."""
+  if _SELF:
+    return
+  from corenet_amd import _lib
+  from corenet_amd.model import conv_geometry as G
+  B, D, H, W, cout = 1, 4, 8, 16, 2
+  S, SENT = D * H * W, -77.0
+  g = t.Generator().manual_seed(7)
+  ysC, ysB, xsB = 8 * S, 18 * 8 * S, 16 * S
+  x = t.randn((B + 1) * xsB + 16, generator=g).to(DEV)
+  dyc = t.randn((B + 1) * ysB + 16, generator=g); dy = dyc.to(DEV)
+  y = t.full(((B + 1) * ysB + 16,), SENT, device=DEV)
+  dx = t.full(((B + 1) * xsB + 16,), SENT, device=DEV)
+  dx1 = t.full(((B + 1) * xsB + 16,), SENT, device=DEV)                           # output of the one good row
+  dw = t.full((16 * 64 * 8 * 17 + 16,), SENT, device=DEV)
+  nimg = be.lib.crn_convt_s2k7_ximage_bytes(B, D, H, W)
+  ximg = t.full((be.lib.crn_convt_s2k7_ximage_bytes(B + 1, D, H, W) + 64,), 0xA5, dtype=t.uint8, device=DEV)
+  wbytes = max(fn(ws, 0)[1] for fn, ws in ((G.convt_par_fwd_table, (16, 16, 7, 7, 7)), (G.convt_par_dgrad_table, (16, 16, 7, 7, 7)),
+                                           (G.convt_res_fwd_table, (16, 2, 7, 7, 7)), (G.convt_res_dgrad_table, (16, 2, 7, 7, 7))))
+  wimg = t.zeros(wbytes + 64, dtype=t.uint8, device=DEV)
+  w1 = t.randn(16, 1, 7, 7, 7, generator=g) / np.sqrt(16 * 343 / 8)               # the one-class image of the good row
+  tab1, nb1 = G.convt_res_dgrad_table(tuple(w1.shape), 0)
+  img1c = t.zeros(nb1 + 64, dtype=t.uint8)
+  EMU.bf3_gather_image(w1.reshape(-1), t.as_tensor(tab1), img1c)
+  img1 = img1c.to(DEV)
+
+  st = _lib.stream()
+  P = lambda tt: tt.data_ptr()
+  fwd_args = dict(x=P(x), x_sB=xsB, B=B, D=D, H=H, W=W, tr=None, wimg=P(wimg), bias=None, y=P(y), y_sB=ysB, y_sC=ysC, Cout=cout, stream=st)
+  dgr_args = dict(dy=P(dy), dy_sB=ysB, dy_sC=ysC, Cout=cout, B=B, D=D, H=H, W=W, wimg=P(wimg), dx=P(dx), dx_sB=xsB, accumulate=0, stream=st)
+  good = {
+      "fwd": fwd_args, "c2_fwd": fwd_args, "dgrad": dgr_args, "c2_dgrad": dgr_args,
+      "wgrad": dict(x=P(x), x_sB=xsB, B=B, D=D, H=H, W=W, tr=None, dy=P(dy), dy_sB=ysB, dy_sC=ysC, Cout=cout, dw=P(dw), Npad=8 * cout,
+                    zero_first=1, ximg=P(ximg), stream=st),
+      "ximage": dict(x=P(x), x_sB=xsB, B=B, D=D, H=H, W=W, tr=None, img=P(ximg), img_bytes=nimg, stream=st),
+  }
+  fns = {"fwd": be.lib._crn_convt_s2k7_fwd_bf3, "c2_fwd": be.lib._crn_convt_s2k7_c2_fwd_bf3, "dgrad": be.lib._crn_convt_s2k7_dgrad_bf3,
+         "c2_dgrad": be.lib._crn_convt_s2k7_c2_dgrad_bf3, "wgrad": be.lib._crn_convt_s2k7_wgrad_bf3, "ximage": be.lib._crn_convt_s2k7_ximage}
+  call = lambda e, **bad: fns[e](*{**good[e], **bad}.values())
+  EINVAL, ENOMEM = -1, -2
+  FWD, DGR, ALL5 = ("fwd", "c2_fwd"), ("dgrad", "c2_dgrad"), ("fwd", "c2_fwd", "dgrad", "c2_dgrad", "wgrad")
+  rows = []                                                                       # (entry, what is wrong, expected status)
+  for es, names in ((FWD, ("x", "wimg", "y")), (DGR, ("dy", "wimg", "dx")), (("wgrad",), ("x", "dy", "dw")), (("ximage",), ("x", "img"))):
+    rows += [(e, {n: None}, EINVAL) for e in es for n in names]                   # a null required pointer
+  rows += [(e, {"Cout": c}, EINVAL) for e in ("fwd", "dgrad") for c in (0, 17)]
+  rows += [("wgrad", {"Cout": 0}, EINVAL), ("wgrad", {"Cout": 17, "Npad": 8 * 17}, EINVAL)]
+  rows += [("c2_fwd", {"Cout": 3}, EINVAL), ("c2_dgrad", {"Cout": 3}, EINVAL), ("c2_fwd", {"Cout": 1}, EINVAL)]
+  rows += [(e, bad, EINVAL) for e in ALL5 for bad in ({"D": 3}, {"H": 4}, {"W": 8})]
+  for es, names in ((FWD, ("x", "y")), (DGR, ("dy", "dx")), (("wgrad",), ("x", "dy", "ximg")), (("ximage",), ("x", "img"))):
+    rows += [(e, {n: good[e][n] + 4}, EINVAL) for e in es for n in names]         # a base pointer off by 4 bytes
+  for es, names in ((FWD, ("x_sB", "y_sB", "y_sC")), (DGR, ("dx_sB", "dy_sB", "dy_sC")), (("wgrad",), ("x_sB", "dy_sB", "dy_sC")),
+                    (("ximage",), ("x_sB",))):
+    rows += [(e, {n: good[e][n] + 2}, EINVAL) for e in es for n in names]         # a stride that is no multiple of 4
+  rows += [("dgrad", {"dy_sC": 8 * S - 4}, EINVAL), ("wgrad", {"Npad": 8 * cout - 1}, EINVAL), ("ximage", {"img_bytes": nimg - 1}, ENOMEM)]
+  for e, bad, want in rows:
+    rc = call(e, **bad)
+    assert rc == want, (e, bad, rc, want)
+  was = be._deterministic
+  be.set_deterministic(True)
+  try:
+    rc = call("wgrad")
+  finally:
+    be.set_deterministic(was)
+  assert rc == EINVAL, ("wgrad", "deterministic", rc)
+  for name, buf in (("y", y), ("dx", dx), ("dw", dw)):
+    assert bool((buf == SENT).all()), name + " was written by a rejected call"
+  assert bool((ximg == 0xA5).all()), "the operand image was written by a rejected call"
+
+  # c2_dgrad with ONE class is a good call (c2_fwd rejects it above)
+  rc = call("c2_dgrad", Cout=1, wimg=P(img1), dx=P(dx1))
+  assert rc == 0, ("c2_dgrad", "Cout 1", rc)
+  want = t.zeros(B, 16, D, H, W)
+  EMU.convt_par_dgrad(dyc[:B * ysB].view(B, 18, 2 * D, 2 * H, 2 * W), 1, img1c, want, False, host_table=tab1)
+  got = dx1.cpu()
+  e = float((got[:B * xsB].view(B, 16, D, H, W) - want).abs().max() / want.abs().max())
+  print(f"c2_dgrad one class: max-abs-err/max = {e:.2e}")
+  assert e <= 2e-5, ("c2_dgrad", "Cout 1", e)
+  assert bool((got[B * xsB:] == SENT).all())
+  # ... as is a dy whose channels are closer than one output volume, which only the generic data gradient rejects (above)
+  rc = call("c2_dgrad", dy_sC=8 * S - 4)
+  assert rc == 0, ("c2_dgrad", "dy_sC", rc)
+  # ... and the call every row above spoils is one that each entry accepts
+  for e in ("ximage",) + ALL5:
+    rc = call(e)
+    assert rc == 0, (e, "good call", rc)
+  t.cuda.synchronize()
+
+
 @pytest.mark.parametrize("name,kind,wshape,pad,dims,B", BF3_CASES, ids=[c[0] for c in BF3_CASES])
 def test_conv_bf16x3_fwd_dgrad(be, name, kind, wshape, pad, dims, B):
   """The split-bf16 MFMA engine (crn_conv_fwd_bf3) on the decoder layer shapes of stages 4-6
