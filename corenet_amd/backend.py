@@ -496,6 +496,27 @@ class HipBackend:
     st = (C.c_int64 * 4)(*grid.stride())
     self.lib.crn_box_filter(ptr(grid), st, ptr(out), N, D, H, W, int(k), ptr(ws), n, _lib.stream())
 
+  # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
+  def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
+                     tri_index: t.Tensor, valid: t.Tensor):
+    """points [N, S, 3], tri_index [N, S], valid bool [N] <- S area-stratified samples of every object of the soup;
+    tri_offsets: device int64 [N + 1]."""
+    N, T = tri_offsets.numel() - 1, triangles.shape[0]
+    n = self.lib.crn_sample_surface_workspace_bytes(T, N)
+    ws = self.workspace("pm_sample", n, triangles.device)
+    self.lib.crn_sample_surface(ptr(triangles), ptr(tri_offsets), N, T, int(num_samples), int(seed) & 0xffffffff, ptr(ws), n,
+                                ptr(points), ptr(tri_index), ptr(valid), _lib.stream())
+
+  def nearest(self, a: t.Tensor, a_offsets: t.Tensor, b: t.Tensor, b_offsets: t.Tensor, max_na: int, max_nb: int,
+              dist2: t.Tensor, index: t.Tensor):
+    """dist2 [Na], index [Na] <- per query of a the nearest candidate of the same object of b; offsets: device int64
+    [N + 1], max_na / max_nb: the largest object's queries / candidates (host ints)."""
+    N, Na = a_offsets.numel() - 1, a.shape[0]
+    n = self.lib.crn_nearest_workspace_bytes(Na)
+    ws = self.workspace("pm_nearest", n, a.device)
+    self.lib.crn_nearest(ptr(a), ptr(a_offsets), ptr(b), ptr(b_offsets), N, Na, int(max_na), int(max_nb), ptr(ws), n,
+                         ptr(dist2), ptr(index), _lib.stream())
+
   def voxelize_mesh(self, tri, tri_mesh, view2voxel, M, D, H, W, sub_side, mult, conservative,
                     depth_mult, grid):
     self.lib.crn_voxelize_mesh(ptr(tri), ptr(tri_mesh), tri.shape[0], ptr(view2voxel), M, D, H, W,

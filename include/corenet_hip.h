@@ -611,6 +611,40 @@ int crn_voxel_faces_cpu(const int32_t* labels, int N, int D, int H, int W, const
                         const float* box_matrices, float* box_out, const float* matrices, int material_base,
                         int64_t* counts, float* triangles, float* normals, int32_t* material_ids, int num_threads);
 
+/* ---------------- surface points and nearest neighbours (corenet_amd.mesh_metrics) -----------------
+ * Objects are ragged and described by int64 offsets [N + 1] (CSR, non-decreasing, offsets[0] >= 0); an object may be
+ * empty.  Arithmetic: csrc/point_metrics_common.h; rules: corenet_amd/mesh_metrics.py and DESIGN section 15.
+ *
+ * crn_sample_surface: S area-stratified samples of every object of the triangle soup triangles [T][3][3]; object n owns
+ * triangles [tri_offsets[n], tri_offsets[n + 1]).  points f32 [N][S][3], tri_index int32 [N][S] (local to the object),
+ * valid uint8 [N]: 0 when the object has no triangle of positive finite area (its points are 0, its indices -1).  A
+ * triangle's weight is round(area / largest area of the object * 2^24), an integer; sample i takes the triangle whose
+ * interval of the running integer sum contains floor((i + u_i) / S * total), then a point by the square-root warp of two
+ * more uniforms; the uniforms are a hash of (seed, i, 0 / 1 / 2).  A row depends only on (the object's triangles, S, seed).
+ * workspace: crn_sample_surface_workspace_bytes(T, N).  tri_offsets: DEVICE memory for the GPU call.
+ *
+ * crn_nearest: for query q of object n (a [Na][3], a_offsets) the candidate of object n (b [Nb][3], b_offsets) with the
+ * smallest (d2, index), d2 = (dx*dx + dy*dy) + dz*dz in float32 without contraction; a candidate whose d2 is NaN is
+ * never chosen; no eligible candidate: +inf and -1.  dist2 f32 [Na], index int32 [Na] (local to the object).
+ * max_na / max_nb: the largest number of queries / candidates of one object (they size the launch; the offsets stay on
+ * the device).  workspace: crn_nearest_workspace_bytes(Na) (64-bit keys for launches that split the candidates of an
+ * object over several workgroups and merge with atomicMin on (bits(d2) << 32) | index: commutative, so deterministic).
+ * Neither call waits for the GPU.  The host twins take HOST memory and run one object per task.                    */
+#define CRN_PM_MAX_SAMPLES 2147483647LL
+#define CRN_PM_MAX_CANDIDATES 2147483647LL
+size_t crn_sample_surface_workspace_bytes(int64_t T, int N);
+int crn_sample_surface(const float* triangles, const int64_t* tri_offsets, int N, int64_t T, int64_t S, uint32_t seed,
+                       void* workspace, size_t workspace_bytes, float* points, int32_t* tri_index, uint8_t* valid,
+                       crnStream s);
+int crn_sample_surface_cpu(const float* triangles, const int64_t* tri_offsets, int N, int64_t S, uint32_t seed,
+                           float* points, int32_t* tri_index, uint8_t* valid, int num_threads);
+size_t crn_nearest_workspace_bytes(int64_t Na);
+int crn_nearest(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int N, int64_t Na,
+                int64_t max_na, int64_t max_nb, void* workspace, size_t workspace_bytes, float* dist2, int32_t* index,
+                crnStream s);
+int crn_nearest_cpu(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int N,
+                    float* dist2, int32_t* index, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
