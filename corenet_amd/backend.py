@@ -434,6 +434,13 @@ class HipBackend:
     off = self.lib.crn_loss_status_ptr(ptr(ws), B) - ws.data_ptr()
     return int(ws[off:off + 4].view(t.int32)) == 0
 
+  def loss_partials(self, B, Cn, S, device) -> t.Tensor:
+    """The partial sums the first pass of the last loss_fwd_bwd on `device` left at the head of its workspace
+    (include/corenet_hip.h): float64 [B][nblk][6], nblk = min(ceil(S / 2048), 512) (a copy; synchronises)."""
+    ws = self.workspace("loss", self.lib.crn_loss_workspace_bytes(B, Cn), device)
+    nblk = min(max(1, -(-S // 2048)), 512)
+    return ws[:B * nblk * 48].view(t.float64).view(B, nblk, 6).clone()
+
   def softmax_superres(self, logits, m, B, Cn, D, H, W, out):
     self.lib.crn_softmax_superres(ptr(logits), m, B, Cn, D, H, W, ptr(out), _lib.stream())
 

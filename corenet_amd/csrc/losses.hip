@@ -210,7 +210,8 @@ extern "C" int crn_loss_fwd_bwd(int kind, const float* logits, const int32_t* gt
                                 size_t workspace_bytes, crnStream stream) {
   CRN_ENTRY(stream);
   hipStream_t st = (hipStream_t)stream;
-  if (kind < 0 || kind > 4 || B < 1 || C < 2 || C > 32 || S < 1 || !logits || !gt || !loss) return CRN_EINVAL;
+  if (kind < 0 || kind > 4 || B < 1 || B > 64 || C < 2 || C > 32 || S < 1 || !logits || !gt || !loss) return CRN_EINVAL;   // (B: the
+  // finalize kernel's LDS holds 64 samples; rejected here, before anything is launched)
   if (workspace_bytes < crn_loss_workspace_bytes(B, C)) return CRN_ENOMEM;
   const int nblk = loss_nblk(S);
   double* part = reinterpret_cast<double*>(workspace);
@@ -222,7 +223,6 @@ extern "C" int crn_loss_fwd_bwd(int kind, const float* logits, const int32_t* gt
   else if (C <= 16) CRN_LOSS_P1(16); else CRN_LOSS_P1(32);
 #undef CRN_LOSS_P1
   CRN_CHECK_LAUNCH();
-  if (B > 64) return CRN_EINVAL;
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, part, nblk, B, S, kind, grad_scale, loss, coef, bad_label);
   CRN_CHECK_LAUNCH();
   if (dlogits) {

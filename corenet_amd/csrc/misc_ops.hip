@@ -142,6 +142,14 @@ __global__ void linear_bwd_dw_kernel(const float* x, const float* dy, int lddy, 
     db[n] = t;
   }
 }
+// the bias gradient alone (a call without dw): the same sum, in the same order, as in the kernel above
+__global__ void linear_bwd_db_kernel(const float* dy, int lddy, int B, int N, float* db) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float t = 0.f;
+  for (int b = 0; b < B; ++b) t += dy[(int64_t)b * lddy + n];
+  db[n] = t;
+}
 
 __global__ void fill_offset_kernel(float* x, int64_t sB, int64_t S, int c0, const float* offset, int64_t total) {
   const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -437,6 +445,9 @@ extern "C" int crn_linear_bwd(const float* x, const float* w, const float* dy, i
   if (dw) {
     hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(nblk((int64_t)N * K)), dim3(256), 0, (hipStream_t)s, x, dy, lddy, B,
                        K, N, dw, db);
+    CRN_CHECK_LAUNCH();
+  } else if (db) {
+    hipLaunchKernelGGL(linear_bwd_db_kernel, dim3(nblk(N)), dim3(256), 0, (hipStream_t)s, dy, lddy, B, N, db);
     CRN_CHECK_LAUNCH();
   }
   return CRN_OK;

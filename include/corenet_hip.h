@@ -363,6 +363,8 @@ int crn_relu_mean_fwd(const float* x_pre, int B, int C, int64_t S, int64_t sB, f
 /* y[b,n] = bias[n] + sum_k x[b,k] w[n,k]  (nn.Linear, reconstruction_decoder.py:49) */
 int crn_linear_fwd(const float* x, const float* w, const float* bias, int B, int K, int N,
                    float* y, int ldy, crnStream s);
+/* dx[b,k] = sum_n dy[b,n] w[n,k],  dw[n,k] = sum_b dy[b,n] x[b,k],  db[n] = sum_b dy[b,n].  Each of dx, dw, db may be
+ * NULL and is then not computed; every non-NULL one is written, whichever of the others are given.                */
 int crn_linear_bwd(const float* x, const float* w, const float* dy, int lddy, int B, int K, int N,
                    float* dx, float* dw, float* db, crnStream s);
 /* dx[b,c,s] (+)= (x_pre>0) * davg[b,c] / S                                    */
@@ -425,7 +427,13 @@ int crn_ray_sample_bwd_idx(const float* dout, int64_t dout_sB, int B, int C, int
  * when dlogits != NULL, d loss / d logits * grad_scale.
  * workspace: crn_loss_workspace_bytes(B,C).  A label outside [0,C) (the
  * reference raises inside F.one_hot / cross_entropy) is computed as class 0 and
- * sets the int at crn_loss_status_ptr(workspace, B) (device memory) to 1.      */
+ * sets the int at crn_loss_status_ptr(workspace, B) (device memory) to 1; a call
+ * without such a label sets it back to 0.  B <= 64, 2 <= C <= 32; a call outside
+ * these returns CRN_EINVAL and launches nothing (loss, dlogits, workspace untouched).
+ * The workspace begins with the first pass's partial sums, double [B][nblk][6] with
+ * nblk = min(ceil(S / 2048), 512): block j sums, in a fixed order, the voxels v with
+ * (v / 256) % nblk == j -- I_fg, U_fg, I_ag, U_ag, w * (logZ - logit[gt]), and the
+ * number of labels outside [0,C).                                                      */
 int crn_loss_fwd_bwd(int kind, const float* logits, const int32_t* gt, const float* weights,
                      int B, int C, int64_t S, float* loss, float* dlogits, float grad_scale,
                      void* workspace, size_t workspace_bytes, crnStream s);

@@ -407,11 +407,37 @@ class EmuBackend:
   def loss_fwd_bwd(self, kind, logits, gt_i32, B, Cn, S, loss, dlogits, grad_scale=1.0, weights=None):
     l = logits.detach().clone().requires_grad_(dlogits is not None)
     w = None if weights is None else weights.view(l.shape[0], *l.shape[2:])
-    v = getattr(O, self.LOSSES[kind])(gt_i32.long().view(l.shape[0], *l.shape[2:]), l, w)
-    loss.fill_(float(v))
+    # a label outside [0, C) is computed as class 0 and sets the status word; a clean call clears it
+    g = gt_i32.long().view(l.shape[0], *l.shape[2:])
+    bad = (g < 0) | (g >= Cn)
+    self._labels_in_range = not bool(bad.any())
+    g0 = t.where(bad, t.zeros_like(g), g)
+    self._loss_call = (logits.detach().reshape(B, Cn, S), g0.reshape(B, S), bad.reshape(B, S),
+                       None if weights is None else weights.reshape(B, S))
+    v = getattr(O, self.LOSSES[kind])(g0, l, w)
+    loss.fill_(float(v.detach()))
     if dlogits is not None:
       v.backward()
       dlogits.copy_(l.grad * grad_scale)
+
+  def loss_labels_in_range(self, B, Cn, device) -> bool:
+    return self._labels_in_range
+
+  def loss_partials(self, B, Cn, S, device):
+    """The first pass's partial sums, float64 [B][nblk][6], nblk = min(ceil(S / 2048), 512): block j sums the voxels
+    v with (v // 256) % nblk == j; per voxel (float32) I_fg, U_fg, I_ag, U_ag, w * (logZ - l[gt]), label out of range."""
+    l, g, bad, w = self._loss_call
+    w = t.ones(B, S) if w is None else w
+    p = l.softmax(1)
+    pfg, gf = p[:, 1:].sum(1), (g >= 1).float()
+    hot = F.one_hot(g, Cn).permute(0, 2, 1)[:, 1:].float()
+    ia = (hot * p[:, 1:]).sum(1) * (Cn - 1) * w
+    ua = (hot * (Cn - 1) + (1 - hot) * p[:, 1:]).sum(1) * w
+    x = (l.logsumexp(1) - l.gather(1, g[:, None])[:, 0]) * w
+    q = t.stack([t.min(gf, pfg) * w, t.max(gf, pfg) * w, ia, ua, x, bad.float()], 2).double()
+    nblk = min(max(1, -(-S // 2048)), 512)
+    out = t.zeros(B, nblk, 6, dtype=t.float64)
+    return out.index_add_(1, (t.arange(S) // 256) % nblk, q)
 
   def softmax_superres(self, logits, m, B, Cn, D, H, W, out):
     # super_resolution.py:105-112 (reshape/permute) after the per-offset softmax (:124)
@@ -421,8 +447,9 @@ class EmuBackend:
   def argmax_confusion(self, logits, gt_i32, B, Cn, S, labels, cm):
     lab = logits.argmax(1)
     if labels is not None: labels.copy_(lab.to(t.int32))
-    if gt_i32 is not None:
-      cm += O.confusion_matrix(gt_i32, lab, Cn).reshape(-1)
+    if gt_i32 is not None:                               # labels outside [0, C) are not counted
+      g = gt_i32.reshape(-1).long(); ok = (g >= 0) & (g < Cn)
+      cm += O.confusion_matrix(g[ok], lab.reshape(-1)[ok], Cn).reshape(-1)
 
   def adam_step(self, p, g, m, v, n, lr, b1, b2, eps, grad_scale, step):
     gg = g * grad_scale
@@ -459,7 +486,7 @@ class EmuBackend:
         out[b].copy_((labels[lo:hi].to(g.dtype)[:, None, None, None] * g[lo:hi]).max(0).values.to(t.int32))
 
   def add_i64(self, p, n, v):
-    p += v
+    p[:n] += v
 
   def zero(self, x):
     x.zero_()
