@@ -753,6 +753,8 @@ static int bn_stats_impl(const float* x, int B, int C, int64_t S, int64_t sB, in
                          double* ws, size_t ws_bytes, crnStream stream, const BnTail* tail, bool* tail_done) {
   hipStream_t st = (hipStream_t)stream;
   if (B < 1 || C < 1 || S < 1 || B > 64) return CRN_EINVAL;
+  if (!x || !gamma || !beta || !running_mean || !running_var || !scale || !shift) return CRN_EINVAL;
+  if (training && (!nbt || !saved)) return CRN_EINVAL;
   int nparts = 1;
   const bool reg_form = training && owner_form(S, C, B) && vec_ok(S, {sB}, {x}) && (int64_t)B * S <= 16384;
   // a split-K convolution left the partial sums of x pending (crn_splitk_defer): the register kernel adds them up
@@ -900,6 +902,7 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
                        size_t ws_bytes, crnStream stream, const BnHead* head) {
   hipStream_t st = (hipStream_t)stream;
   if (B < 1 || C < 1 || S < 1 || B > 64) return CRN_EINVAL;
+  if (!x || !dy || !gamma || !scale || !shift || !saved || !dx || !dgamma || !dbeta) return CRN_EINVAL;
   const bool v = vec_ok(S, {sB_x, sB_dy, sB_dx}, {x, dy, dx});
   // The register-resident owner kernel keeps 16 float4 of x and of dy per thread when a channel has up to 16384 elements: 359
   // registers, i.e. a workgroup that only fits on a CU with NO wave of a weight-gradient kernel (206-250 registers x 2 waves per
@@ -1031,13 +1034,16 @@ extern "C" int crn_batch_renorm_bwd_apply(const float* x, int64_t sB_x, const fl
   CRN_ENTRY(stream);
   hipStream_t st = (hipStream_t)stream;
   if (B < 1 || C < 1 || S < 1 || B > 64 || nparts < 1 || !ws) return CRN_EINVAL;
+  if (!x || !dy || !gamma || !scale || !shift || !saved || !dx || !dgamma || !dbeta) return CRN_EINVAL;
   if (ws_bytes < (size_t)C * nparts * 2 * sizeof(double)) return CRN_ENOMEM;
-  { const int rcf = crn_splitk_flush(st); if (rcf != CRN_OK) return rcf; }
   const int ns = nsplit_for(S, C, B);
-  dim3 grid(ns, C, B);
   // deterministic mode: sum(dx) by the ordered two-level reduction over dx afterwards (as in crn_batch_renorm_bwd); it re-uses
-  // `ws` once the apply kernel has read the partial sums
+  // `ws` once the apply kernel has read the partial sums -- with few parts given and many slices of its own that second use
+  // is the larger one, and it is checked here, before anything is launched
   float* const dsum_det = (dsum && ndsum > 0 && crn_deterministic()) ? dsum : nullptr;
+  if (dsum_det && ws_bytes < (size_t)ndsum * ns * B * sizeof(double)) return CRN_ENOMEM;
+  { const int rcf = crn_splitk_flush(st); if (rcf != CRN_OK) return rcf; }
+  dim3 grid(ns, C, B);
   if (dsum_det) dsum = nullptr;
   if (vec_ok(S, {sB_x, sB_dy, sB_dx}, {x, dy, dx}))
     hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
@@ -1050,7 +1056,6 @@ extern "C" int crn_batch_renorm_bwd_apply(const float* x, int64_t sB_x, const fl
   CRN_CHECK_LAUNCH();
   if (dsum_det) {
     const int nparts2 = ns * B;
-    if (ws_bytes < (size_t)ndsum * nparts2 * sizeof(double)) return CRN_ENOMEM;
     dim3 gridb(ns, ndsum, B);
     if (vec_ok(S, {sB_dx}, {dx}))
       hipLaunchKernelGGL(bias_grad_partial_kernel<true>, gridb, dim3(kThreads), 0, st, dx, S, sB_dx, ws);

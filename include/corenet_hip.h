@@ -237,7 +237,10 @@ int crn_bias_grad(const float* dy, int B, int C, int64_t S, int64_t sB, float* d
  * train: batch mean / biased var -> r,d clamps from num_batches_tracked,
  * running-stat update (Q3,Q4); writes per-channel
  *   scale = gamma*r/sigma_b, shift = beta + gamma*(d - mu*r/sigma_b)
- * and saves mu, 1/sigma_b, r, d for the backward.  eval: running stats.          */
+ * and saves mu, 1/sigma_b, r, d for the backward.  eval: running stats (saved, running statistics and the workspace are
+ * not touched).  B <= 64.  Every argument is checked before anything is launched or written: CRN_EINVAL for B > 64 or a
+ * NULL tensor (num_batches_tracked and saved may be NULL in eval mode only), CRN_ENOMEM for a workspace smaller than
+ * crn_batch_renorm_workspace_bytes(C) needs for this shape -- the same holds for crn_batch_renorm_bwd below.          */
 int crn_batch_renorm_stats(const float* x, int B, int C, int64_t S, int64_t sB, int pre_relu,
                            const float* gamma, const float* beta,
                            float* running_mean, float* running_var,
@@ -288,7 +291,9 @@ int crn_batch_renorm_bwd(const float* x, int64_t sB_x, const float* dy, int64_t 
 /* The second pass of crn_batch_renorm_bwd alone: `workspace` already holds the per-channel partial sums
  * [C][nparts][2] (sum g, sum g*xn) written by crn_conv_fwd_bf3_slabs_bnbwd (fuse->nparts > 0) on the same stream.
  * post_relu must be 0 (the fused sums do not mask).  Same dx / dgamma / dbeta / dsum as crn_batch_renorm_bwd up to the
- * summation order of the two sums.                                                                                */
+ * summation order of the two sums.  In deterministic mode (crn_set_deterministic) with dsum the workspace is used a second
+ * time, for ndsum * (slices * B) doubles of the ordered sum over dx: CRN_ENOMEM if it is too small for either use, before
+ * anything is launched.                                                                                            */
 int crn_batch_renorm_bwd_apply(const float* x, int64_t sB_x, const float* dy, int64_t sB_dy,
                                int B, int C, int64_t S, int pre_relu,
                                const float* gamma, const float* scale, const float* shift,

@@ -218,17 +218,22 @@ class EmuBackend:
     else: db.copy_(v)
 
   # -- BatchRenorm --------------------------------------------------------------
-  def bn_stats(self, x, B, Cn, S, sB, pre_relu, gamma, beta, rmean, rvar, nbt, eps, momentum,
-               training, scale, shift, saved):
-    if not training:
-      rstd = 1.0 / (rvar + eps).sqrt()
-      scale.copy_(gamma * rstd); shift.copy_(beta - gamma * rmean * rstd)
-      return
-    v = t.as_strided(x, (B, Cn, S), (sB, S, 1), x.storage_offset())
-    if pre_relu: v = v.relu()
-    vd = v.double()
-    mean = vd.mean((0, 2)); var = (vd * vd).mean((0, 2)) - mean * mean
-    b_mean, b_var = mean.to(x.dtype), var.clamp(min=0).to(x.dtype)
+  def set_deterministic(self, on=True):
+    pass                                       # the emulator's sums are ordered already
+
+  def _bn_ws(self, Cn, device=None):
+    """The BatchRenorm workspace (HipBackend._bn_ws): [Cn][4096 parts][2] doubles as bytes, and its size."""
+    n = Cn * 64 * 64 * 2 * 8
+    w = getattr(self, "_bn_ws_buf", None)
+    if w is None or w.numel() < n:
+      w = self._bn_ws_buf = t.zeros(n, dtype=t.uint8)
+    return w, n
+
+  @staticmethod
+  def _bn_finalize_sums(s1, s2, count, Cn, dtype, gamma, beta, rmean, rvar, nbt, eps, momentum, scale, shift, saved):
+    """bn_finalize_channel of csrc/batch_renorm.hip: float64 sums -> float32 statistics and everything derived from them."""
+    mean = s1 / count; var = s2 / count - mean * mean
+    b_mean, b_var = mean.to(dtype), var.clamp(min=0).to(dtype)
     b_std = (b_var + eps).sqrt(); run_std = (rvar + eps).sqrt()
     nt = nbt.reshape(())          # float32 schedule arithmetic, as batch_renorm.py:41-42
     d_max = float((5.0 * (nt - 5000) / (25000 - 5000)).clamp(0.0, 5.0))
@@ -240,6 +245,42 @@ class EmuBackend:
     saved.view(4, Cn).copy_(t.stack([b_mean, rstd, r, d]))
     rvar += momentum * (b_var * Cn / (Cn - 1) - rvar)
     rmean += momentum * (b_mean - rmean)
+
+  def bn_stats(self, x, B, Cn, S, sB, pre_relu, gamma, beta, rmean, rvar, nbt, eps, momentum,
+               training, scale, shift, saved):
+    if not training:
+      rstd = 1.0 / (rvar + eps).sqrt()
+      scale.copy_(gamma * rstd); shift.copy_(beta - gamma * rmean * rstd)
+      return
+    v = t.as_strided(x, (B, Cn, S), (sB, S, 1), x.storage_offset())
+    if pre_relu: v = v.relu()
+    vd = v.double()
+    self._bn_finalize_sums(vd.sum((0, 2)), (vd * vd).sum((0, 2)), float(B * S), Cn, x.dtype, gamma, beta, rmean, rvar, nbt,
+                           eps, momentum, scale, shift, saved)
+
+  def bn_finalize(self, parts, Cn, count, gamma, beta, rmean, rvar, nbt, eps, momentum, scale, shift, saved):
+    """crn_batch_renorm_finalize: the partial sums [Cn][parts][2] (float64) at the head of the BatchRenorm workspace."""
+    ws, _ = self._bn_ws(Cn)
+    p = ws[:Cn * parts * 16].view(t.float64).view(Cn, parts, 2)
+    self._bn_finalize_sums(p[:, :, 0].sum(1), p[:, :, 1].sum(1), float(count), Cn, scale.dtype, gamma, beta, rmean, rvar, nbt,
+                           eps, momentum, scale, shift, saved)
+
+  def bn_stats_tail(self, x, B, Cn, S, sB, gamma, beta, rmean, rvar, nbt, eps, momentum, training, scale, shift, saved,
+                    r, rscale, rshift, sB_r, y_pre, sB_pre, y, sB_y, relu, y2=None, W=0):
+    self.bn_stats(x, B, Cn, S, sB, False, gamma, beta, rmean, rvar, nbt, eps, momentum, training, scale, shift, saved)
+    self.affine_add_relu(x, scale, shift, r, rscale, rshift, B, Cn, S, sB, sB_r, y_pre, sB_pre, y, sB_y, relu)
+    if y2 is not None:
+      yv = t.as_strided(y, (B, Cn, S // W, W), (sB_y, S, W, 1), y.storage_offset())
+      y2.view(B, Cn, (S // W + 1) // 2, (W + 1) // 2).copy_(yv[:, :, ::2, ::2])
+
+  def bn_bwd_head(self, x, sB_x, dy, sB_dy, g, sB_g, act, sB_act, g2, sB_g2, B, Cn, S, gamma, scale, shift, saved,
+                  dx, sB_dx, dgamma, dbeta, accumulate=False, dsum=None, ndsum=0, g_compact=None, W=0):
+    if g_compact is not None:
+      gv = t.as_strided(g, (B, Cn, S // W, W), (sB_g, S, W, 1), g.storage_offset())
+      gv.zero_(); gv[:, :, ::2, ::2] = g_compact
+    self.relu_bwd_add(g, act, g2, B, Cn, S, sB_g, sB_act, sB_g2, dy, sB_dy)
+    self.bn_bwd(x, sB_x, dy, sB_dy, B, Cn, S, False, False, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta,
+                accumulate, dsum, ndsum)
 
   def bn_bwd(self, x, sB_x, dy, sB_dy, B, Cn, S, pre_relu, post_relu, gamma, scale, shift, saved,
              dx, sB_dx, dgamma, dbeta, accumulate=False, dsum=None, ndsum=0):
