@@ -5,6 +5,7 @@
 #include "crn_common.h"
 #include <cstdlib>
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -34,6 +35,13 @@ __device__ __forceinline__ void for_slice(Slice sl, F4 f4, F1 f1) {
 }
 
 // ---- statistics -------------------------------------------------------------
+// One element into the fp64 sums of a channel: sum(x'), sum(x'^2) with x' = relu(x) under pre_relu.
+__device__ __forceinline__ void bn_acc(float v, int pre_relu, double& s1, double& s2) {
+  if (pre_relu) v = fmaxf(v, 0.f);
+  s1 += (double)v;
+  s2 += (double)v * (double)v;
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void bn_partial_kernel(const float* x, int64_t S, int64_t sB,
                                                                int pre_relu, double* ws) {
@@ -41,11 +49,7 @@ __global__ __launch_bounds__(kThreads) void bn_partial_kernel(const float* x, in
   const int c = blockIdx.y, b = blockIdx.z;
   const float* p = x + (int64_t)b * sB + (int64_t)c * S;
   double s1 = 0.0, s2 = 0.0;
-  auto one = [&](float v) {
-    if (pre_relu) v = fmaxf(v, 0.f);
-    s1 += (double)v;
-    s2 += (double)v * (double)v;
-  };
+  auto one = [&](float v) { bn_acc(v, pre_relu, s1, s2); };
   for_slice<VEC>(block_slice(S),
                  [&](int64_t s) { const f32x4 v = *reinterpret_cast<const f32x4*>(p + s);
                                   one(v.x); one(v.y); one(v.z); one(v.w); },
@@ -68,10 +72,9 @@ __device__ __forceinline__ BnChannelIn bn_channel_in(int c, const float* gamma, 
                                                      const int64_t* nbt) {
   return BnChannelIn{gamma[c], beta[c], running_mean[c], running_var[c], (float)nbt[0]};
 }
-__device__ __forceinline__ void bn_finalize_channel_in(int c, int C, double s1, double s2, double count,
-                                                       const BnChannelIn& in, float* running_mean, float* running_var,
-                                                       float eps, float momentum, float* scale, float* shift,
-                                                       float* saved) {
+__device__ __forceinline__ void bn_finalize_channel(int c, int C, double s1, double s2, double count,
+                                                    const BnChannelIn& in, float* running_mean, float* running_var,
+                                                    float eps, float momentum, float* scale, float* shift, float* saved) {
   const float g = in.g, bt = in.bt;
   const double mean_d = s1 / count;
   double var_d = s2 / count - mean_d * mean_d;
@@ -79,6 +82,7 @@ __device__ __forceinline__ void bn_finalize_channel_in(int c, int C, double s1, 
   const float b_mean = (float)mean_d, b_var = (float)var_d;
   const float b_std = sqrtf(b_var + eps);
   const float run_std = sqrtf(in.rvar + eps);
+  // batch_renorm.py:41-42: schedules from num_batches_tracked (before the increment)
   const float nt = in.nt;
   const float d_max = fminf(fmaxf(5.0f * (nt - 5000.f) / (25000.f - 5000.f), 0.f), 5.f);
   const float r_max = 1.0f + fminf(fmaxf(2.0f * (nt - 5000.f) / (40000.f - 5000.f), 0.f), 2.f);
@@ -90,38 +94,10 @@ __device__ __forceinline__ void bn_finalize_channel_in(int c, int C, double s1, 
   scale[c] = g * r * rstd;
   shift[c] = bt + g * (d - b_mean * r * rstd);
   saved[c] = b_mean; saved[C + c] = rstd; saved[2 * C + c] = r; saved[3 * C + c] = d;
+  // batch_renorm.py:54-56 (SURVEY Q4: the "unbiased" factor uses C = channel count)
   const float unbiased = b_var * (float)C / (float)(C - 1);
   running_var[c] = in.rvar + momentum * (unbiased - in.rvar);
   running_mean[c] = in.rmean + momentum * (b_mean - in.rmean);
-}
-
-__device__ __forceinline__ void bn_finalize_channel(int c, int C, double s1, double s2, double count,
-                                                    const float* gamma, const float* beta, float* running_mean,
-                                                    float* running_var, const int64_t* nbt, float eps,
-                                                    float momentum, float* scale, float* shift, float* saved) {
-  const float g = gamma[c], bt = beta[c];
-  const double mean_d = s1 / count;
-  double var_d = s2 / count - mean_d * mean_d;
-  if (var_d < 0.0) var_d = 0.0;
-  const float b_mean = (float)mean_d, b_var = (float)var_d;
-  const float b_std = sqrtf(b_var + eps);
-  const float run_std = sqrtf(running_var[c] + eps);
-  // batch_renorm.py:41-42: schedules from num_batches_tracked (before the increment)
-  const float nt = (float)nbt[0];
-  const float d_max = fminf(fmaxf(5.0f * (nt - 5000.f) / (25000.f - 5000.f), 0.f), 5.f);
-  const float r_max = 1.0f + fminf(fmaxf(2.0f * (nt - 5000.f) / (40000.f - 5000.f), 0.f), 2.f);
-  float r = b_std / run_std;
-  r = fminf(fmaxf(r, 1.0f / r_max), r_max);
-  float d = (b_mean - running_mean[c]) / run_std;
-  d = fminf(fmaxf(d, -d_max), d_max);
-  const float rstd = 1.0f / b_std;
-  scale[c] = g * r * rstd;
-  shift[c] = bt + g * (d - b_mean * r * rstd);
-  saved[c] = b_mean; saved[C + c] = rstd; saved[2 * C + c] = r; saved[3 * C + c] = d;
-  // batch_renorm.py:54-56 (SURVEY Q4: the "unbiased" factor uses C = channel count)
-  const float unbiased = b_var * (float)C / (float)(C - 1);
-  running_var[c] += momentum * (unbiased - running_var[c]);
-  running_mean[c] += momentum * (b_mean - running_mean[c]);
 }
 
 __global__ void bn_finalize_kernel(const double* ws, int nparts, int C, double count,
@@ -145,7 +121,7 @@ __global__ void bn_finalize_kernel(const double* ws, int nparts, int C, double c
   for (int i = lane; i < nparts; i += 64) { s1 += ws[((int64_t)c * nparts + i) * 2]; s2 += ws[((int64_t)c * nparts + i) * 2 + 1]; }
   s1 = crn_wave_sum(s1); s2 = crn_wave_sum(s2);
   if (lane == 0)
-    bn_finalize_channel_in(c, C, s1, s2, count, cin, running_mean, running_var, eps, momentum, scale, shift, saved);
+    bn_finalize_channel(c, C, s1, s2, count, cin, running_mean, running_var, eps, momentum, scale, shift, saved);
 }
 
 // The same for MANY parts per channel (the partial sums a convolution's workgroups leave: 2048 for decoder stage_6.c1): one
@@ -166,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void bn_finalize_wide_kernel(const double
   double t1, t2;
   crn_block_sum2(s1, s2, red, t1, t2);
   if (threadIdx.x == 0)
-    bn_finalize_channel_in(c, C, t1, t2, count, cin, running_mean, running_var, eps, momentum, scale, shift, saved);
+    bn_finalize_channel(c, C, t1, t2, count, cin, running_mean, running_var, eps, momentum, scale, shift, saved);
 }
 
 // Eval mode: scale/shift of EVERY BatchRenorm of the model from the running statistics in one launch
@@ -193,12 +169,9 @@ __global__ __launch_bounds__(kThreads) void bn_owner_stats_kernel(
     float* shift, float* saved) {
   __shared__ double red[kThreads / 64];
   const int c = blockIdx.x;
+  const BnChannelIn cin = bn_channel_in(c, gamma, beta, running_mean, running_var, nbt);
   double s1 = 0.0, s2 = 0.0;
-  auto one = [&](float v) {
-    if (pre_relu) v = fmaxf(v, 0.f);
-    s1 += (double)v;
-    s2 += (double)v * (double)v;
-  };
+  auto one = [&](float v) { bn_acc(v, pre_relu, s1, s2); };
   Slice all; all.s0 = 0; all.s1 = S;
   for (int b = 0; b < B; ++b) {
     const float* p = x + (int64_t)b * sB + (int64_t)c * S;
@@ -210,8 +183,29 @@ __global__ __launch_bounds__(kThreads) void bn_owner_stats_kernel(
   const double t1 = crn_block_sum(s1, red);
   const double t2 = crn_block_sum(s2, red);
   if (threadIdx.x == 0)
-    bn_finalize_channel(c, C, t1, t2, (double)B * (double)S, gamma, beta, running_mean, running_var, nbt, eps,
-                        momentum, scale, shift, saved);
+    bn_finalize_channel(c, C, t1, t2, (double)B * (double)S, cin, running_mean, running_var, eps, momentum, scale, shift,
+                        saved);
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Sum of the `splits` partial results ([split][b][c][pos], dense) a split-K convolution left in the scratch, for float4 s4 of
+// (b, c): split 0 first, the order of the reduction kernel.
+__device__ __forceinline__ f32x4 bn_splitk_sum(const float* part, int splits, int B, int C, int S4, int b, int c, int s4) {
+  const f32x4* pp = reinterpret_cast<const f32x4*>(part) + ((int64_t)b * C + c) * S4 + s4;
+  const int64_t slab4 = (int64_t)B * C * S4;
+  f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int sp = 0; sp < splits; ++sp) sum += pp[sp * slab4];
+  return sum;
+}
+
+// Where float4 s4 of channel c's full plane (rows of width W, a multiple of 4) lands in the stride-2 compaction [c][H2][W2] of
+// the tensor: `off` = the offset of the float2 that holds its elements 0 and 2 (even columns); false on an odd row (nothing of it is
+// kept).
+__device__ __forceinline__ bool bn_stride2_offset(int c, int s4, int W, int W2, int H2, int64_t& off) {
+  const int s = s4 * 4, row = s / W, col = s - row * W;
+  off = ((int64_t)c * H2 + (row >> 1)) * W2 + (col >> 1);
+  return !(row & 1);
 }
 
 // Register-resident owner kernels: when all of (B, S) of a channel fits in NV float4 per thread (B*S <= 1024*NV), every
@@ -259,31 +253,20 @@ __global__ __launch_bounds__(kThreads) void bn_owner_stats_reg_kernel(
     if (part == nullptr) {
       v[k] = e < total4 ? *xp : (f32x4){0.f, 0.f, 0.f, 0.f};
     } else {
-      f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (e < total4) {
-        const f32x4* pp = reinterpret_cast<const f32x4*>(part) + ((int64_t)b * C + c) * S4 + s4;
-        const int64_t slab4 = (int64_t)B * C * S4;
-        for (int sp = 0; sp < splits; ++sp) sum += pp[sp * slab4];
-        *xp = sum;
-      }
-      v[k] = sum;
+      v[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (e < total4) *xp = v[k] = bn_splitk_sum(part, splits, B, C, S4, b, c, s4);
     }
   }
   double s1 = 0.0, s2 = 0.0;
 #pragma unroll
   for (int k = 0; k < NV; ++k)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float t = v[k][i];
-      if (pre_relu) t = fmaxf(t, 0.f);
-      s1 += (double)t;
-      s2 += (double)t * (double)t;
-    }
+    for (int i = 0; i < 4; ++i) bn_acc(v[k][i], pre_relu, s1, s2);
   double t1, t2;
   crn_block_sum2(s1, s2, red, t1, t2);
   if (threadIdx.x == 0) {
-    bn_finalize_channel_in(c, C, t1, t2, (double)B * (double)S4 * 4.0, cin, running_mean, running_var, eps, momentum,
-                           scale, shift, saved);
+    bn_finalize_channel(c, C, t1, t2, (double)B * (double)S4 * 4.0, cin, running_mean, running_var, eps, momentum,
+                        scale, shift, saved);
     if (TAIL) { tail_affine[0] = scale[c]; tail_affine[1] = shift[c]; }     // (the fp32 values the un-fused tail would load)
   }
   if (TAIL) {
@@ -306,18 +289,60 @@ __global__ __launch_bounds__(kThreads) void bn_owner_stats_reg_kernel(
             for (int i = 0; i < 4; ++i) q[i] = fmaxf(q[i], 0.f);
           }
           *reinterpret_cast<f32x4*>(tail.y + (int64_t)b * tail.sBy + o) = q;
-          if (tail.y2) {
-            const int s = s4 * 4, row = s / tail.W, col = s - row * tail.W;
-            if (!(row & 1)) {
-              typedef float f32x2 __attribute__((ext_vector_type(2)));
-              float* d2 = tail.y2 + (int64_t)b * tail.sBy2 + ((int64_t)c * tail.H2 + (row >> 1)) * tail.W2 + (col >> 1);
-              *reinterpret_cast<f32x2*>(d2) = (f32x2){q[0], q[2]};
-            }
-          }
+          int64_t o2;
+          if (tail.y2 && bn_stride2_offset(c, s4, tail.W, tail.W2, tail.H2, o2))
+            *reinterpret_cast<f32x2*>(tail.y2 + (int64_t)b * tail.sBy2 + o2) = (f32x2){q[0], q[2]};
         }
       }
     }
   }
+}
+
+// ---- backward: the arithmetic every backward kernel shares ------------------------
+// Per-channel values of the forward pass that the per-element terms need.
+struct BnBwdChannel { float sc, sh, mu, rstd; };
+__device__ __forceinline__ BnBwdChannel bn_bwd_channel(int c, int C, const float* scale, const float* shift, const float* saved) {
+  return BnBwdChannel{scale[c], shift[c], saved[c], saved[C + c]};
+}
+
+// Reduction term of one element: g masked where the post-ReLU output is not positive, into sum(g) and sum(g * xhat).
+__device__ __forceinline__ void bn_bwd_acc(float x, float g, int pre_relu, int post_relu, BnBwdChannel ch, double& s1, double& s2) {
+  if (pre_relu) x = fmaxf(x, 0.f);
+  if (post_relu && !(x * ch.sc + ch.sh > 0.f)) g = 0.f;
+  s1 += (double)g;
+  s2 += (double)g * (double)((x - ch.mu) * ch.rstd);
+}
+
+// dx of one element: k = gamma * r * rstd, mg / mgx = the channel's mean(g) / mean(g * xhat); zero where the pre-ReLU input is <= 0.
+__device__ __forceinline__ float bn_bwd_dx(float xr, float g, int pre_relu, int post_relu, BnBwdChannel ch, float k, float mg, float mgx) {
+  const float x = pre_relu ? fmaxf(xr, 0.f) : xr;
+  if (post_relu && !(x * ch.sc + ch.sh > 0.f)) g = 0.f;
+  float o = k * (g - mg - (x - ch.mu) * ch.rstd * mgx);
+  if (pre_relu && !(xr > 0.f)) o = 0.f;
+  return o;
+}
+
+// Closing of a channel's reduction (one thread): the two means go to sm[0], sm[1] for the apply pass of the workgroup, and
+// the gradients of gamma and beta come back (r, d = the saved renorm factors).
+struct BnAffineGrad { float dg, db; };
+__device__ __forceinline__ BnAffineGrad bn_bwd_close(double s1, double s2, double count, float r, float d, float* sm) {
+  sm[0] = (float)(s1 / count); sm[1] = (float)(s2 / count);
+  return BnAffineGrad{(float)(r * s2 + d * s1), (float)s1};
+}
+__device__ __forceinline__ void bn_bwd_store_grad(BnAffineGrad g, int c, float* dgamma, float* dbeta, int accumulate) {
+  if (accumulate) { dgamma[c] += g.dg; dbeta[c] += g.db; } else { dgamma[c] = g.dg; dbeta[c] = g.db; }
+}
+
+// fp32 sum of one value per thread over the workgroup, the waves in order (valid in thread 0): a channel's share of sum(dx),
+// which the caller stores or adds atomically to dsum.  redf: kThreads / 64 floats.
+__device__ __forceinline__ float bn_block_sum_f32(float v, float* redf) {
+  const float w = crn_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) redf[threadIdx.x >> 6] = w;
+  __syncthreads();
+  float tsum = 0.f;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < kThreads / 64; ++i) tsum += redf[i];
+  return tsum;
 }
 
 // part != nullptr: dy is the output of a split-K convolution (a data gradient) still in `splits` partial sums in the
@@ -345,7 +370,7 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_reg_kernel(
   if (HEAD) crn_kernargs_now(head.g, head.sBg, head.act, head.sBact, head.g2, head.sBg2, head.gc, head.sBgc, head.W, head.W2, head.H2);
   const int c = blockIdx.x, total4 = B * S4;
   // every per-channel scalar of the kernel is loaded here, next to x and dy: one round trip to memory, not three
-  const float sc = scale[c], sh = shift[c], mu = saved[c], rstd = saved[C + c];
+  const BnBwdChannel ch = bn_bwd_channel(c, C, scale, shift, saved);
   const float rr = saved[2 * C + c], dd = saved[3 * C + c], gam = gamma[c];
   float dg0 = 0.f, db0 = 0.f;
   if (accumulate && threadIdx.x == 0) { dg0 = dgamma[c]; db0 = dbeta[c]; }
@@ -361,10 +386,9 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_reg_kernel(
       const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
       f32x4 g = z;
       if (ok && head.gc) {
-        const int s = s4 * 4, row = s / head.W, col = s - row * head.W;
-        if (!(row & 1)) {
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          const f32x2 v = *reinterpret_cast<const f32x2*>(head.gc + (int64_t)b * head.sBgc + ((int64_t)c * head.H2 + (row >> 1)) * head.W2 + (col >> 1));
+        int64_t o2;
+        if (bn_stride2_offset(c, s4, head.W, head.W2, head.H2, o2)) {
+          const f32x2 v = *reinterpret_cast<const f32x2*>(head.gc + (int64_t)b * head.sBgc + o2);
           g[0] = v[0]; g[2] = v[1];
         }
       } else if (ok) {
@@ -380,37 +404,23 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_reg_kernel(
     } else if (part == nullptr) {
       gv[k] = ok ? *reinterpret_cast<const f32x4*>(dy + (int64_t)b * sBdy + o) : (f32x4){0.f, 0.f, 0.f, 0.f};
     } else {
-      f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (ok) {
-        const f32x4* pp = reinterpret_cast<const f32x4*>(part) + ((int64_t)b * C + c) * S4 + s4;
-        const int64_t slab4 = (int64_t)B * C * S4;
-        for (int sp = 0; sp < splits; ++sp) sum += pp[sp * slab4];
-      }
-      gv[k] = sum;
+      gv[k] = ok ? bn_splitk_sum(part, splits, B, C, S4, b, c, s4) : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
   }
   double s1 = 0.0, s2 = 0.0;
 #pragma unroll
   for (int k = 0; k < NV; ++k)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float a = xv[k][i], g = gv[k][i];
-      if (pre_relu) a = fmaxf(a, 0.f);
-      if (post_relu && !(a * sc + sh > 0.f)) g = 0.f;
-      s1 += (double)g;
-      s2 += (double)g * (double)((a - mu) * rstd);
-    }
+    for (int i = 0; i < 4; ++i) bn_bwd_acc(xv[k][i], gv[k][i], pre_relu, post_relu, ch, s1, s2);
   double t1, t2;
   crn_block_sum2(s1, s2, red, t1, t2);
   if (threadIdx.x == 0) {
-    const double count = (double)B * (double)S4 * 4.0;
-    sm[0] = (float)(t1 / count); sm[1] = (float)(t2 / count);
-    const float dg = (float)(rr * t2 + dd * t1), db = (float)t1;
-    dgamma[c] = dg0 + dg; dbeta[c] = db0 + db;
+    const BnAffineGrad ag = bn_bwd_close(t1, t2, (double)B * (double)S4 * 4.0, rr, dd, sm);
+    dgamma[c] = dg0 + ag.dg; dbeta[c] = db0 + ag.db;       // (dg0, db0 were loaded with everything else: not bn_bwd_store_grad)
   }
   __syncthreads();
   const float mg = sm[0], mgx = sm[1];
-  const float kf = gam * rr * rstd;
+  const float kf = gam * rr * ch.rstd;
   float lsum = 0.f;
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
@@ -420,27 +430,15 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_reg_kernel(
       f32x4 o;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float xr = xv[k][i];
-        const float a = pre_relu ? fmaxf(xr, 0.f) : xr;
-        float g = gv[k][i];
-        if (post_relu && !(a * sc + sh > 0.f)) g = 0.f;
-        float r = kf * (g - mg - (a - mu) * rstd * mgx);
-        if (pre_relu && !(xr > 0.f)) r = 0.f;
-        lsum += r;
-        o[i] = r;
+        o[i] = bn_bwd_dx(xv[k][i], gv[k][i], pre_relu, post_relu, ch, kf, mg, mgx);
+        lsum += o[i];
       }
       *reinterpret_cast<f32x4*>(dx + (int64_t)b * sBdx + ((int64_t)c * S4 + s4) * 4) = o;
     }
   }
   if (dsum && c < ndsum) {       // bias gradient of the convolution that produced x: sum of dx
-    const float w = crn_wave_sum(lsum);
-    if ((threadIdx.x & 63) == 0) redf[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float tsum = 0.f;
-      for (int i = 0; i < kThreads / 64; ++i) tsum += redf[i];
-      dsum[c] = tsum;
-    }
+    const float tsum = bn_block_sum_f32(lsum, redf);
+    if (threadIdx.x == 0) dsum[c] = tsum;
   }
 }
 
@@ -456,14 +454,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_partial_kernel(
   if (dsum && c < ndsum && blockIdx.x == 0 && b == 0 && threadIdx.x == 0) dsum[c] = 0.f;
   const float* px = x + (int64_t)b * sBx + (int64_t)c * S;
   const float* pg = dy + (int64_t)b * sBdy + (int64_t)c * S;
-  const float sc = scale[c], sh = shift[c], mu = saved[c], rstd = saved[C + c];
+  const BnBwdChannel ch = bn_bwd_channel(c, C, scale, shift, saved);
   double s1 = 0.0, s2 = 0.0;
-  auto one = [&](float xv, float gv) {
-    if (pre_relu) xv = fmaxf(xv, 0.f);
-    if (post_relu && !(xv * sc + sh > 0.f)) gv = 0.f;
-    s1 += (double)gv;
-    s2 += (double)gv * (double)((xv - mu) * rstd);
-  };
+  auto one = [&](float xv, float gv) { bn_bwd_acc(xv, gv, pre_relu, post_relu, ch, s1, s2); };
   for_slice<VEC>(block_slice(S),
                  [&](int64_t s) { const f32x4 a = *reinterpret_cast<const f32x4*>(px + s);
                                   const f32x4 g = *reinterpret_cast<const f32x4*>(pg + s);
@@ -491,19 +484,15 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(
   // the partial sums of the channel are added up by the whole workgroup (one thread walking up to 4096 of them kept
   // the other 255 waiting at the barrier for several memory latencies), and the per-channel scalars used after the
   // barrier are loaded before it
-  const float sc = scale[c], sh = shift[c], mu = saved[c], rstd = saved[C + c];
-  const float k = gamma[c] * saved[2 * C + c] * rstd;
+  const BnBwdChannel ch = bn_bwd_channel(c, C, scale, shift, saved);
+  const float k = gamma[c] * saved[2 * C + c] * ch.rstd;
   double p1 = 0.0, p2 = 0.0;
   for (int i = threadIdx.x; i < nparts; i += kThreads) { p1 += ws[((int64_t)c * nparts + i) * 2]; p2 += ws[((int64_t)c * nparts + i) * 2 + 1]; }
   double s1, s2;
   crn_block_sum2(p1, p2, redd, s1, s2);
   if (threadIdx.x == 0) {
-    sm[0] = (float)(s1 / count); sm[1] = (float)(s2 / count);
-    if (blockIdx.x == 0 && b == 0) {
-      const float r = saved[2 * C + c], d = saved[3 * C + c];
-      const float dg = (float)(r * s2 + d * s1), db = (float)s1;
-      if (accumulate) { dgamma[c] += dg; dbeta[c] += db; } else { dgamma[c] = dg; dbeta[c] = db; }
-    }
+    const BnAffineGrad ag = bn_bwd_close(s1, s2, count, saved[2 * C + c], saved[3 * C + c], sm);
+    if (blockIdx.x == 0 && b == 0) bn_bwd_store_grad(ag, c, dgamma, dbeta, accumulate);
   }
   __syncthreads();
   const float mg = sm[0], mgx = sm[1];
@@ -512,10 +501,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(
   float* po = dx + (int64_t)b * sBdx + (int64_t)c * S;
   float lsum = 0.f;
   auto one = [&](float xr, float gv) -> float {
-    const float xv = pre_relu ? fmaxf(xr, 0.f) : xr;
-    if (post_relu && !(xv * sc + sh > 0.f)) gv = 0.f;
-    float o = k * (gv - mg - (xv - mu) * rstd * mgx);
-    if (pre_relu && !(xr > 0.f)) o = 0.f;
+    const float o = bn_bwd_dx(xr, gv, pre_relu, post_relu, ch, k, mg, mgx);
     lsum += o;
     return o;
   };
@@ -527,14 +513,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(
                                   *reinterpret_cast<f32x4*>(po + s) = o; },
                  [&](int64_t s) { po[s] = one(px[s], pg[s]); });
   if (dsum && c < ndsum) {       // bias gradient of the convolution that produced x: sum of dx
-    const float w = crn_wave_sum(lsum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float tsum = 0.f;
-      for (int i = 0; i < kThreads / 64; ++i) tsum += red[i];
-      atomicAdd(dsum + c, tsum);
-    }
+    const float tsum = bn_block_sum_f32(lsum, red);
+    if (threadIdx.x == 0) atomicAdd(dsum + c, tsum);
   }
 }
 
@@ -548,15 +528,10 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_kernel(
   __shared__ float sm[2];
   __shared__ float redf[kThreads / 64];
   const int c = blockIdx.x;
-  const float sc = scale[c], sh = shift[c], mu = saved[c], rstd = saved[C + c];
+  const BnBwdChannel ch = bn_bwd_channel(c, C, scale, shift, saved);
   Slice all; all.s0 = 0; all.s1 = S;
   double s1 = 0.0, s2 = 0.0;
-  auto acc = [&](float xv, float gv) {
-    if (pre_relu) xv = fmaxf(xv, 0.f);
-    if (post_relu && !(xv * sc + sh > 0.f)) gv = 0.f;
-    s1 += (double)gv;
-    s2 += (double)gv * (double)((xv - mu) * rstd);
-  };
+  auto acc = [&](float xv, float gv) { bn_bwd_acc(xv, gv, pre_relu, post_relu, ch, s1, s2); };
   for (int b = 0; b < B; ++b) {
     const float* px = x + (int64_t)b * sBx + (int64_t)c * S;
     const float* pg = dy + (int64_t)b * sBdy + (int64_t)c * S;
@@ -568,22 +543,15 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_kernel(
   }
   const double t1 = crn_block_sum(s1, red);
   const double t2 = crn_block_sum(s2, red);
-  if (threadIdx.x == 0) {
-    const double count = (double)B * (double)S;
-    sm[0] = (float)(t1 / count); sm[1] = (float)(t2 / count);
-    const float r = saved[2 * C + c], d = saved[3 * C + c];
-    const float dg = (float)(r * t2 + d * t1), db = (float)t1;
-    if (accumulate) { dgamma[c] += dg; dbeta[c] += db; } else { dgamma[c] = dg; dbeta[c] = db; }
-  }
+  if (threadIdx.x == 0)
+    bn_bwd_store_grad(bn_bwd_close(t1, t2, (double)B * (double)S, saved[2 * C + c], saved[3 * C + c], sm), c, dgamma, dbeta,
+                      accumulate);
   __syncthreads();
   const float mg = sm[0], mgx = sm[1];
-  const float k = gamma[c] * saved[2 * C + c] * rstd;
+  const float k = gamma[c] * saved[2 * C + c] * ch.rstd;
   float lsum = 0.f;
   auto one = [&](float xr, float gv) -> float {
-    const float xv = pre_relu ? fmaxf(xr, 0.f) : xr;
-    if (post_relu && !(xv * sc + sh > 0.f)) gv = 0.f;
-    float o = k * (gv - mg - (xv - mu) * rstd * mgx);
-    if (pre_relu && !(xr > 0.f)) o = 0.f;
+    const float o = bn_bwd_dx(xr, gv, pre_relu, post_relu, ch, k, mg, mgx);
     lsum += o;
     return o;
   };
@@ -600,14 +568,8 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_kernel(
                    [&](int64_t s) { po[s] = one(px[s], pg[s]); });
   }
   if (dsum && c < ndsum) {       // bias gradient of the convolution that produced x: sum of dx
-    const float w = crn_wave_sum(lsum);
-    if ((threadIdx.x & 63) == 0) redf[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float tsum = 0.f;
-      for (int i = 0; i < kThreads / 64; ++i) tsum += redf[i];
-      dsum[c] = tsum;
-    }
+    const float tsum = bn_block_sum_f32(lsum, redf);
+    if (threadIdx.x == 0) dsum[c] = tsum;
   }
 }
 
@@ -738,6 +700,51 @@ inline int nsplit_for(int64_t S, int C, int B) {
 
 constexpr int kMaxParts = 64 * 64;   // nsplit(<=64) * B(<=64)
 
+// The launch dispatchers: f gets the compile-time value as a std::integral_constant / std::bool_constant argument.
+// NV of the register kernels: the smallest of 1, 2, 4, 8, 16 float4 per thread that hold the B * S values of a channel.
+template <typename F>
+inline void with_nv(int64_t BS, F f) {
+  const int per = (int)crn_cdiv(BS / 4, kThreads);
+  if (per <= 1) f(std::integral_constant<int, 1>{}); else if (per <= 2) f(std::integral_constant<int, 2>{});
+  else if (per <= 4) f(std::integral_constant<int, 4>{}); else if (per <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+template <typename F>
+inline void with_bool(bool on, F f) {
+  if (on) f(std::true_type{}); else f(std::false_type{});
+}
+
+// A split-K convolution may have left the partial sums of its output pending (crn_splitk_defer).  If that output is `base`
+// ([B][C][S] dense, batch stride sB) and the launch about to be made is a register kernel on the same stream, the kernel adds
+// them up itself: *part / *splits say where they are.  A pending sum meant for anything else is flushed first.
+int take_or_flush_pending(const float* base, int64_t sB, int B, int C, int64_t S, hipStream_t st, bool reg_form,
+                          const float** part, int* splits) {
+  *part = nullptr; *splits = 0;
+  CrnSplitPending& pend = crn_splitk_pending();
+  if (!pend.active) return CRN_OK;
+  const crnView& py = pend.y;
+  if (reg_form && pend.stream == st && py.base == base && py.B == B && py.C == C && (int64_t)py.D * py.H * py.W == S && sB == (int64_t)C * S) {
+    *part = pend.scratch; *splits = pend.splits; pend.active = false;
+    return CRN_OK;
+  }
+  return crn_splitk_flush(st);
+}
+
+// out[c] (+)= sum of src[:, c, :] for c < n in an order that does not depend on how workgroups are scheduled: ns * B fp64
+// partial sums per channel into ws, then one wave per channel adds them up.
+int bias_grad_ordered(const float* src, int B, int n, int64_t S, int64_t sB, int ns, float* out, int accumulate, double* ws,
+                      size_t ws_bytes, hipStream_t st) {
+  const int nparts = ns * B;
+  if (ws_bytes < (size_t)n * nparts * sizeof(double)) return CRN_ENOMEM;
+  with_bool(vec_ok(S, {sB}, {src}), [&](auto vec) {
+    hipLaunchKernelGGL(bias_grad_partial_kernel<decltype(vec)::value>, dim3(ns, n, B), dim3(kThreads), 0, st, src, S, sB, ws);
+  });
+  CRN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(bias_grad_final_kernel, dim3(crn_cdiv(n, 4)), dim3(256), 0, st, ws, nparts, n, out, accumulate);
+  CRN_CHECK_LAUNCH();
+  return CRN_OK;
+}
+
 }  // namespace
 
 extern "C" size_t crn_batch_renorm_workspace_bytes(int C) {
@@ -758,48 +765,29 @@ static int bn_stats_impl(const float* x, int B, int C, int64_t S, int64_t sB, in
   int nparts = 1;
   const bool reg_form = training && owner_form(S, C, B) && vec_ok(S, {sB}, {x}) && (int64_t)B * S <= 16384;
   // a split-K convolution left the partial sums of x pending (crn_splitk_defer): the register kernel adds them up
-  const float* part = nullptr;
-  int psplits = 0;
-  {
-    CrnSplitPending& pend = crn_splitk_pending();
-    if (pend.active) {
-      const crnView& py = pend.y;
-      if (reg_form && pend.stream == st && py.base == x && py.B == B && py.C == C && (int64_t)py.D * py.H * py.W == S && sB == (int64_t)C * S) {
-        part = pend.scratch; psplits = pend.splits; pend.active = false;
-      } else {
-        const int rcf = crn_splitk_flush(st);
-        if (rcf != CRN_OK) return rcf;
-      }
-    }
-  }
+  const float* part;
+  int psplits;
+  const int rcp = take_or_flush_pending(x, sB, B, C, S, st, reg_form, &part, &psplits);
+  if (rcp != CRN_OK) return rcp;
   if (reg_form) {
-    const int per = (int)crn_cdiv((int64_t)B * S / 4, kThreads);       // float4 per thread
-#define CRN_BN_STATS_REG(NV)                                                                                      \
-  hipLaunchKernelGGL(bn_owner_stats_reg_kernel<NV>, dim3(C), dim3(kThreads), 0, st, const_cast<float*>(x), B, C, (int)(S / 4), sB, pre_relu, \
-                     gamma, beta, running_mean, running_var, nbt, eps, momentum, scale, shift, saved, part, psplits)
-#define CRN_BN_STATS_TAIL(NV)                                                                                     \
-  hipLaunchKernelGGL((bn_owner_stats_reg_kernel<NV, true>), dim3(C), dim3(kThreads), 0, st, const_cast<float*>(x), B, C, (int)(S / 4), sB, pre_relu, \
-                     gamma, beta, running_mean, running_var, nbt, eps, momentum, scale, shift, saved, part, psplits, *tail)
-    if (tail && vec_ok(S, {tail->r ? tail->sBr : 0, tail->y_pre ? tail->sBpre : 0, tail->y ? tail->sBy : 0},
-                       {tail->r, tail->y_pre, tail->y})) {
-      if (per <= 1) CRN_BN_STATS_TAIL(1); else if (per <= 2) CRN_BN_STATS_TAIL(2); else if (per <= 4) CRN_BN_STATS_TAIL(4);
-      else if (per <= 8) CRN_BN_STATS_TAIL(8); else CRN_BN_STATS_TAIL(16);
-      *tail_done = true;
-    } else
-    if (per <= 1) CRN_BN_STATS_REG(1); else if (per <= 2) CRN_BN_STATS_REG(2); else if (per <= 4) CRN_BN_STATS_REG(4);
-    else if (per <= 8) CRN_BN_STATS_REG(8); else CRN_BN_STATS_REG(16);
-#undef CRN_BN_STATS_REG
-#undef CRN_BN_STATS_TAIL
+    const bool with_tail = tail && vec_ok(S, {tail->r ? tail->sBr : 0, tail->y_pre ? tail->sBpre : 0, tail->y ? tail->sBy : 0},
+                                          {tail->r, tail->y_pre, tail->y});
+    with_nv((int64_t)B * S, [&](auto nv) {
+      with_bool(with_tail, [&](auto fused) {
+        hipLaunchKernelGGL((bn_owner_stats_reg_kernel<decltype(nv)::value, decltype(fused)::value>), dim3(C), dim3(kThreads), 0, st,
+                           const_cast<float*>(x), B, C, (int)(S / 4), sB, pre_relu, gamma, beta, running_mean, running_var, nbt,
+                           eps, momentum, scale, shift, saved, part, psplits, with_tail ? *tail : BnTail{});
+      });
+    });
+    if (with_tail) *tail_done = true;
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
   if (training && owner_form(S, C, B)) {
-    if (vec_ok(S, {sB}, {x}))
-      hipLaunchKernelGGL(bn_owner_stats_kernel<true>, dim3(C), dim3(kThreads), 0, st, x, B, C, S, sB, pre_relu, gamma,
-                         beta, running_mean, running_var, nbt, eps, momentum, scale, shift, saved);
-    else
-      hipLaunchKernelGGL(bn_owner_stats_kernel<false>, dim3(C), dim3(kThreads), 0, st, x, B, C, S, sB, pre_relu, gamma,
-                         beta, running_mean, running_var, nbt, eps, momentum, scale, shift, saved);
+    with_bool(vec_ok(S, {sB}, {x}), [&](auto vec) {
+      hipLaunchKernelGGL(bn_owner_stats_kernel<decltype(vec)::value>, dim3(C), dim3(kThreads), 0, st, x, B, C, S, sB, pre_relu,
+                         gamma, beta, running_mean, running_var, nbt, eps, momentum, scale, shift, saved);
+    });
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
@@ -808,10 +796,9 @@ static int bn_stats_impl(const float* x, int B, int C, int64_t S, int64_t sB, in
     nparts = ns * B;
     if (ws_bytes < (size_t)C * nparts * 2 * sizeof(double)) return CRN_ENOMEM;
     dim3 grid(ns, C, B);
-    if (vec_ok(S, {sB}, {x}))
-      hipLaunchKernelGGL(bn_partial_kernel<true>, grid, dim3(kThreads), 0, st, x, S, sB, pre_relu, ws);
-    else
-      hipLaunchKernelGGL(bn_partial_kernel<false>, grid, dim3(kThreads), 0, st, x, S, sB, pre_relu, ws);
+    with_bool(vec_ok(S, {sB}, {x}), [&](auto vec) {
+      hipLaunchKernelGGL(bn_partial_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, S, sB, pre_relu, ws);
+    });
     CRN_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(crn_cdiv(C, 4)), dim3(256), 0, st, ws, nparts, C,
@@ -927,14 +914,11 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
       head = &expanded;
     }
     if (reg_form && hv) {
-      const int per = (int)crn_cdiv((int64_t)B * S / 4, kThreads);
-#define CRN_BN_BWD_HEAD(NV)                                                                                         \
-  hipLaunchKernelGGL((bn_owner_bwd_reg_kernel<NV, true>), dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, B, (int)(S / 4), C, \
-                     pre_relu, post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum, \
-                     (const float*)nullptr, 0, *head)
-      if (per <= 1) CRN_BN_BWD_HEAD(1); else if (per <= 2) CRN_BN_BWD_HEAD(2); else if (per <= 4) CRN_BN_BWD_HEAD(4);
-      else if (per <= 8) CRN_BN_BWD_HEAD(8); else CRN_BN_BWD_HEAD(16);
-#undef CRN_BN_BWD_HEAD
+      with_nv((int64_t)B * S, [&](auto nv) {
+        hipLaunchKernelGGL((bn_owner_bwd_reg_kernel<decltype(nv)::value, true>), dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy,
+                           B, (int)(S / 4), C, pre_relu, post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta,
+                           accumulate, dsum, ndsum, (const float*)nullptr, 0, *head);
+      });
       CRN_CHECK_LAUNCH();
       return CRN_OK;
     }
@@ -942,39 +926,25 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
                                           const_cast<float*>(dy), sB_dy, stream);
     if (rch != CRN_OK) return rch;
   }
-  const float* part = nullptr;
-  int psplits = 0;
-  {
-    CrnSplitPending& pend = crn_splitk_pending();
-    if (pend.active) {
-      const crnView& py = pend.y;
-      if (reg_form && pend.stream == st && py.base == dy && py.B == B && py.C == C && (int64_t)py.D * py.H * py.W == S && sB_dy == (int64_t)C * S) {
-        part = pend.scratch; psplits = pend.splits; pend.active = false;
-      } else {
-        const int rcf = crn_splitk_flush(st);
-        if (rcf != CRN_OK) return rcf;
-      }
-    }
-  }
+  // a split-K convolution (a data gradient) left the partial sums of dy pending: the register kernel adds them up
+  const float* part;
+  int psplits;
+  const int rcp = take_or_flush_pending(dy, sB_dy, B, C, S, st, reg_form, &part, &psplits);
+  if (rcp != CRN_OK) return rcp;
   if (reg_form) {
-    const int per = (int)crn_cdiv((int64_t)B * S / 4, kThreads);       // float4 per thread (of x and of dy)
-#define CRN_BN_BWD_REG(NV)                                                                                          \
-  hipLaunchKernelGGL(bn_owner_bwd_reg_kernel<NV>, dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, B, (int)(S / 4), C, \
-                     pre_relu, post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum, \
-                     part, psplits)
-    if (per <= 1) CRN_BN_BWD_REG(1); else if (per <= 2) CRN_BN_BWD_REG(2); else if (per <= 4) CRN_BN_BWD_REG(4);
-    else if (per <= 8) CRN_BN_BWD_REG(8); else CRN_BN_BWD_REG(16);
-#undef CRN_BN_BWD_REG
+    with_nv((int64_t)B * S, [&](auto nv) {        // float4 per thread of x and of dy
+      hipLaunchKernelGGL(bn_owner_bwd_reg_kernel<decltype(nv)::value>, dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, B,
+                         (int)(S / 4), C, pre_relu, post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta, accumulate,
+                         dsum, ndsum, part, psplits);
+    });
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
   if (owner_ok) {
-    if (v)
-      hipLaunchKernelGGL(bn_owner_bwd_kernel<true>, dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, B, S, C, pre_relu,
-                         post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
-    else
-      hipLaunchKernelGGL(bn_owner_bwd_kernel<false>, dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, B, S, C, pre_relu,
-                         post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
+    with_bool(v, [&](auto vec) {
+      hipLaunchKernelGGL(bn_owner_bwd_kernel<decltype(vec)::value>, dim3(C), dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, B, S, C,
+                         pre_relu, post_relu, gamma, scale, shift, saved, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
+    });
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
@@ -986,32 +956,19 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
   // sum is taken afterwards by the ordered two-level reduction of crn_bias_grad over dx
   float* const dsum_det = (dsum && ndsum > 0 && crn_deterministic()) ? dsum : nullptr;
   if (dsum_det) dsum = nullptr;
-  if (v)
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
+  with_bool(v, [&](auto vec) {
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
                        pre_relu, post_relu, scale, shift, saved, ws, dsum, ndsum);
-  else
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
-                       pre_relu, post_relu, scale, shift, saved, ws, dsum, ndsum);
+  });
   CRN_CHECK_LAUNCH();
-  if (v)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
+  with_bool(v, [&](auto vec) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
                        pre_relu, post_relu, gamma, scale, shift, saved, ws, nparts,
                        (double)B * (double)S, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
-                       pre_relu, post_relu, gamma, scale, shift, saved, ws, nparts,
-                       (double)B * (double)S, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
+  });
   CRN_CHECK_LAUNCH();
-  if (dsum_det) {
-    dim3 gridb(ns, ndsum, B);
-    if (vec_ok(S, {sB_dx}, {dx}))
-      hipLaunchKernelGGL(bias_grad_partial_kernel<true>, gridb, dim3(kThreads), 0, st, dx, S, sB_dx, ws);
-    else
-      hipLaunchKernelGGL(bias_grad_partial_kernel<false>, gridb, dim3(kThreads), 0, st, dx, S, sB_dx, ws);
-    CRN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bias_grad_final_kernel, dim3(crn_cdiv(ndsum, 4)), dim3(256), 0, st, ws, nparts, ndsum, dsum_det, 0);
-    CRN_CHECK_LAUNCH();
-  }
+  // (ws held 2 * C * nparts doubles above: the ndsum * nparts of this second use fit for ndsum <= 2 * C)
+  if (dsum_det) return bias_grad_ordered(dx, B, ndsum, S, sB_dx, ns, dsum_det, 0, ws, ws_bytes, st);
   return CRN_OK;
 }
 
@@ -1045,26 +1002,13 @@ extern "C" int crn_batch_renorm_bwd_apply(const float* x, int64_t sB_x, const fl
   { const int rcf = crn_splitk_flush(st); if (rcf != CRN_OK) return rcf; }
   dim3 grid(ns, C, B);
   if (dsum_det) dsum = nullptr;
-  if (vec_ok(S, {sB_x, sB_dy, sB_dx}, {x, dy, dx}))
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
+  with_bool(vec_ok(S, {sB_x, sB_dy, sB_dx}, {x, dy, dx}), [&](auto vec) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
                        pre_relu, 0, gamma, scale, shift, saved, ws, nparts,
                        (double)B * (double)S, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
-                       pre_relu, 0, gamma, scale, shift, saved, ws, nparts,
-                       (double)B * (double)S, dx, sB_dx, dgamma, dbeta, accumulate, dsum, ndsum);
+  });
   CRN_CHECK_LAUNCH();
-  if (dsum_det) {
-    const int nparts2 = ns * B;
-    dim3 gridb(ns, ndsum, B);
-    if (vec_ok(S, {sB_dx}, {dx}))
-      hipLaunchKernelGGL(bias_grad_partial_kernel<true>, gridb, dim3(kThreads), 0, st, dx, S, sB_dx, ws);
-    else
-      hipLaunchKernelGGL(bias_grad_partial_kernel<false>, gridb, dim3(kThreads), 0, st, dx, S, sB_dx, ws);
-    CRN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bias_grad_final_kernel, dim3(crn_cdiv(ndsum, 4)), dim3(256), 0, st, ws, nparts2, ndsum, dsum_det, 0);
-    CRN_CHECK_LAUNCH();
-  }
+  if (dsum_det) return bias_grad_ordered(dx, B, ndsum, S, sB_dx, ns, dsum_det, 0, ws, ws_bytes, st);
   return CRN_OK;
 }
 
@@ -1097,12 +1041,10 @@ int crn_affine_add_relu_impl(const float* x, const float* scale, const float* sh
   hipStream_t st = (hipStream_t)stream;
   if (B < 1 || C < 1 || S < 1 || (!y && !y_pre)) return CRN_EINVAL;
   dim3 grid(nsplit_for(S, C, B), C, B);
-  if (vec_ok(S, {sB_x, r ? sB_r : 0, y_pre ? sB_pre : 0, y ? sB_y : 0}, {x, r, y_pre, y}))
-    hipLaunchKernelGGL(affine_add_relu_kernel<true>, grid, dim3(kThreads), 0, st, x, scale, shift, r, rscale,
+  with_bool(vec_ok(S, {sB_x, r ? sB_r : 0, y_pre ? sB_pre : 0, y ? sB_y : 0}, {x, r, y_pre, y}), [&](auto vec) {
+    hipLaunchKernelGGL(affine_add_relu_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, scale, shift, r, rscale,
                        rshift, S, sB_x, sB_r, y_pre, sB_pre, y, sB_y, relu);
-  else
-    hipLaunchKernelGGL(affine_add_relu_kernel<false>, grid, dim3(kThreads), 0, st, x, scale, shift, r, rscale,
-                       rshift, S, sB_x, sB_r, y_pre, sB_pre, y, sB_y, relu);
+  });
   CRN_CHECK_LAUNCH();
   return CRN_OK;
 }
@@ -1118,12 +1060,10 @@ int crn_relu_bwd_add_impl(const float* dy, const float* y_pre, const float* dy2,
   hipStream_t st = (hipStream_t)stream;
   if (B < 1 || C < 1 || S < 1 || !y_pre || !dx) return CRN_EINVAL;
   dim3 grid(nsplit_for(S, C, B), C, B);
-  if (vec_ok(S, {dy ? sB_dy : 0, sB_pre, dy2 ? sB_dy2 : 0, sB_dx}, {dy, y_pre, dy2, dx}))
-    hipLaunchKernelGGL(relu_bwd_add_kernel<true>, grid, dim3(kThreads), 0, st, dy, y_pre, dy2, S, sB_dy,
+  with_bool(vec_ok(S, {dy ? sB_dy : 0, sB_pre, dy2 ? sB_dy2 : 0, sB_dx}, {dy, y_pre, dy2, dx}), [&](auto vec) {
+    hipLaunchKernelGGL(relu_bwd_add_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, dy, y_pre, dy2, S, sB_dy,
                        sB_pre, sB_dy2, dx, sB_dx);
-  else
-    hipLaunchKernelGGL(relu_bwd_add_kernel<false>, grid, dim3(kThreads), 0, st, dy, y_pre, dy2, S, sB_dy,
-                       sB_pre, sB_dy2, dx, sB_dx);
+  });
   CRN_CHECK_LAUNCH();
   return CRN_OK;
 }
@@ -1138,17 +1078,5 @@ extern "C" int crn_bias_grad(const float* dy, int B, int C, int64_t S, int64_t s
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
-  const int ns = nsplit_for(S, C, B);
-  const int nparts = ns * B;
-  if (ws_bytes < (size_t)C * nparts * sizeof(double)) return CRN_ENOMEM;
-  dim3 grid(ns, C, B);
-  if (vec_ok(S, {sB}, {dy}))
-    hipLaunchKernelGGL(bias_grad_partial_kernel<true>, grid, dim3(kThreads), 0, st, dy, S, sB, ws);
-  else
-    hipLaunchKernelGGL(bias_grad_partial_kernel<false>, grid, dim3(kThreads), 0, st, dy, S, sB, ws);
-  CRN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bias_grad_final_kernel, dim3(crn_cdiv(C, 4)), dim3(256), 0, st, ws, nparts, C, db,
-                     accumulate);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return bias_grad_ordered(dy, B, C, S, sB, nsplit_for(S, C, B), db, accumulate, ws, ws_bytes, st);
 }

@@ -15,7 +15,7 @@ float64 y lies within 1e-4 * max|y| of zero (asserted on the host before any GPU
 reference agree on every element and none is left out of a comparison.
 
 CRN_TEST_SELFCHECK=1 runs the same assertions against the contract emulator on a CPU (error returns, alignment cases,
-the route probe, bit-for-bit comparisons of two kernels and the split-K test are then left out)."""
+the route probe, bit-for-bit comparisons of two kernels and the split-K tests are then left out)."""
 import os
 
 import numpy as np
@@ -985,6 +985,71 @@ def test_stats_take_over_a_pending_splitk_sum(be):
   assert t.equal(y2, y_ref)
   for a, b in zip(other, want):
     assert t.equal(a, b)
+
+
+def test_backward_takes_over_a_pending_splitk_sum(be):
+  """The same on the backward side: the deferred convolution's output is the `dy` of a BatchRenorm backward (a data gradient
+  in the engine).  The backward launch adds the partial sums up while it loads them and does NOT store dy (it is the only
+  reader): dx, dgamma, dbeta and dsum equal those over the un-deferred convolution bit for bit and dy keeps its sentinel.
+  A backward call on another dy flushes the pending sum instead."""
+  if _SELF:
+    pytest.skip("the emulator has no split-K")
+  from corenet_amd import views as V
+  from corenet_amd.model import conv_geometry as G
+  EMU = EmuBackend()
+  wshape, (H, W), B = (64, 192, 1, 1), (8, 8), 1          # the forward test's shape: two splits, the NV = 1 register kernel
+  C, cin = wshape[:2]
+  S = H * W
+  g = t.Generator().manual_seed(43)
+  w = t.randn(wshape, generator=g) / np.sqrt(cin)
+  fwd = G.conv_fwd(wshape, 0)
+  assert G.operand_eligible(fwd)
+  idx = t.as_tensor(fwd.index); wf = t.zeros(idx.numel()); EMU.gather(w.reshape(-1), idx, wf)
+  desc, blocks = G.operand_table([(0, 0, fwd)])
+  wop = t.zeros(G.operand_entries(fwd) * 32, dtype=t.uint8, device=DEV)
+  be.bf3_operands(wf.to(DEV), (t.as_tensor(desc).to(DEV), blocks), wop)
+  a = t.randn(B, cin, H, W, generator=g).to(DEV)
+  conv = lambda y: be.conv2d_bf3(V.view_of(a), None, wop, fwd.npad, None, 0, V.view_of(y), fwd.window, fwd.pad_lo)
+  dy_ref = t.full((B, C, H, W), SENT, device=DEV)
+  conv(dy_ref)
+  _sync()
+  assert not bool((dy_ref == SENT).any())
+  x = t.randn(B, C, S, generator=g) * 2 + 0.4
+  gamma, beta = t.rand(C, generator=g) + 0.5, t.randn(C, generator=g)
+  r32 = f32(fwd_ref(x, False, gamma, beta, t.randn(C, generator=g), t.rand(C, generator=g) * 3 + 0.1, 12000))
+  xd = x.to(DEV)
+  args = [v.to(DEV) for v in (gamma, r32["scale"], r32["shift"], r32["saved"].reshape(-1))]
+  nds = C - 2
+
+  def bwd(dy):
+    dx = t.full((B, C, S), SENT, device=DEV)
+    dg, db, ds = [t.full((C,), SENT, device=DEV) for _ in range(3)]
+    be.bn_bwd(xd, C * S, dy, C * S, B, C, S, False, False, *args, dx, C * S, dg, db, False, ds, nds)
+    _sync()
+    return dx, dg, db, ds
+  names = ("dx", "dgamma", "dbeta", "dsum")
+  want = bwd(dy_ref)
+  assert not bool((want[0] == SENT).any()) and not bool((want[3][:nds] == SENT).any())
+  all_sentinel(want[3][nds:], "dsum tail")
+  dy = t.full((B, C, H, W), SENT, device=DEV)
+  be.splitk_defer()
+  conv(dy)
+  _sync()
+  all_sentinel(dy, "the split-K sum was not left pending: the test would prove nothing")
+  got = bwd(dy)
+  for p, q, nm in zip(got, want, names):
+    assert t.equal(p, q), nm
+  all_sentinel(dy, "dy is not written by the take-over")
+  # the backward call is for another dy: the pending sum is flushed
+  dy2 = t.full((B, C, H, W), SENT, device=DEV)
+  be.splitk_defer()
+  conv(dy2)
+  _sync()
+  all_sentinel(dy2, "the split-K sum was not left pending")
+  other = bwd(dy_ref.clone())
+  assert t.equal(dy2, dy_ref)
+  for p, q, nm in zip(other, want, names):
+    assert t.equal(p, q), nm
 
 
 # ------------------------------------------------------------------ the formula itself
