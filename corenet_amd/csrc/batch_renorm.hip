@@ -715,8 +715,10 @@ inline void with_bool(bool on, F f) {
 }
 
 // A split-K convolution may have left the partial sums of its output pending (crn_splitk_defer).  If that output is `base`
-// ([B][C][S] dense, batch stride sB) and the launch about to be made is a register kernel on the same stream, the kernel adds
-// them up itself: *part / *splits say where they are.  A pending sum meant for anything else is flushed first.
+// and the launch about to be made is a register kernel on the same stream, the kernel adds them up itself: *part / *splits say
+// where they are.  The kernel stores the sum as [B][C][S] with nothing in between: only base, the extents and sB are compared
+// here, the rest is the producer's guarantee (a sum is left pending only for a crn_splitk_dense view, splitk.h).  A pending sum
+// meant for anything else is flushed first.
 int take_or_flush_pending(const float* base, int64_t sB, int B, int C, int64_t S, hipStream_t st, bool reg_form,
                           const float** part, int* splits) {
   *part = nullptr; *splits = 0;

@@ -1472,8 +1472,9 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   if (!x || !y || (!w && !wslab) || Npad <= 0 || (Npad & 15) || x->B != y->B || kd < 1 || kh < 1 || kw < 1) return CRN_EINVAL;
   if (y->C > Npad || x->C > kTabC) return CRN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const bool armed = crn_splitk_take_armed();
-  { const int rcf = crn_splitk_flush(st); if (rcf != CRN_OK) return rcf; }
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
   const int xmode = even_view(*x) ? 1 : ((x->sW == 2 && x->chan_off != nullptr && (x->W & 1) == 0) ? 2 : 0);
   if (!xmode) return CRN_EINVAL;
   Bf3Geom g{};
@@ -1547,24 +1548,11 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   float* scratch = nullptr;
   // the partial sums: added up by a reduction launch -- or, after crn_splitk_defer, by the BatchRenorm launch that reads
   // this (dense) output next (decoder stages 2-4: statistics after c1, the norms' backward after both data gradients)
-  auto finish_splits = [&]() -> int {
-    const int64_t S = (int64_t)yreal.D * yreal.H * yreal.W;
-    if (armed && !accumulate && yreal.chan_off == nullptr && yreal.sW == 1 && yreal.sH == yreal.W &&
-        yreal.sD == (int64_t)yreal.H * yreal.W && yreal.sC == S && yreal.sB == (int64_t)yreal.C * S) {
-      crn_splitk_set_pending(yreal, scratch, splits, st);
-      return CRN_OK;
-    }
-    return crn_splitk_reduce(yreal, scratch, splits, accumulate, st);
-  };
+  auto finish_splits = [&]() { return crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st); };
   if (splits > 1) {
-    const int64_t S = (int64_t)y->D * y->H * y->W, ytot = (int64_t)y->B * y->C * S;
-    scratch = crn_splitk_scratch((size_t)splits * ytot, st);
+    scratch = crn_splitk_scratch((size_t)splits * y->B * y->C * y->D * y->H * y->W, st);
     if (!scratch) { splits = 1; g.chunks_per_split = g.nchunks; }
-    else {
-      g.mode = 3;
-      g.y.base = scratch; g.y.chan_off = nullptr;
-      g.y.sW = 1; g.y.sH = y->W; g.y.sD = y->H * y->W; g.y.sC = S; g.y.sB = (int64_t)y->C * S;
-    }
+    else { g.mode = 3; g.y = crn_splitk_scratch_view(yreal, scratch); }
   }
   const crnView& yo = g.y;
   g.vec_store = (g.mw >= 4 && yo.sW == 1 && (yo.W & 3) == 0 && (yo.sH & 3) == 0 && (yo.sD & 3) == 0 && (yo.sB & 3) == 0 &&

@@ -739,8 +739,9 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
   const int64_t S = (int64_t)x->D * x->H * x->W;
   if (S * x->C * 4 >= ((int64_t)1 << 31)) return CRN_EINVAL;           // one sample inside the 2 GiB buffer range
   hipStream_t st = (hipStream_t)stream;
-  const bool armed = crn_splitk_take_armed();
-  { const int rcf = crn_splitk_flush(st); if (rcf != CRN_OK) return rcf; }
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
   E2dGeom g{};
   g.x = *x; g.y = *y;
   if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
@@ -778,13 +779,12 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
   g.chunks_per_split = (g.nchunks + splits - 1) / splits;
   splits = (g.nchunks + g.chunks_per_split - 1) / g.chunks_per_split;
   g.tab = g.tr.scale ? g.chunks_per_split * CB * 32 : 0;
-  crnView yreal = *y;
-  const float* scratch = nullptr;
+  const crnView yreal = *y;
+  float* scratch = nullptr;
   if (splits > 1) {
-    float* sc = crn_splitk_scratch((size_t)splits * x->B * y->C * S, st);
-    if (!sc) return CRN_ENOMEM;
-    scratch = sc;
-    g.y.base = sc; g.y.sC = S; g.y.sB = (int64_t)y->C * S; g.y.sH = x->W; g.y.sD = x->H * x->W;
+    scratch = crn_splitk_scratch((size_t)splits * x->B * y->C * S, st);
+    if (!scratch) return CRN_ENOMEM;
+    g.y = crn_splitk_scratch_view(yreal, scratch);
     g.mode = 3;
   } else {
     g.mode = accumulate ? 1 : 0;
@@ -797,13 +797,7 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
   if (k1) rc = launch_e2d<1, 4, 16>(g, grid, lds, st);
   else if (TW == 16) rc = launch_e2d<9, 1, 16>(g, grid, lds, st);
   else rc = launch_e2d<9, 1, 8>(g, grid, lds, st);
-  if (rc == CRN_OK && splits > 1) {
-    if (armed && !accumulate && yreal.sB == (int64_t)yreal.C * S) {      // the next BatchRenorm launch adds them up
-      crn_splitk_set_pending(yreal, scratch, splits, st);
-      return rc;
-    }
-    rc = crn_splitk_reduce(yreal, scratch, splits, accumulate, st);
-  }
+  if (rc == CRN_OK && splits > 1) rc = crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st);
   return rc;
 }
 

@@ -24,11 +24,9 @@
 //    (crnInTransform), so normalised activations are never written to HBM.
 #include "conv_kernels.h"
 #include <algorithm>
-#include <mutex>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 namespace {
 using namespace crnk;
@@ -328,11 +326,6 @@ bool vec_view(const crnView& v) {
 }
 int vec_lead(int pw) { return ((-pw) % 4 + 4) % 4; }   // (w0 - pw - lead) % 4 == 0 for 4-aligned tile origins
 
-bool plain_view(const crnView& v) {
-  return v.chan_off == nullptr && v.sW == 1 && v.sH == v.W && (v.D == 1 || v.sD == v.H * v.W) &&
-         v.sC == (int64_t)v.D * v.H * v.W && (((uintptr_t)v.base) & 15) == 0 && (v.sB & 3) == 0;
-}
-
 // y of a pointwise conv: positions flatten to one index with a single stride (plain: 1; channel-last
 // [B][pos][C]: the pixel pitch), channels have their own stride
 bool flat_out_view(const crnView& v) {
@@ -354,94 +347,6 @@ __global__ void zero_view_kernel(crnView v) {
     const int64_t co = v.chan_off ? (int64_t)v.chan_off[c] : (int64_t)c * v.sC;
     v.base[r * v.sB + co + (int64_t)d * v.sD + (int64_t)h * v.sH + (int64_t)w * v.sW] = 0.f;
   }
-}
-
-// y[b,c,pos] (view) = (accumulate ? y : 0) + sum_s scratch[s][b][c][pos] (dense)
-__global__ void splitk_reduce_kernel(crnView v, const float* scratch, int splits, int accumulate) {
-  const int64_t S = (int64_t)v.D * v.H * v.W, per_b = (int64_t)v.C * S;
-  const int64_t total = per_b * v.B;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    int64_t r = e;
-    const int w = r % v.W; r /= v.W;
-    const int h = r % v.H; r /= v.H;
-    const int d = r % v.D; r /= v.D;
-    const int c = r % v.C; r /= v.C;
-    float sum = 0.f;
-    for (int s = 0; s < splits; ++s) sum += scratch[(int64_t)s * total + e];
-    const int64_t co = v.chan_off ? (int64_t)v.chan_off[c] : (int64_t)c * v.sC;
-    float* dst = v.base + r * v.sB + co + (int64_t)d * v.sD + (int64_t)h * v.sH + (int64_t)w * v.sW;
-    *dst = accumulate ? *dst + sum : sum;
-  }
-}
-
-// the same reduction for plain outputs (every sample a contiguous [C][D][H][W] block): float4 elements, no index
-// arithmetic, and the loads of four splits in flight at a time (the generic kernel walks its splits one load latency
-// after the other and spends five integer divisions per element; 60 of these launches sit on the step's critical path)
-__global__ __launch_bounds__(256) void splitk_reduce_plain_kernel(float* y, int64_t ysB, const float* scratch,
-                                                                  int64_t per_b4, int64_t total4, int splits,
-                                                                  int accumulate) {
-  crn_kernargs_now(y, ysB, scratch, per_b4, total4, splits, accumulate);
-  const f32x4* sc4 = reinterpret_cast<const f32x4*>(scratch);
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total4; e += (int64_t)gridDim.x * blockDim.x) {
-    f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int s = 0;
-    for (; s + 4 <= splits; s += 4) {
-      const f32x4 a = sc4[(int64_t)s * total4 + e], b = sc4[(int64_t)(s + 1) * total4 + e];
-      const f32x4 c = sc4[(int64_t)(s + 2) * total4 + e], d = sc4[(int64_t)(s + 3) * total4 + e];
-      sum += a; sum += b; sum += c; sum += d;               // same order as the generic kernel: split 0 first
-    }
-    for (; s < splits; ++s) sum += sc4[(int64_t)s * total4 + e];
-    const int64_t b = e / per_b4, r = e - b * per_b4;
-    f32x4* dst = reinterpret_cast<f32x4*>(y + b * ysB) + r;
-    *dst = accumulate ? *dst + sum : sum;
-  }
-}
-
-// per-device scratch for split-K partial sums (one process drives one GPU; calls that use it on different
-// streams of the same device must not overlap)
-// One scratch per (device, stream): convolutions that split their reduction on DIFFERENT streams (the engine runs the
-// ray-traced skip path beside the encoder / decoder chain) must not share partial-sum storage.  Grown on demand;
-// hipFree synchronises the device, so a buffer is never released under a kernel that still uses it.
-constexpr int kSkSlots = 64;
-// pinned: the slot belongs to a stream whose launches are CAPTURED into HIP graphs (crn_splitk_reserve): a graph holds the
-// buffer's address, so a pinned slot that has to grow keeps its outgrown buffers (`retired`) until crn_splitk_release.
-struct SkSlot { int dev; hipStream_t st; float* buf; size_t cap; bool used; bool pinned; std::vector<float*>* retired; };
-SkSlot g_sk_slots[kSkSlots] = {};
-std::mutex g_sk_mu;                      // the table is shared by every host thread that launches (autograd worker, main)
-float* splitk_scratch(size_t floats, hipStream_t st) {
-  std::lock_guard<std::mutex> lock(g_sk_mu);
-  constexpr int kSlots = kSkSlots;
-  SkSlot* const slots = g_sk_slots;
-  typedef SkSlot Slot;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  Slot* sl = nullptr;
-  for (int i = 0; i < kSlots && !sl; ++i)
-    if (slots[i].used && slots[i].dev == dev && slots[i].st == st) sl = &slots[i];
-  for (int i = 0; i < kSlots && !sl; ++i)
-    if (!slots[i].used) { slots[i] = Slot{dev, st, nullptr, 0, true, false, nullptr}; sl = &slots[i]; }
-  if (!sl) return nullptr;
-  if (floats > sl->cap) {
-    if (floats > ((size_t)256 << 20) / 4) return nullptr;       // larger outputs keep the atomic path
-    // a stream that is being captured cannot allocate (hipMalloc would fail the capture): the launch keeps the atomic path
-    // (crn_splitk_reserve sizes the scratch BEFORE a capture, so this only catches a launch that needs more
-    // than any eager run before it did)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-    if (cap != hipStreamCaptureStatusNone) return nullptr;
-    if (sl->buf) {
-      if (sl->pinned) {
-        if (!sl->retired) sl->retired = new std::vector<float*>();
-        sl->retired->push_back(sl->buf);                       // a captured graph may still read / write it
-      } else {
-        (void)hipFree(sl->buf);
-      }
-    }
-    sl->cap = sl->pinned ? floats : std::max(floats, ((size_t)16 << 20) / 4);     // (a capture stream gets what was asked for)
-    if (hipMalloc(&sl->buf, sl->cap * 4) != hipSuccess) { sl->buf = nullptr; sl->cap = 0; }
-  }
-  return sl->buf;
 }
 
 int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
@@ -516,100 +421,6 @@ bool fwd_cfg(int MSUB, int NSUB, int B, int Cin, int Npad, int D, int H, int W, 
 
 }  // namespace
 
-CrnSplitPending& crn_splitk_pending() {
-  static thread_local CrnSplitPending p;
-  return p;
-}
-bool crn_splitk_take_armed() {
-  CrnSplitPending& p = crn_splitk_pending();
-  const bool a = p.armed;
-  p.armed = false;
-  return a;
-}
-int crn_splitk_reduce_view(const crnView& y, const float* scratch, int splits, int accumulate, hipStream_t st) {
-  return crn_splitk_reduce(y, scratch, splits, accumulate, st);
-}
-int crn_splitk_flush(hipStream_t st) {
-  CrnSplitPending& p = crn_splitk_pending();
-  if (!p.active) return CRN_OK;
-  p.active = false;
-  (void)st;                       // the sum is ordered behind the convolution: it runs on the conv's own stream / device
-  int cur = -1;
-  CRN_HIP(hipGetDevice(&cur));
-  if (cur != p.device) CRN_HIP(hipSetDevice(p.device));
-  const int rc = crn_splitk_reduce(p.y, p.scratch, p.splits, 0, p.stream);
-  if (cur != p.device) CRN_HIP(hipSetDevice(cur));
-  return rc;
-}
-void crn_splitk_set_pending(const crnView& y, const float* scratch, int splits, hipStream_t st) {
-  CrnSplitPending& p = crn_splitk_pending();
-  p.active = true; p.y = y; p.scratch = scratch; p.splits = splits; p.stream = st;
-  if (hipGetDevice(&p.device) != hipSuccess) p.device = 0;
-}
-extern "C" int crn_splitk_defer(int on) {
-  crn_splitk_pending().armed = on != 0;
-  return CRN_OK;
-}
-float* crn_splitk_scratch(size_t floats, hipStream_t st) { return splitk_scratch(floats, st); }
-// A stream that is about to be CAPTURED into a HIP graph cannot allocate: give it, ahead of the capture, a scratch as
-// large as the largest one any stream of this device has needed so far (floats == 0) or `floats`.
-extern "C" int crn_splitk_reserve(int64_t floats, crnStream stream) {
-  int dev = 0;
-  CRN_HIP(hipGetDevice(&dev));
-  size_t want = floats > 0 ? (size_t)floats : 0;
-  if (!want) {
-    std::lock_guard<std::mutex> lock(g_sk_mu);
-    for (int i = 0; i < kSkSlots; ++i)
-      if (g_sk_slots[i].used && g_sk_slots[i].dev == dev) want = std::max(want, g_sk_slots[i].cap);
-  }
-  {
-    std::lock_guard<std::mutex> lock(g_sk_mu);               // mark (or create) the stream's slot as pinned first
-    SkSlot* sl = nullptr;
-    for (int i = 0; i < kSkSlots && !sl; ++i)
-      if (g_sk_slots[i].used && g_sk_slots[i].dev == dev && g_sk_slots[i].st == (hipStream_t)stream) sl = &g_sk_slots[i];
-    for (int i = 0; i < kSkSlots && !sl; ++i)
-      if (!g_sk_slots[i].used) { g_sk_slots[i] = SkSlot{dev, (hipStream_t)stream, nullptr, 0, true, false, nullptr}; sl = &g_sk_slots[i]; }
-    if (!sl) return CRN_ENOMEM;
-    sl->pinned = true;
-  }
-  if (!want) return CRN_OK;
-  return splitk_scratch(want, (hipStream_t)stream) ? CRN_OK : CRN_ENOMEM;
-}
-// Gives back the scratch of a stream that is about to be destroyed (a capture stream whose graphs are gone); hipFree waits for
-// the device, so nothing that still reads the buffer can be running.  Unknown streams are not an error.
-extern "C" int crn_splitk_release(crnStream stream) {
-  int dev = 0;
-  CRN_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_sk_mu);
-  for (int i = 0; i < kSkSlots; ++i) {
-    SkSlot& sl = g_sk_slots[i];
-    if (sl.used && sl.dev == dev && sl.st == (hipStream_t)stream) {
-      if (sl.buf) CRN_HIP(hipFree(sl.buf));
-      if (sl.retired) {
-        for (float* b : *sl.retired) (void)hipFree(b);
-        delete sl.retired;
-      }
-      sl = SkSlot{};
-    }
-  }
-  return CRN_OK;
-}
-int crn_splitk_reduce(const crnView& y, const float* scratch, int splits, int accumulate, hipStream_t st) {
-  const int64_t ytot = (int64_t)y.B * y.C * y.D * y.H * y.W;
-  const int64_t per_b = (int64_t)y.C * y.D * y.H * y.W;
-  if (plain_view(y) && (per_b & 3) == 0 && (((uintptr_t)scratch) & 15) == 0) {
-    const int64_t total4 = ytot / 4;
-    hipLaunchKernelGGL(splitk_reduce_plain_kernel, dim3((unsigned)std::min<int64_t>(crn_cdiv(total4, 256), 4096)), dim3(256),
-                       0, st, y.base, y.sB, scratch, per_b / 4, total4, splits, accumulate);
-    CRN_CHECK_LAUNCH();
-    return CRN_OK;
-  }
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(crn_cdiv(ytot, 256), 4096)), dim3(256), 0, st,
-                     y, scratch, splits, accumulate);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
-}
-
 static long long* g_pw_stamps = nullptr;
 #ifdef CRN_TOOLS      // tools/_build/libcorenet_hip_tools.so only (corenet_amd.build.build_tools)
 extern "C" int crn_pw_debug_stamps(long long* out32) {       // tuning aid (CRN_PW_STAMPS=1)
@@ -628,8 +439,9 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
     return CRN_EINVAL;
   if (y->C > Npad) return CRN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const bool armed = crn_splitk_take_armed();
-  { const int rcf = crn_splitk_flush(st); if (rcf != CRN_OK) return rcf; }
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
   const int64_t Sx = (int64_t)x->D * x->H * x->W;
   if (kd * kh * kw == 1 && pd == 0 && ph == 0 && pw == 0 && splits <= 1 && one_position(*x) && one_position(*y) &&
       x->B <= kDenseB) {
@@ -676,7 +488,7 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
       if (sp > 1) {
         p.cps = (crn_cdiv(x->C, sp) + 31) & ~31;
         sp = crn_cdiv(x->C, p.cps);
-        if (sp > 1 && (scratch = splitk_scratch((size_t)sp * ytot, st)) != nullptr) {
+        if (sp > 1 && (scratch = crn_splitk_scratch((size_t)sp * ytot, st)) != nullptr) {
           p.splits = sp; p.y = scratch; p.ysB = (int64_t)y->C * Sx; p.ysC = Sx; p.ysP = 1; p.mode = 0;
         } else {
           p.cps = (x->C + 31) & ~31;
@@ -699,14 +511,7 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
     const size_t tab_bytes = p.tr.scale ? (size_t)2 * p.cps * sizeof(float) : 0;
     hipLaunchKernelGGL(pointwise_fwd_kernel<2>, grid, dim3(256), tab_bytes, st, p);
     CRN_CHECK_LAUNCH();
-    if (p.splits > 1) {
-      if (armed && !accumulate && plain_view(*y) && y->sB == (int64_t)y->C * Sx) {
-        crn_splitk_set_pending(*y, scratch, p.splits, st);
-        return CRN_OK;
-      }
-      return crn_splitk_reduce(*y, scratch, p.splits, accumulate, st);
-    }
-    return CRN_OK;
+    return p.splits > 1 ? crn_splitk_finish(*y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
   }
   // Score every (MSUB, NSUB) tile: useful MFMA rows x operand reuse of the tile x how well
   // the grid (with split-K as a fallback) fills 256 CUs.
@@ -786,12 +591,10 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   // only when the scratch cannot be had
   const crnView yreal = *y;
   const int64_t ytot = (int64_t)y->B * y->C * y->D * y->H * y->W;
-  float* scratch = g.mode == 2 ? splitk_scratch((size_t)splits * ytot, st) : nullptr;
+  float* scratch = g.mode == 2 ? crn_splitk_scratch((size_t)splits * ytot, st) : nullptr;
   if (scratch) {
     g.mode = 3;
-    const int64_t S = (int64_t)y->D * y->H * y->W;
-    g.y.base = scratch; g.y.chan_off = nullptr;
-    g.y.sW = 1; g.y.sH = y->W; g.y.sD = y->H * y->W; g.y.sC = S; g.y.sB = (int64_t)y->C * S;
+    g.y = crn_splitk_scratch_view(yreal, scratch);
   }
   y = &g.y;                                // epilogue alignment below refers to the tensor actually written
   if (g.mode == 2 && !accumulate) {
@@ -816,15 +619,9 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
 #define CRN_FWD_CASE(M, N) if (best.MSUB == M && NSUB == N) rc = crn_launch_fwd_##M##_##N(g, xvec, grid, lds_bytes, st);
   CRN_FWD_CONFIGS(CRN_FWD_CASE)
 #undef CRN_FWD_CASE
-  if (rc == CRN_OK && g.mode == 3) {
-    // the next BatchRenorm launch over y adds the partial sums up itself when the caller armed it (crn_splitk_defer) -- like the
-    // pointwise and the split-bf16 paths above: the encoder's fp32 3x3 layers and decoder stage 2 lose their reduction launch
-    if (armed && !accumulate && plain_view(yreal) && yreal.sB == (int64_t)yreal.C * yreal.D * yreal.H * yreal.W) {
-      crn_splitk_set_pending(yreal, scratch, splits, st);
-      return rc;
-    }
-    rc = crn_splitk_reduce(yreal, scratch, splits, accumulate, st);
-  }
+  // the next BatchRenorm launch over y adds the partial sums up itself when the caller armed it (crn_splitk_defer) -- like the
+  // pointwise and the split-bf16 paths: the encoder's fp32 3x3 layers and decoder stage 2 lose their reduction launch
+  if (rc == CRN_OK && g.mode == 3) rc = crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st);
   return rc;
 }
 

@@ -99,25 +99,5 @@ __device__ __forceinline__ void crn_kernarg_touch(const T& g) {
 // backward becomes its own ordered reduction, and the ray-sample scatter accumulates in 64-bit fixed point.
 bool crn_deterministic();
 
-// A split-K convolution whose partial sums are still in the scratch: the next BatchRenorm launch over `y` adds them up
-// itself (crn_splitk_defer); anything else that needs the scratch or y first calls crn_splitk_flush.
-struct CrnSplitPending {
-  bool armed = false, active = false;
-  crnView y{};                 // the conv's real output (dense [B][C][S])
-  const float* scratch = nullptr;
-  int splits = 0;
-  hipStream_t stream = nullptr;  // the stream (and its device) the convolution ran on: only a BatchRenorm call on the SAME
-  int device = -1;               // stream may take the sum over; a flush always runs on this stream, behind the conv
-};
-CrnSplitPending& crn_splitk_pending();                 // per host thread
-// Run the pending reduction now, on the stream of the convolution that left it (no-op if none).  EVERY entry point of
-// the library calls this first (CRN_ENTRY(stream)), except the BatchRenorm calls that can take the sum over.
-int crn_splitk_flush(hipStream_t st);
-void crn_splitk_set_pending(const crnView& y, const float* scratch, int splits, hipStream_t st);
-#define CRN_ENTRY(stream_arg)                                                          \
-  do {                                                                                 \
-    const int crn_rcf_ = crn_splitk_flush((hipStream_t)(stream_arg));                  \
-    if (crn_rcf_ != CRN_OK) return crn_rcf_;                                           \
-  } while (0)
-bool crn_splitk_take_armed();                          // consumes the arming of crn_splitk_defer
-int crn_splitk_reduce_view(const crnView& y, const float* scratch, int splits, int accumulate, hipStream_t st);
+// the split-K service: CrnSplitPending, CRN_ENTRY, crn_splitk_*
+#include "splitk.h"

@@ -1052,6 +1052,137 @@ def test_backward_takes_over_a_pending_splitk_sum(be):
     assert t.equal(p, q), nm
 
 
+def _packed(w, geom):
+  idx = t.as_tensor(geom.index); out = t.zeros(idx.numel())
+  EmuBackend().gather(w.reshape(-1), idx, out)
+  return out
+
+
+def _stats_after_a_deferred_conv(be, conv, yshape, pre_relu, seed):
+  """The steps of test_stats_take_over_a_pending_splitk_sum for any producer: conv(y) runs the convolution into y.  All four
+  producers end in crn_splitk_finish, so each is held to the same bit-for-bit result whether the statistics launch takes the
+  sum over (its register form) or flushes it first."""
+  B, C = yshape[:2]
+  S = int(np.prod(yshape[2:]))
+  g = t.Generator().manual_seed(seed)
+  y_ref = t.full(yshape, SENT, device=DEV)
+  conv(y_ref)
+  _sync()
+  assert not bool((y_ref == SENT).any())
+  gamma, beta = (t.rand(C, generator=g) + 0.5).to(DEV), t.randn(C, generator=g).to(DEV)
+  rm0, rv0 = t.randn(C, generator=g), t.rand(C, generator=g) * 3 + 0.1
+  nbt = t.tensor([12000], dtype=t.int64, device=DEV)
+
+  def stats(y):
+    rm, rv = dev(rm0), dev(rv0)
+    sc, sh, sv = [t.full((n,), SENT, device=DEV) for n in (C, C, 4 * C)]
+    be.bn_stats(y, B, C, S, C * S, pre_relu, gamma, beta, rm, rv, nbt, EPS, MOM, True, sc, sh, sv)
+    _sync()
+    return sc, sh, sv, rm, rv
+  names = ("scale", "shift", "saved", "running_mean", "running_var")
+  want = stats(y_ref)
+  y = t.full(yshape, SENT, device=DEV)
+  be.splitk_defer()
+  conv(y)
+  _sync()
+  all_sentinel(y, "the split-K sum was not left pending: the test would prove nothing")
+  got = stats(y)
+  assert t.equal(y, y_ref)
+  for a, b, nm in zip(got, want, names):
+    assert t.equal(a, b), nm
+  # the statistics call is for another tensor: the pending sum is flushed
+  y2 = t.full(yshape, SENT, device=DEV)
+  be.splitk_defer()
+  conv(y2)
+  _sync()
+  all_sentinel(y2, "the split-K sum was not left pending")
+  other = stats(y_ref.clone())
+  assert t.equal(y2, y_ref)
+  for a, b, nm in zip(other, want, names):
+    assert t.equal(a, b), nm
+
+
+def _fp32_conv(be, wshape, pad, hw, seed):
+  """crn_conv_fwd with splits = 0 (the engine's value: the backend's default of 1 disables the automatic split) on one sample."""
+  from corenet_amd import views as V
+  from corenet_amd.model import conv_geometry as G
+  g = t.Generator().manual_seed(seed)
+  w = t.randn(wshape, generator=g) / np.sqrt(np.prod(wshape[1:]))
+  fwd = G.conv_fwd(wshape, pad)
+  wf = _packed(w, fwd).to(DEV)
+  x = t.randn((1, wshape[1]) + hw, generator=g).to(DEV)
+  def conv(y, accumulate=False):
+    be.conv_fwd(V.view_of(x), None, wf, fwd.npad, None, 0, V.view_of(y), fwd.window, fwd.pad_lo, 0, accumulate, math="fp32")
+  return conv
+
+
+def test_stats_after_a_deferred_pointwise_conv(be):
+  """The fp32 pointwise path of crn_conv_fwd: weight (64, 256, 1, 1) on one 8 x 8 map is 2 workgroups and 256 / 128 = 2
+  channel slices, so the dispatch computes 2 splits."""
+  if _SELF:
+    pytest.skip("the emulator has no split-K")
+  _stats_after_a_deferred_conv(be, _fp32_conv(be, (64, 256, 1, 1), 0, (8, 8), 45), (1, 64, 8, 8), False, 46)
+
+
+def test_stats_after_a_deferred_generic_fp32_conv(be):
+  """The generic fp32 engine of crn_conv_fwd: weight (128, 256, 3, 3) on one 8 x 8 map.  Every tile configuration covers the
+  map with one position tile (at most 8 workgroups over the 128 columns) and needs at least four channel chunks, so the cost
+  model's split penalty (20000 cycles) is far below the chunks a split saves each workgroup: 256 input channels already
+  split (the sentinel assertion says so on the GPU), the encoder's own 512 -> 512 is not needed."""
+  if _SELF:
+    pytest.skip("the emulator has no split-K")
+  _stats_after_a_deferred_conv(be, _fp32_conv(be, (128, 256, 3, 3), 1, (8, 8), 47), (1, 128, 8, 8), False, 48)
+
+
+def test_stats_after_a_deferred_bf16x3_conv(be):
+  """The split-bf16 decoder engine (crn_conv_fwd_bf3_slabs): weight (16, 64, 5, 5, 5) on one 8^3 sample is one tile and one
+  column block, which cannot fill the chip, so the launch splits over its channel chunks.  The statistics are the decoder's
+  (pre_relu); 16 channels are below the channel-owner form, so here the statistics call flushes the pending sum itself."""
+  if _SELF:
+    pytest.skip("the emulator has no split-K")
+  from corenet_amd import views as V
+  from corenet_amd.model import conv_geometry as G
+  wshape, dims = (16, 64, 5, 5, 5), (8, 8, 8)
+  g = t.Generator().manual_seed(49)
+  w = t.randn(wshape, generator=g) / np.sqrt(np.prod(wshape[1:]))
+  fwd = G.conv_fwd(wshape, 2)
+  desc, blocks = G.operand_table([(0, 0, fwd, True)])
+  slab = t.zeros(G.slab_entries(fwd) * 32, dtype=t.uint8, device=DEV)
+  be.bf3_operands(_packed(w, fwd).to(DEV), (t.as_tensor(desc).to(DEV), blocks), slab)
+  x = t.randn((1, wshape[1]) + dims, generator=g).to(DEV)
+  conv = lambda y: be.conv_fwd(V.view_of(x), None, None, fwd.npad, None, 0, V.view_of(y), fwd.window, fwd.pad_lo, 0,
+                               math="bf16x3", wslab=slab)
+  _stats_after_a_deferred_conv(be, conv, (1, wshape[0]) + dims, True, 50)
+
+
+def test_an_accumulating_conv_is_never_left_pending(be):
+  """accumulate with the arming set (the pointwise producer's shape): the sum is reduced at once -- y is written when the call
+  returns -- and equals the un-armed accumulating call bit for bit.  Both equal prior + the plain result exactly: the reduction
+  adds the splits up in the plain call's order (split 0 first, from zero) and then adds that float32 sum to y once."""
+  if _SELF:
+    pytest.skip("the emulator has no split-K")
+  conv = _fp32_conv(be, (64, 256, 1, 1), 0, (8, 8), 45)
+  y_ref = t.full((1, 64, 8, 8), SENT, device=DEV)
+  be.splitk_defer()
+  conv(y_ref)
+  _sync()
+  all_sentinel(y_ref, "the launch does not split: the test would prove nothing")
+  prior = t.randn(1, 64, 8, 8, generator=t.Generator().manual_seed(51)).to(DEV)
+  conv(y_ref.clone())                                      # (flushes the sum left pending for y_ref)
+  _sync()
+  assert not bool((y_ref == SENT).any())
+  y_a = prior.clone()
+  conv(y_a, accumulate=True)
+  _sync()
+  y_b = prior.clone()
+  be.splitk_defer()
+  conv(y_b, accumulate=True)
+  _sync()
+  assert not t.equal(y_b, prior), "the accumulating sum was left pending"
+  assert t.equal(y_b, y_a)
+  assert t.equal(y_a, prior + y_ref)
+
+
 # ------------------------------------------------------------------ the formula itself
 @pytest.mark.parametrize("pre,post", [(False, False), (True, False), (False, True), (True, True)])
 def test_backward_formula_is_autograd_of_the_oracle(pre, post):
