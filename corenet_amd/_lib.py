@@ -40,6 +40,15 @@ class CrnView(C.Structure):
               ("chan_off", vp), ("sD", C.c_int32), ("sH", C.c_int32), ("sW", C.c_int32)]
 
 
+class CrnConvPlan(C.Structure):
+  """Mirror of crnConvPlan (include/corenet_hip.h)."""
+  _fields_ = [(n, C.c_int32) for n in ("path", "msub", "nsub", "xstage", "dystage", "forced", "cc", "td", "th", "tw", "mw",
+                                        "splits", "chunks", "vec_store", "balanced", "lds_bytes", "lds_budget")]
+
+
+PLAN_PATHS = {1: "dense_cols", 2: "dense_rows", 3: "dense_wgrad", 4: "pointwise", 5: "generic"}
+
+
 class CrnInTransform(C.Structure):
   _fields_ = [("scale", vp), ("shift", vp), ("pre_relu", C.c_int32), ("post_relu", C.c_int32)]
 
@@ -57,6 +66,10 @@ class HipError(RuntimeError):
 _SIGS = {
     "crn_conv_fwd": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32,
                      C.POINTER(CrnView), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "crn_conv_fwd_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32,
+                          C.POINTER(CrnView), i32, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(CrnConvPlan)],
+    "crn_conv_wgrad_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), C.POINTER(CrnView), vp, i32,
+                            i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(CrnConvPlan)],
     "crn_conv_fwd_bf3": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32,
                          C.POINTER(CrnView), i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "crn_conv_fwd_bf3_slabs": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32,

@@ -109,6 +109,30 @@ class HipBackend:
                           pad_lo[0], pad_lo[1], pad_lo[2], splits, int(accumulate), _ctapboxes(boxes),
                           _lib.stream())
 
+  @staticmethod
+  def _plan_dict(p) -> dict:
+    d = {n: int(getattr(p, n)) for n, _ in p._fields_}
+    d["path"] = _lib.PLAN_PATHS[d["path"]]
+    return d
+
+  def conv_fwd_plan(self, x: View, tr: Optional[Transform], w: t.Tensor, npad: int, bias: Optional[t.Tensor], bias_sB: int,
+                    y: View, window, pad_lo, splits: int = 1, accumulate: bool = False, boxes=None) -> dict:
+    """What conv_fwd(math="fp32") would launch for these arguments (crn_conv_fwd_plan): a dict of the crnConvPlan fields,
+    path by name.  Host arithmetic only: works on views of CPU tensors too.  A rejected shape raises HipError."""
+    p = _lib.CrnConvPlan()
+    self.lib.crn_conv_fwd_plan(C.byref(_cview(x)), _ctr(tr), ptr(w), npad, ptr(bias), bias_sB, C.byref(_cview(y)),
+                               window[0], window[1], window[2], pad_lo[0], pad_lo[1], pad_lo[2], splits, int(accumulate),
+                               _ctapboxes(boxes), C.byref(p))
+    return self._plan_dict(p)
+
+  def conv_wgrad_plan(self, x: View, tr: Optional[Transform], dy: View, dw: t.Tensor, npad: int, window, pad_lo,
+                      zero_first: bool = True, boxes=None) -> dict:
+    """What conv_wgrad(math="fp32") on the generic engine would launch (crn_conv_wgrad_plan); see conv_fwd_plan."""
+    p = _lib.CrnConvPlan()
+    self.lib.crn_conv_wgrad_plan(C.byref(_cview(x)), _ctr(tr), C.byref(_cview(dy)), ptr(dw), npad, window[0], window[1],
+                                 window[2], pad_lo[0], pad_lo[1], pad_lo[2], int(zero_first), _ctapboxes(boxes), C.byref(p))
+    return self._plan_dict(p)
+
   def conv_fwd_stats(self, x: View, tr: Optional[Transform], wslab: t.Tensor, npad: int, bias, bias_sB: int, y: View, window,
                      pad_lo, boxes, Cn: int, pre_relu: bool) -> int:
     """conv_fwd(math="bf16x3", wslab) that also leaves the partial sums of the BatchRenorm behind it in this stream's

@@ -50,8 +50,9 @@ struct PwGeom {
   long long* stamps;               // tuning aid (CRN_PW_STAMPS=1): shader-clock stamps of workgroup 0
 };
 
-// NS = 16-column blocks per workgroup (2: 64 x 32 tiles)
+constexpr int kPwBN = 32;           // output columns of one workgroup (64 x 32 tiles)
 constexpr int kPwTab = 2048;        // channels of one workgroup (its split's range) whose scale / shift are staged in LDS
+// NS = 16-column blocks per workgroup (kPwBN / 16)
 template <int NS>
 __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   constexpr int BM = 64, BN = NS * 16, KC = 64, SA = BM + 16, SB = BN + 16;   // KC 64: half the barriers of KC 32
@@ -419,100 +420,73 @@ bool fwd_cfg(int MSUB, int NSUB, int B, int Cin, int Npad, int D, int H, int W, 
   return true;
 }
 
-}  // namespace
-
-static long long* g_pw_stamps = nullptr;
-#ifdef CRN_TOOLS      // tools/_build/libcorenet_hip_tools.so only (corenet_amd.build.build_tools)
-extern "C" int crn_pw_debug_stamps(long long* out32) {       // tuning aid (CRN_PW_STAMPS=1)
-  if (!g_pw_stamps) return CRN_EINVAL;
-  CRN_HIP(hipDeviceSynchronize());
-  CRN_HIP(hipMemcpy(out32, g_pw_stamps, 32 * sizeof(long long), hipMemcpyDeviceToHost));
-  return CRN_OK;
-}
-#endif
-extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const float* w, int Npad,
-                            const float* bias, int bias_sB, const crnView* y,
-                            int kd, int kh, int kw, int pd, int ph, int pw,
-                            int splits, int accumulate, const crnTapBoxes* boxes, crnStream stream) {
+// ---------------- forward plan: which kernel a call gets ---------------------
+// Host arithmetic on the views' extents, strides and alignment only: crn_conv_fwd launches what fwd_select says, and
+// crn_conv_fwd_plan reports it, so there is one copy of the selection.
+int fwd_check_args(const crnView* x, const float* w, int Npad, const crnView* y, int kd, int kh, int kw,
+                   const crnTapBoxes* boxes) {
   if (boxes && (boxes->n_groups < 0 || boxes->n_groups > 8 || boxes->c_groups < 0 || boxes->c_groups > 8)) return CRN_EINVAL;
   if (!x || !y || !w || Npad <= 0 || (Npad & 15) || x->B != y->B || kd < 1 || kh < 1 || kw < 1)
     return CRN_EINVAL;
   if (y->C > Npad) return CRN_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  int rcf;
-  const bool armed = crn_splitk_begin(st, &rcf);
-  if (rcf != CRN_OK) return rcf;
+  return CRN_OK;
+}
+
+struct FwdSel {
+  int path;                  // CRN_PLAN_*
+  int zs;                    // dense_rows: slices of the input channels
+  int pw_splits, pw_cps;     // pointwise: K splits to ask the scratch for (1: none) and their channels
+  int pw_cps_whole;          // ... channels of the only split when the launch does not split
+  FwdCfg cfg;                // generic: tile configuration,
+  int xvec, lead;            // staging of x (0 scalar, 1 float4 units, 2 position pairs) and its left lead,
+  bool forced;               // scalar staging because no 16-byte configuration fits,
+  int splits, nchunks;       // splits of the nchunks channel chunks the launch asks for
+};
+
+// epilogue of the generic kernels: float4 stores (y = the tensor actually written, the scratch view when splitting)
+bool fwd_vec_store(const crnView& y, int mw, int mode) {
+  return y.sW == 1 && mw >= 4 && (y.W & 3) == 0 && (y.sH & 3) == 0 && (y.sD & 3) == 0 && (y.sB & 3) == 0 &&
+         (y.sC & 3) == 0 && (((uintptr_t)y.base) & 15) == 0 && y.chan_off == nullptr && mode != 2;
+}
+
+int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int Npad, const crnView* y,
+               int kd, int kh, int kw, int pd, int ph, int pw, int splits, FwdSel* s) {
+  *s = FwdSel{};
   const int64_t Sx = (int64_t)x->D * x->H * x->W;
+  const bool has_scale = tr && tr->scale;
   if (kd * kh * kw == 1 && pd == 0 && ph == 0 && pw == 0 && splits <= 1 && one_position(*x) && one_position(*y) &&
       x->B <= kDenseB) {
-    const crnInTransform trv = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
-    if (y->C >= 1024 && x->C <= 2048) {              // wide output: a thread per column
-      hipLaunchKernelGGL(dense_cols_kernel, dim3((unsigned)crn_cdiv(y->C, 64)), dim3(256), (size_t)x->B * x->C * 4, st,
-                         x->base, x->sB, x->sC, trv, w, Npad, y->C, x->C, x->B, bias, bias_sB, y->base, y->sB, y->sC,
-                         accumulate);
-      CRN_CHECK_LAUNCH();
-      return CRN_OK;
-    }
-    if (y->C <= 256 && !trv.scale && x->C >= 1024) {   // long reduction onto few columns
-      const int zs = (y->sC == 1 && y->sB >= y->C && !crn_deterministic()) ? std::max(1, std::min(16, x->C / 2048)) : 1;   // slices of >= 2048 rows
-      if (zs > 1 && !accumulate)
-        CRN_HIP(hipMemset2DAsync(y->base, (size_t)y->sB * 4, 0, (size_t)y->C * 4, (size_t)x->B, st));
-      hipLaunchKernelGGL(dense_rows_kernel, dim3((unsigned)crn_cdiv(y->C, 8), (unsigned)x->B, (unsigned)zs), dim3(256), 0, st,
-                         x->base, x->sB, x->sC, w, Npad, y->C, x->C, bias, bias_sB, y->base, y->sB, y->sC, accumulate,
-                         crn_cdiv(x->C, zs));
-      CRN_CHECK_LAUNCH();
+    if (y->C >= 1024 && x->C <= 2048) { s->path = CRN_PLAN_DENSE_COLS; return CRN_OK; }   // wide output: a thread per column
+    if (y->C <= 256 && !has_scale && x->C >= 1024) {   // long reduction onto few columns
+      s->path = CRN_PLAN_DENSE_ROWS;
+      s->zs = (y->sC == 1 && y->sB >= y->C && !crn_deterministic()) ? std::max(1, std::min(16, x->C / 2048)) : 1;   // slices of >= 2048 rows
       return CRN_OK;
     }
   }
   if (kd * kh * kw == 1 && pd == 0 && ph == 0 && pw == 0 && splits <= 1 && plain_view(*x) && flat_out_view(*y) &&
       Sx == (int64_t)y->D * y->H * y->W && (Sx & 3) == 0 && (((uintptr_t)w) & 15) == 0 &&
       (int64_t)x->C * Sx * 4 < ((int64_t)1 << 31) && (int64_t)x->C * Npad * 4 < ((int64_t)1 << 31) &&
-      (!tr || !tr->scale || x->C <= kPwTab)) {           // (buffer offsets of the hand-tracked loads; the LDS tables)
-    PwGeom p{};
-    p.x = x->base; p.y = y->base; p.w = w; p.bias = bias;
-    p.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
-    p.B = x->B; p.C = x->C; p.N = y->C; p.Npad = Npad; p.S = (int)Sx;
-    p.xsB = x->sB; p.ysB = y->sB; p.bias_sB = bias_sB; p.mode = accumulate ? 1 : 0;
-    p.ysC = y->sC; p.ysP = y->sW;
-    p.splits = 1; p.cps = (x->C + 63) & ~63;
+      (!has_scale || x->C <= kPwTab)) {           // (buffer offsets of the hand-tracked loads; the LDS tables)
+    s->path = CRN_PLAN_POINTWISE;
+    s->pw_splits = 1; s->pw_cps = s->pw_cps_whole = (x->C + 63) & ~63;
     // long reductions over few positions (stage4/5 of the encoder: K = 1024..2048, 64..256 positions per sample):
     // split the channels over blocks, partial sums to the split-K scratch, one reduction launch
     // (64-column tiles were measured equal to 32-column ones on the whole step, 10.07 vs 10.04 ms: these launches are
     // latency bound, not operand-traffic bound)
-    constexpr int BNh = 32, pw_blocks = 256, pw_fill = 512, pw_minc = 128;
-    const int64_t blocks = crn_cdiv(Sx, 64) * crn_cdiv(y->C, BNh) * (int64_t)x->B;
-    const int64_t ytot = (int64_t)y->B * y->C * Sx;
-    float* scratch = nullptr;
+    constexpr int pw_blocks = 256, pw_fill = 512, pw_minc = 128;
+    const int64_t blocks = crn_cdiv(Sx, 64) * crn_cdiv(y->C, kPwBN) * (int64_t)x->B;
     if (splits < 1 && blocks < pw_blocks && x->C >= 2 * pw_minc) {
       int sp = (int)std::min<int64_t>(std::min<int64_t>(x->C / pw_minc, 16), crn_cdiv(pw_fill, blocks));
       if (sp > 1) {
-        p.cps = (crn_cdiv(x->C, sp) + 31) & ~31;
-        sp = crn_cdiv(x->C, p.cps);
-        if (sp > 1 && (scratch = crn_splitk_scratch((size_t)sp * ytot, st)) != nullptr) {
-          p.splits = sp; p.y = scratch; p.ysB = (int64_t)y->C * Sx; p.ysC = Sx; p.ysP = 1; p.mode = 0;
-        } else {
-          p.cps = (x->C + 31) & ~31;
-        }
+        const int cps = (crn_cdiv(x->C, sp) + 31) & ~31;
+        sp = crn_cdiv(x->C, cps);
+        if (sp > 1) { s->pw_splits = sp; s->pw_cps = cps; }
+        s->pw_cps_whole = (x->C + 31) & ~31;
       }
     }
-#ifdef CRN_TOOLS
-    static const bool want_stamps = getenv("CRN_PW_STAMPS") != nullptr;
-#else
-    constexpr bool want_stamps = false;
-#endif
-    static long long* pw_stamps = nullptr;
-    if (want_stamps) {
-      if (!pw_stamps) CRN_HIP(hipMalloc(&pw_stamps, 32 * sizeof(long long)));
-      CRN_HIP(hipMemsetAsync(pw_stamps, 0, 32 * sizeof(long long), st));
-      p.stamps = pw_stamps;
-      g_pw_stamps = pw_stamps;
-    }
-    dim3 grid((unsigned)crn_cdiv(Sx, 64), (unsigned)crn_cdiv(y->C, BNh), (unsigned)(x->B * p.splits));
-    const size_t tab_bytes = p.tr.scale ? (size_t)2 * p.cps * sizeof(float) : 0;
-    hipLaunchKernelGGL(pointwise_fwd_kernel<2>, grid, dim3(256), tab_bytes, st, p);
-    CRN_CHECK_LAUNCH();
-    return p.splits > 1 ? crn_splitk_finish(*y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
+    return CRN_OK;
   }
+  s->path = CRN_PLAN_GENERIC;
   // Score every (MSUB, NSUB) tile: useful MFMA rows x operand reuse of the tile x how well
   // the grid (with split-K as a fallback) fills 256 CUs.
   static const int kM[4] = {8, 4, 2, 1};
@@ -559,6 +533,95 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
     }
   }
   if (!have) return CRN_EINVAL;
+  s->cfg = best; s->xvec = xvec; s->lead = lead; s->forced = forced;
+  s->nchunks = crn_cdiv(x->C, best.CC);
+  if (splits < 1) {   // auto split-K (atomic accumulate) only when the output grid cannot fill the chip
+    splits = forced ? (best.blocks >= 192 ? 1 : (int)std::min<int64_t>(std::min(s->nchunks, 16), crn_cdiv(256, best.blocks)))
+                    : best_splits;
+  }
+  if (splits > s->nchunks) splits = s->nchunks;
+  s->splits = crn_cdiv(s->nchunks, crn_cdiv(s->nchunks, splits));
+  return CRN_OK;
+}
+
+}  // namespace
+
+static long long* g_pw_stamps = nullptr;
+#ifdef CRN_TOOLS      // tools/_build/libcorenet_hip_tools.so only (corenet_amd.build.build_tools)
+extern "C" int crn_pw_debug_stamps(long long* out32) {       // tuning aid (CRN_PW_STAMPS=1)
+  if (!g_pw_stamps) return CRN_EINVAL;
+  CRN_HIP(hipDeviceSynchronize());
+  CRN_HIP(hipMemcpy(out32, g_pw_stamps, 32 * sizeof(long long), hipMemcpyDeviceToHost));
+  return CRN_OK;
+}
+#endif
+extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const float* w, int Npad,
+                            const float* bias, int bias_sB, const crnView* y,
+                            int kd, int kh, int kw, int pd, int ph, int pw,
+                            int splits, int accumulate, const crnTapBoxes* boxes, crnStream stream) {
+  const int rca = fwd_check_args(x, w, Npad, y, kd, kh, kw, boxes);
+  if (rca != CRN_OK) return rca;
+  hipStream_t st = (hipStream_t)stream;
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
+  FwdSel sel;
+  const int rcs = fwd_select(x, tr, w, Npad, y, kd, kh, kw, pd, ph, pw, splits, &sel);
+  if (rcs != CRN_OK) return rcs;
+  const int64_t Sx = (int64_t)x->D * x->H * x->W;
+  if (sel.path == CRN_PLAN_DENSE_COLS) {
+    const crnInTransform trv = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL(dense_cols_kernel, dim3((unsigned)crn_cdiv(y->C, 64)), dim3(256), (size_t)x->B * x->C * 4, st,
+                       x->base, x->sB, x->sC, trv, w, Npad, y->C, x->C, x->B, bias, bias_sB, y->base, y->sB, y->sC,
+                       accumulate);
+    CRN_CHECK_LAUNCH();
+    return CRN_OK;
+  }
+  if (sel.path == CRN_PLAN_DENSE_ROWS) {
+    const int zs = sel.zs;
+    if (zs > 1 && !accumulate)
+      CRN_HIP(hipMemset2DAsync(y->base, (size_t)y->sB * 4, 0, (size_t)y->C * 4, (size_t)x->B, st));
+    hipLaunchKernelGGL(dense_rows_kernel, dim3((unsigned)crn_cdiv(y->C, 8), (unsigned)x->B, (unsigned)zs), dim3(256), 0, st,
+                       x->base, x->sB, x->sC, w, Npad, y->C, x->C, bias, bias_sB, y->base, y->sB, y->sC, accumulate,
+                       crn_cdiv(x->C, zs));
+    CRN_CHECK_LAUNCH();
+    return CRN_OK;
+  }
+  if (sel.path == CRN_PLAN_POINTWISE) {
+    PwGeom p{};
+    p.x = x->base; p.y = y->base; p.w = w; p.bias = bias;
+    p.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
+    p.B = x->B; p.C = x->C; p.N = y->C; p.Npad = Npad; p.S = (int)Sx;
+    p.xsB = x->sB; p.ysB = y->sB; p.bias_sB = bias_sB; p.mode = accumulate ? 1 : 0;
+    p.ysC = y->sC; p.ysP = y->sW;
+    p.splits = 1; p.cps = sel.pw_cps_whole;
+    const int64_t ytot = (int64_t)y->B * y->C * Sx;
+    float* scratch = nullptr;
+    if (sel.pw_splits > 1 && (scratch = crn_splitk_scratch((size_t)sel.pw_splits * ytot, st)) != nullptr) {
+      p.splits = sel.pw_splits; p.cps = sel.pw_cps;
+      p.y = scratch; p.ysB = (int64_t)y->C * Sx; p.ysC = Sx; p.ysP = 1; p.mode = 0;
+    }
+#ifdef CRN_TOOLS
+    static const bool want_stamps = getenv("CRN_PW_STAMPS") != nullptr;
+#else
+    constexpr bool want_stamps = false;
+#endif
+    static long long* pw_stamps = nullptr;
+    if (want_stamps) {
+      if (!pw_stamps) CRN_HIP(hipMalloc(&pw_stamps, 32 * sizeof(long long)));
+      CRN_HIP(hipMemsetAsync(pw_stamps, 0, 32 * sizeof(long long), st));
+      p.stamps = pw_stamps;
+      g_pw_stamps = pw_stamps;
+    }
+    dim3 grid((unsigned)crn_cdiv(Sx, 64), (unsigned)crn_cdiv(y->C, kPwBN), (unsigned)(x->B * p.splits));
+    const size_t tab_bytes = p.tr.scale ? (size_t)2 * p.cps * sizeof(float) : 0;
+    hipLaunchKernelGGL(pointwise_fwd_kernel<kPwBN / 16>, grid, dim3(256), tab_bytes, st, p);
+    CRN_CHECK_LAUNCH();
+    return p.splits > 1 ? crn_splitk_finish(*y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
+  }
+  const FwdCfg& best = sel.cfg;
+  const int xvec = sel.xvec, lead = sel.lead;
+  splits = sel.splits;
   ConvGeom g{};
   g.x = *x; g.y = *y;
   if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
@@ -572,14 +635,8 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   g.tilesD = crn_cdiv(y->D, g.TD); g.tilesH = crn_cdiv(y->H, g.TH); g.tilesW = crn_cdiv(y->W, g.TW);
   const int NSUB = best.NSUB, CC = best.CC;
   g.CC = CC; g.WSP = pad16mod32(g.T * NSUB * 16);
-  g.nchunks = crn_cdiv(x->C, CC);
-  if (splits < 1) {   // auto split-K (atomic accumulate) only when the output grid cannot fill the chip
-    splits = forced ? (best.blocks >= 192 ? 1 : (int)std::min<int64_t>(std::min(g.nchunks, 16), crn_cdiv(256, best.blocks)))
-                    : best_splits;
-  }
-  if (splits > g.nchunks) splits = g.nchunks;
+  g.nchunks = sel.nchunks;
   g.chunks_per_split = crn_cdiv(g.nchunks, splits);
-  splits = crn_cdiv(g.nchunks, g.chunks_per_split);
   g.mode = splits > 1 ? 2 : (accumulate ? 1 : 0);
   g.lg2 = ilog2_ceil(g.PH * g.PW); g.npass = xvec ? 0 : stage_passes(CC * g.PD, g.PH * g.PW);
   g.magic_PW = magic20(g.PW); g.magic_PD = magic20(g.PD); g.magic_T = magic20(g.T);
@@ -605,11 +662,7 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   dim3 grid((unsigned)(g.tilesD * g.tilesH * g.tilesW * y->B), (unsigned)crn_cdiv(Npad, NSUB * 16),
             (unsigned)splits);
   const size_t lds_bytes = best.lds;
-  {
-    bool al = y->sW == 1 && g.mw >= 4 && (y->W & 3) == 0 && (y->sH & 3) == 0 && (y->sD & 3) == 0 && (y->sB & 3) == 0 &&
-              (y->sC & 3) == 0 && (((uintptr_t)y->base) & 15) == 0 && y->chan_off == nullptr && g.mode != 2;
-    g.vec_store = al ? 1 : 0;
-  }
+  g.vec_store = fwd_vec_store(*y, g.mw, g.mode) ? 1 : 0;
   if (boxes) {
     // groups must divide the channel counts, otherwise the information is ignored
     if (boxes->n_groups > 0 && y->C % boxes->n_groups == 0) { g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box)); }
@@ -663,9 +716,28 @@ bool wg_cand(int TD, int TH, int TW, int RSUB, int NSUB, int Cin, int Npad, int 
 }  // namespace
 
 namespace {
-// One weight-gradient launch: window kd x kh x kw, dw [Cin][T][Npad].
-int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
-                 int kd, int kh, int kw, int pd, int ph, int pw, const crnTapBoxes* boxes, hipStream_t st) {
+// ---------------- weight-gradient plan ---------------------------------------
+// As fwd_select: host arithmetic only, shared by the launch and crn_conv_wgrad_plan.
+int wgrad_check_args(const crnView* x, const crnView* dy, const float* dw, int Npad, int kd, int kh, int kw) {
+  if (!x || !dy || !dw || Npad <= 0 || (Npad & 15) || x->B != dy->B) return CRN_EINVAL;
+  if (kd * kh * kw > 512) return CRN_EINVAL;
+  return CRN_OK;
+}
+// dense layer on a 1^3 grid (stage_1)
+bool wgrad_dense(const crnView* x, const crnView* dy, int T) {
+  return T == 1 && one_position(*x) && one_position(*dy) && dy->C >= 1024;
+}
+
+struct WgSel {
+  WgCand best;
+  int xlead, dvec;                 // staging of x (>= 0: float4 units with that lead) and of dy (0 scalar, 1 float4, 2 pairs)
+  int ntiles, cblocks, nblocks;
+  int splits, tiles_per_split;     // position-tile splits the launch asks for
+  bool balanced;                   // per-group splits from the tap boxes
+};
+
+int wg_select(const crnView* x, const crnView* dy, int Npad, int kd, int kh, int kw, int pw, const crnTapBoxes* boxes,
+              WgSel* s) {
   const int T = kd * kh * kw;
   g_stage_unit = 4;                              // x patches of the weight gradient: float4 units only
   const int Dy = dy->D, Hy = dy->H, Wy = dy->W;
@@ -705,6 +777,31 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
       best = c;
     }
   }
+  s->best = best; s->xlead = xlead; s->dvec = dvec;
+  const int NB = best.NSUB * 16;
+  s->ntiles = crn_cdiv(Dy, best.TD) * crn_cdiv(Hy, best.TH) * crn_cdiv(Wy, best.TW) * dy->B;
+  s->cblocks = crn_cdiv(x->C, best.CC); s->nblocks = crn_cdiv(Npad, NB);
+  // one resident round: at most 512 (= 2 per CU) workgroups, or the stragglers double the time
+  constexpr int budget = 512;
+  int splits = std::max(1, std::min(s->ntiles, budget / (s->cblocks * s->nblocks)));
+  if (crn_deterministic()) splits = 1;                       // (the per-group splits of the launch follow: min(ntiles, ~splits))
+  s->tiles_per_split = crn_cdiv(s->ntiles, splits);
+  s->splits = crn_cdiv(s->ntiles, s->tiles_per_split);
+  s->balanced = boxes && boxes->n_groups > 0 && boxes->n_groups <= 8 && dy->C % boxes->n_groups == 0 &&
+                (dy->C / boxes->n_groups) % NB == 0;           // every block's columns belong to one group
+  return CRN_OK;
+}
+
+// One weight-gradient launch: window kd x kh x kw, dw [Cin][T][Npad].
+int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                 int kd, int kh, int kw, int pd, int ph, int pw, const crnTapBoxes* boxes, hipStream_t st) {
+  const int T = kd * kh * kw;
+  WgSel sel;
+  const int rcs = wg_select(x, dy, Npad, kd, kh, kw, pw, boxes, &sel);
+  if (rcs != CRN_OK) return rcs;
+  const WgCand& best = sel.best;
+  const int xlead = sel.xlead, dvec = sel.dvec;
+  const int Dy = dy->D, Hy = dy->H, Wy = dy->W;
   WgradGeom g{};
   g.x = *x; g.dy = *dy;
   if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
@@ -718,18 +815,10 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
   const int npos = g.TD * g.TH * g.TW;
   g.CC = CC;
   g.tilesD = crn_cdiv(Dy, g.TD); g.tilesH = crn_cdiv(Hy, g.TH); g.tilesW = crn_cdiv(Wy, g.TW);
-  g.ntiles = g.tilesD * g.tilesH * g.tilesW * dy->B;
-  const int cblocks = crn_cdiv(x->C, CC), nblocks = crn_cdiv(Npad, NB);
-  // one resident round: at most 512 (= 2 per CU) workgroups, or the stragglers double the time
-  constexpr int budget = 512;
-  int splits = std::max(1, std::min(g.ntiles, budget / (cblocks * nblocks)));
-  if (crn_deterministic()) splits = 1;                       // (the per-group splits below follow: min(ntiles, ~splits))
-  g.tiles_per_split = crn_cdiv(g.ntiles, splits);
-  splits = crn_cdiv(g.ntiles, g.tiles_per_split);
-  bool balanced = false;
-  if (boxes && boxes->n_groups > 0 && boxes->n_groups <= 8 && dy->C % boxes->n_groups == 0 &&
-      (dy->C / boxes->n_groups) % NB == 0) {           // every block's columns belong to one group
-    balanced = true;
+  g.ntiles = sel.ntiles;
+  const int cblocks = sel.cblocks, nblocks = sel.nblocks, splits = sel.splits;
+  g.tiles_per_split = sel.tiles_per_split;
+  if (sel.balanced) {
     g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box));
     // blocks of a group with fewer real taps do less MFMA work per tile: give them proportionally more
     // tiles (fewer splits), the heavy groups more splits; the total stays within the resident budget
@@ -773,12 +862,12 @@ extern "C" int crn_conv_wgrad(const crnView* x, const crnInTransform* tr, const 
                               float* dw, int Npad, int kd, int kh, int kw, int pd, int ph, int pw,
                               int zero_first, const crnTapBoxes* boxes, crnStream stream) {
   CRN_ENTRY(stream);
-  if (!x || !dy || !dw || Npad <= 0 || (Npad & 15) || x->B != dy->B) return CRN_EINVAL;
+  const int rca = wgrad_check_args(x, dy, dw, Npad, kd, kh, kw);
+  if (rca != CRN_OK) return rca;
   hipStream_t st = (hipStream_t)stream;
   const int T = kd * kh * kw;
-  if (T > 512) return CRN_EINVAL;
   if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * T * Npad * 4, st));
-  if (T == 1 && one_position(*x) && one_position(*dy) && dy->C >= 1024) {      // dense layer on a 1^3 grid (stage_1)
+  if (wgrad_dense(x, dy, T)) {
     const crnInTransform trv = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
     hipLaunchKernelGGL(dense_wgrad_kernel, dim3((unsigned)crn_cdiv(dy->C, 256), (unsigned)x->C), dim3(256), 0, st, x->base,
                        x->sB, x->sC, trv, dy->base, dy->sB, dy->sC, dw, Npad, dy->C, x->C, x->B);
@@ -789,4 +878,65 @@ extern "C" int crn_conv_wgrad(const crnView* x, const crnInTransform* tr, const 
   // group's box (conv_wgrad_kernel).  The alternative -- one launch per output parity with a smaller
   // window -- LOSES on MI355X (eight prologues and atomic epilogues: s5t1 1.02 ms vs 0.94 ms).
   return wgrad_launch(x, tr, dy, dw, Npad, kd, kh, kw, pd, ph, pw, boxes, st);
+}
+
+// ---------------- plan queries: no HIP call, nothing dereferenced but the view structs ----------------
+extern "C" int crn_conv_fwd_plan(const crnView* x, const crnInTransform* tr, const float* w, int Npad,
+                                 const float* bias, int bias_sB, const crnView* y,
+                                 int kd, int kh, int kw, int pd, int ph, int pw,
+                                 int splits, int accumulate, const crnTapBoxes* boxes, crnConvPlan* out) {
+  (void)bias; (void)bias_sB; (void)accumulate;
+  if (!out) return CRN_EINVAL;
+  const int rca = fwd_check_args(x, w, Npad, y, kd, kh, kw, boxes);
+  if (rca != CRN_OK) return rca;
+  FwdSel sel;
+  const int rcs = fwd_select(x, tr, w, Npad, y, kd, kh, kw, pd, ph, pw, splits, &sel);
+  if (rcs != CRN_OK) return rcs;
+  crnConvPlan p{};
+  p.path = sel.path; p.splits = 1; p.chunks = 1; p.lds_budget = (int)kLdsBudget;
+  if (sel.path == CRN_PLAN_DENSE_COLS) {
+    p.lds_bytes = x->B * x->C * 4 + 3 * kDenseB * 64 * 4;
+  } else if (sel.path == CRN_PLAN_DENSE_ROWS) {
+    p.splits = sel.zs; p.chunks = crn_cdiv(x->C, 256); p.lds_bytes = 4 * 8 * 4;
+  } else if (sel.path == CRN_PLAN_POINTWISE) {
+    // 64 positions x 32 columns per workgroup, K chunks of 64 (pointwise_fwd_kernel)
+    p.msub = 4; p.nsub = kPwBN / 16; p.xstage = 1; p.cc = 64; p.td = 1; p.th = 1; p.tw = 64; p.mw = 16;
+    p.splits = sel.pw_splits; p.chunks = crn_cdiv(x->C, 32);
+    p.vec_store = (sel.pw_splits > 1 || y->sW == 1) ? 1 : 0;
+    p.lds_bytes = 64 * (64 + 16) * 4 + 64 * (kPwBN + 16) * 4 + ((tr && tr->scale) ? 2 * sel.pw_cps * 4 : 0);
+  } else {
+    const FwdCfg& c = sel.cfg;
+    p.msub = c.MSUB; p.nsub = c.NSUB; p.xstage = sel.xvec; p.forced = sel.forced ? 1 : 0; p.cc = c.CC;
+    p.td = c.tsd; p.th = c.tsh * c.mh; p.tw = c.tsw * c.mw; p.mw = c.mw;
+    p.splits = sel.splits; p.chunks = sel.nchunks; p.lds_bytes = (int)c.lds;
+    // the scratch view a split launch writes is dense; whether the scratch can be had is only known at the launch
+    p.vec_store = sel.splits > 1 ? fwd_vec_store(crn_splitk_scratch_view(*y, nullptr), c.mw, 3) : fwd_vec_store(*y, c.mw, 0);
+  }
+  *out = p;
+  return CRN_OK;
+}
+
+extern "C" int crn_conv_wgrad_plan(const crnView* x, const crnInTransform* tr, const crnView* dy,
+                                   float* dw, int Npad, int kd, int kh, int kw, int pd, int ph, int pw,
+                                   int zero_first, const crnTapBoxes* boxes, crnConvPlan* out) {
+  (void)tr; (void)pd; (void)ph; (void)zero_first;
+  if (!out) return CRN_EINVAL;
+  const int rca = wgrad_check_args(x, dy, dw, Npad, kd, kh, kw);
+  if (rca != CRN_OK) return rca;
+  crnConvPlan p{};
+  p.splits = 1; p.chunks = 1; p.lds_budget = (int)kLdsBudget;
+  if (wgrad_dense(x, dy, kd * kh * kw)) {
+    p.path = CRN_PLAN_DENSE_WGRAD;
+    *out = p;
+    return CRN_OK;
+  }
+  WgSel sel;
+  const int rcs = wg_select(x, dy, Npad, kd, kh, kw, pw, boxes, &sel);
+  if (rcs != CRN_OK) return rcs;
+  p.path = CRN_PLAN_GENERIC;
+  p.msub = sel.best.RSUB; p.nsub = sel.best.NSUB; p.xstage = sel.xlead >= 0 ? 1 : 0; p.dystage = sel.dvec;
+  p.cc = sel.best.CC; p.td = sel.best.TD; p.th = sel.best.TH; p.tw = sel.best.TW;
+  p.splits = sel.splits; p.chunks = sel.ntiles; p.balanced = sel.balanced ? 1 : 0; p.lds_bytes = (int)sel.best.lds;
+  *out = p;
+  return CRN_OK;
 }

@@ -76,6 +76,35 @@ int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const float* w, int
                  int splits, int accumulate /* y += result instead of y = result */,
                  const crnTapBoxes* boxes /* may be NULL */, crnStream stream);
 
+/* Which kernel a crn_conv_fwd / crn_conv_wgrad call with these arguments gets: the selection the launch itself runs,
+ * as host arithmetic on extents, strides and alignment.  No HIP call is made and no pointer is followed except the view,
+ * transform and box structs themselves (base, chan_off, w, dw, scale are only tested for NULL and alignment), so a
+ * query needs no GPU.  Returns what the launch would return for a rejected call (CRN_EINVAL), CRN_OK otherwise.
+ * The arguments are those of the launch, the stream replaced by the plan.                                        */
+#define CRN_PLAN_DENSE_COLS 1   /* one position, many columns */
+#define CRN_PLAN_DENSE_ROWS 2   /* one position, long reduction onto few columns */
+#define CRN_PLAN_DENSE_WGRAD 3  /* weight gradient of the dense layer */
+#define CRN_PLAN_POINTWISE 4    /* 1x1x1 window on plain views */
+#define CRN_PLAN_GENERIC 5      /* tile engine: msub x nsub configuration */
+typedef struct {
+  int32_t path;             /* CRN_PLAN_* */
+  int32_t msub, nsub;       /* 16-row (forward: MSUB; weight gradient: RSUB) and 16-column MFMA blocks per wave */
+  int32_t xstage, dystage;  /* staging of x / dy: 0 scalars, 1 float4 units, 2 position pairs */
+  int32_t forced;           /* forward: scalar staging because no 16-byte configuration fits */
+  int32_t cc;               /* input channels per chunk */
+  int32_t td, th, tw;       /* position tile */
+  int32_t mw;               /* forward: width of the 16-position sub-tile */
+  int32_t splits;           /* splits the launch asks for (whether the scratch can be had is only known there) */
+  int32_t chunks;           /* what they divide: channel chunks (forward), position tiles (weight gradient) */
+  int32_t vec_store;        /* forward: float4 epilogue (a split launch writes the dense scratch) */
+  int32_t balanced;         /* weight gradient: per-group splits from the tap boxes */
+  int32_t lds_bytes, lds_budget;
+} crnConvPlan;
+int crn_conv_fwd_plan(const crnView* x, const crnInTransform* tr, const float* w, int Npad,
+                      const float* bias, int bias_sB, const crnView* y,
+                      int kd, int kh, int kw, int pd, int ph, int pw,
+                      int splits, int accumulate, const crnTapBoxes* boxes, crnConvPlan* out);
+
 /* The same operation on the split-bf16 ("bf16x3") MFMA engine (csrc/conv_bf3.hip): every fp32 operand is
  * split into two bf16 terms and a product is three v_mfma_f32_16x16x32_bf16 with fp32 accumulation
  * (hi*hi + hi*lo + lo*hi; ~2^-16 relative per product instead of fp32's 2^-24).  A throughput mode for
@@ -156,6 +185,10 @@ int crn_conv_wgrad(const crnView* x, const crnInTransform* tr, const crnView* dy
                    float* dw, int Npad, int kd, int kh, int kw, int pd, int ph, int pw,
                    int zero_first, const crnTapBoxes* boxes /* may be NULL; entries of dw at structural zeros may be left untouched */,
                    crnStream stream);
+
+int crn_conv_wgrad_plan(const crnView* x, const crnInTransform* tr, const crnView* dy,
+                        float* dw, int Npad, int kd, int kh, int kw, int pd, int ph, int pw,
+                        int zero_first, const crnTapBoxes* boxes, crnConvPlan* out);
 
 /* The weight gradient on the split-bf16 MFMA engine (csrc/conv_bf3.hip; see crn_conv_fwd_bf3): same packed
  * dw, same zero_first contract; CRN_EINVAL for shapes it does not cover (windows other than 5^3 / 4^3, dy W neither
