@@ -46,6 +46,14 @@ class CrnConvPlan(C.Structure):
                                         "splits", "chunks", "vec_store", "balanced", "lds_bytes", "lds_budget")]
 
 
+class CrnBf3Plan(C.Structure):
+  """Mirror of crnBf3Plan (include/corenet_hip.h)."""
+  _fields_ = [(n, C.c_int32) for n in ("kind", "nsub", "xmode", "ng", "slabs", "td", "th", "tw", "splits", "chunks", "per_split",
+                                        "vec_store", "mode", "rowskip", "half_last", "lead", "n_groups", "c_groups", "nparts",
+                                        "dmode", "tpw", "twt", "pipe", "inherit", "boxskip", "lds_bytes")]
+
+
+BF3_KINDS = {0: "plain", 1: "half", 2: "ws"}
 PLAN_PATHS = {1: "dense_cols", 2: "dense_rows", 3: "dense_wgrad", 4: "pointwise", 5: "generic"}
 
 
@@ -84,6 +92,10 @@ _SIGS = {
                            i32, i32, i32, i32, i32, i32, i32, vp],
     "crn_conv_wgrad_bf3_boxes": [C.POINTER(CrnView), C.POINTER(CrnInTransform), C.POINTER(CrnView), vp, i32,
                                  i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "crn_conv_fwd_bf3_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, vp, i32, vp, i32,
+                              C.POINTER(CrnView), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "crn_conv_wgrad_bf3_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), C.POINTER(CrnView), vp, i32,
+                                i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "crn_conv_wgrad": [C.POINTER(CrnView), C.POINTER(CrnInTransform), C.POINTER(CrnView), vp, i32,
                        i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "crn_bf3_operands": [vp, vp, i32, i64, vp, vp],

@@ -133,6 +133,27 @@ class HipBackend:
                                  window[2], pad_lo[0], pad_lo[1], pad_lo[2], int(zero_first), _ctapboxes(boxes), C.byref(p))
     return self._plan_dict(p)
 
+  def conv_fwd_bf3_plan(self, x: View, tr: Optional[Transform], w: Optional[t.Tensor], npad: int, bias: Optional[t.Tensor],
+                        bias_sB: int, y: View, window, pad_lo, accumulate: bool = False, boxes=None, wslab=None, fuse=None) -> dict:
+    """What conv_fwd(math="bf16x3") would launch (crn_conv_fwd_bf3_plan): a dict of the crnBf3Plan fields, kind by name.  fuse: a
+    _lib.CrnBnBwdFuse, the request of conv_dgrad_bn_bwd (x set) or conv_fwd_stats (x NULL).  Host arithmetic only, as
+    conv_fwd_plan; a rejected call raises HipError."""
+    p = _lib.CrnBf3Plan()
+    self.lib.crn_conv_fwd_bf3_plan(C.byref(_cview(x)), _ctr(tr), None if wslab is not None else ptr(w), ptr(wslab), npad, ptr(bias),
+                                   bias_sB, C.byref(_cview(y)), window[0], window[1], window[2], pad_lo[0], pad_lo[1], pad_lo[2],
+                                   int(accumulate), _ctapboxes(boxes), None if fuse is None else C.addressof(fuse), C.addressof(p))
+    d = {n: int(getattr(p, n)) for n, _ in p._fields_}
+    d["kind"] = _lib.BF3_KINDS[d["kind"]]
+    return d
+
+  def conv_wgrad_bf3_plan(self, x: View, tr: Optional[Transform], dy: View, dw: t.Tensor, npad: int, window, pad_lo,
+                          zero_first: bool = True, boxes=None) -> dict:
+    """What conv_wgrad(math="bf16x3") would launch (crn_conv_wgrad_bf3_plan); see conv_fwd_bf3_plan."""
+    p = _lib.CrnBf3Plan()
+    self.lib.crn_conv_wgrad_bf3_plan(C.byref(_cview(x)), _ctr(tr), C.byref(_cview(dy)), ptr(dw), npad, window[0], window[1],
+                                     window[2], pad_lo[0], pad_lo[1], pad_lo[2], int(zero_first), _ctapboxes(boxes), C.addressof(p))
+    return {n: int(getattr(p, n)) for n, _ in p._fields_}
+
   def conv_fwd_stats(self, x: View, tr: Optional[Transform], wslab: t.Tensor, npad: int, bias, bias_sB: int, y: View, window,
                      pad_lo, boxes, Cn: int, pre_relu: bool) -> int:
     """conv_fwd(math="bf16x3", wslab) that also leaves the partial sums of the BatchRenorm behind it in this stream's

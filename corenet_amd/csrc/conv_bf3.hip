@@ -1345,21 +1345,28 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
 
 #undef ucount
 
+// software-pipelined LDS reads: measured per variant (profiles/r03_wgrad_pipe_ab.txt)
+constexpr bool bf3_wg_pipe(int NSUB, int TPW, int TWT) { return NSUB == 1 || (TPW == 8 && TWT == 16); }
+
 template <int NSUB, int DM, int TPW, int TWT>
 int launch_bf3_wgrad(const Bf3WgGeom& g, dim3 grid, size_t lds, hipStream_t st) {
-  // software-pipelined LDS reads: measured per variant (profiles/r03_wgrad_pipe_ab.txt)
-  constexpr bool pipe = NSUB == 1 || (TPW == 8 && TWT == 16);
+  constexpr bool pipe = bf3_wg_pipe(NSUB, TPW, TWT);
   auto k = conv_bf3_wgrad_kernel<NSUB, DM, TPW, TWT, pipe>;
   return crn_launch(k, grid, dim3(kThreads), lds, st, g);
 }
 
 unsigned magic20b(int d) { return (unsigned)(((1u << 20) + d - 1) / d); }
 
+// the geometry conv_bf3_half_kernel is written for (of the NSUB 1, unit-stride, ZS 1 kernels)
+bool bf3_half_shape(const Bf3Geom& g) {
+  return g.half_last && g.PW == 20 && g.mw == 16 && g.mh == 1 && g.nsw == 1 && g.nsh == 8;
+}
+
 template <int NSUB, int XM, int NG, int ZS>
 int launch_bf3(const Bf3Geom& g, dim3 grid, size_t lds, hipStream_t st) {
   auto k = g.wslab ? conv_bf3_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_kernel<NSUB, XM, NG, ZS, false>;
   if constexpr (NSUB == 1 && XM == 1 && ZS == 1)         // (instantiated where a model layer needs it: stage_6.c1, 28 channels)
-    if (g.half_last && g.PW == 20 && g.mw == 16 && g.mh == 1 && g.nsw == 1 && g.nsh == 8) k = g.wslab ? conv_bf3_half_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_half_kernel<NSUB, XM, NG, ZS, false>;
+    if (bf3_half_shape(g)) k = g.wslab ? conv_bf3_half_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_half_kernel<NSUB, XM, NG, ZS, false>;
   return crn_launch(k, grid, dim3(kThreads), lds, st, g);
 }
 
@@ -1464,20 +1471,33 @@ extern "C" int crn_conv_fwd_bf3_slabs_stats(const crnView* x, const crnInTransfo
 }
 
 namespace {
-int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
-                      const float* bias, int bias_sB, const crnView* y, int kd, int kh, int kw, int pd, int ph, int pw,
-                      int accumulate, const crnTapBoxes* boxes, crnStream stream, crnBnBwdFuse* fuse) {
-  if (fuse) fuse->nparts = 0;
+// The instantiated forward kernels (NSUB, x staging, NG, ZS), each with staged weights and with slabs; NSUB 1 on unit-stride
+// x also as conv_bf3_half_kernel (launch_bf3).  Stride-2 staging exists for 4x4 planes only.
+#define CRN_BF3_CASES(X) X(1, 1, 7, 1) X(2, 1, 7, 1) X(4, 1, 7, 1) X(1, 1, 4, 1) X(2, 1, 4, 1) X(4, 1, 4, 1) \
+                         X(1, 2, 4, 1) X(2, 2, 4, 1) X(4, 2, 4, 1)
+
+// What a forward launch is: everything between the argument checks and the kernel ladder, host arithmetic on the views
+// (no HIP call), shared by conv_fwd_bf3_impl and crn_conv_fwd_bf3_plan so that there is one copy of the selection.
+// bf3_fwd_select holds every rejection; bf3_fwd_place finishes the geometry once the launch knows whether it has the
+// split-K scratch.
+struct Bf3FwdSel {
+  Bf3Geom g;
+  crnView yreal;
+  int xmode, NSUB, ZS, splits, kind;       // kind: CRN_BF3_PLAIN / HALF / WS
+  int64_t tiles;
+  size_t lds;
+};
+
+int bf3_fwd_select(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
+                   const float* bias, int bias_sB, const crnView* y, int kd, int kh, int kw, int pd, int ph, int pw,
+                   const crnTapBoxes* boxes, Bf3FwdSel* s) {
   if (boxes && (boxes->n_groups < 0 || boxes->n_groups > 8 || boxes->c_groups < 0 || boxes->c_groups > 8)) return CRN_EINVAL;
   if (!x || !y || (!w && !wslab) || Npad <= 0 || (Npad & 15) || x->B != y->B || kd < 1 || kh < 1 || kw < 1) return CRN_EINVAL;
   if (y->C > Npad || x->C > kTabC) return CRN_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  int rcf;
-  const bool armed = crn_splitk_begin(st, &rcf);
-  if (rcf != CRN_OK) return rcf;
   const int xmode = even_view(*x) ? 1 : ((x->sW == 2 && x->chan_off != nullptr && (x->W & 1) == 0) ? 2 : 0);
   if (!xmode) return CRN_EINVAL;
-  Bf3Geom g{};
+  Bf3Geom& g = s->g;
+  g = Bf3Geom{};
   g.x = *x; g.y = *y;
   g.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
   g.w = w; g.wslab = wslab; g.bias = bias; g.Npad = Npad; g.bias_sB = bias_sB;
@@ -1505,7 +1525,6 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
     if (boxes->c_groups > 0 && x->C % boxes->c_groups == 0) { g.c_groups = boxes->c_groups; memcpy(g.c_box, boxes->c_box, sizeof(g.c_box)); }
   }
   const int64_t tiles = (int64_t)g.tilesD * g.tilesH * g.tilesW * y->B;
-  const int KD = g.NG == 7 ? 5 : 4;                   // window depth of the instantiated whole-window slabs
   g.ctab = (x->C + 15) & ~15;
   auto lds_of = [&](int nsub, int zs) { return (size_t)(3 * g.ctab * 4) + (size_t)2 * g.NP * 16 + (size_t)2 * zs * g.NG * 4 * nsub * 16 * 16; };
   // N block (NSUB x 16 columns per workgroup), measured per layer with the pre-arranged weight slabs (tools/bf3bench.sh
@@ -1533,45 +1552,93 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   // 909 -> 841; forwards 154 -> 185, 194 -> 229, 817 -> 996; inside the step ZS = 4 on the data gradients alone: 7.72 vs
   // 7.62 ms (the 24 KiB of extra LDS meet the weight-gradient kernels of the other stream).  ZS stays 1.
   const int ZS = 1;
-  (void)KD;
   const size_t lds = lds_of(NSUB, ZS);
   if (lds > kLdsMax) return CRN_EINVAL;
   if ((int64_t)x->C * g.T * Npad >= ((int64_t)1 << 29)) return CRN_EINVAL;
+  bool instantiated = false;
+#define CRN_BF3_CASE(N, X, G, Z) instantiated = instantiated || (NSUB == N && xmode == X && g.NG == G && ZS == Z);
+  CRN_BF3_CASES(CRN_BF3_CASE)
+#undef CRN_BF3_CASE
+  if (!instantiated) return CRN_EINVAL;               // a stride-2 x under 5x5 window planes
   // split-K over the channel chunks: partial sums to the shared scratch, one reduction launch
   const int64_t blocks = tiles * crn_cdiv(Npad, NSUB * 16);
   int splits = 1;
   if (blocks < 192) splits = (int)std::min<int64_t>(std::min(g.nchunks, 16), crn_cdiv(256, blocks));
   g.chunks_per_split = crn_cdiv(g.nchunks, splits);
   splits = crn_cdiv(g.nchunks, g.chunks_per_split);
+  s->yreal = *y; s->xmode = xmode; s->NSUB = NSUB; s->ZS = ZS; s->splits = splits; s->kind = CRN_BF3_PLAIN;
+  s->tiles = tiles; s->lds = lds;
+  return CRN_OK;
+}
+
+// scratch: where the partial sums of a launch that wants to split go; have_scratch false: there is none, it does not split
+void bf3_fwd_place(Bf3FwdSel* s, bool have_scratch, float* scratch, int accumulate, crnBnBwdFuse* fuse) {
+  Bf3Geom& g = s->g;
+  const crnView* y = &s->yreal;
+  const int NSUB = s->NSUB, xmode = s->xmode;
   g.mode = accumulate ? 1 : 0;
-  const crnView yreal = *y;
-  float* scratch = nullptr;
-  // the partial sums: added up by a reduction launch -- or, after crn_splitk_defer, by the BatchRenorm launch that reads
-  // this (dense) output next (decoder stages 2-4: statistics after c1, the norms' backward after both data gradients)
-  auto finish_splits = [&]() { return crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st); };
-  if (splits > 1) {
-    scratch = crn_splitk_scratch((size_t)splits * y->B * y->C * y->D * y->H * y->W, st);
-    if (!scratch) { splits = 1; g.chunks_per_split = g.nchunks; }
-    else { g.mode = 3; g.y = crn_splitk_scratch_view(yreal, scratch); }
+  if (s->splits > 1) {
+    if (!have_scratch) { s->splits = 1; g.chunks_per_split = g.nchunks; }
+    else { g.mode = 3; g.y = crn_splitk_scratch_view(s->yreal, scratch); }
   }
   const crnView& yo = g.y;
   g.vec_store = (g.mw >= 4 && yo.sW == 1 && (yo.W & 3) == 0 && (yo.sH & 3) == 0 && (yo.sD & 3) == 0 && (yo.sB & 3) == 0 &&
                  (yo.sC & 3) == 0 && (((uintptr_t)yo.base) & 15) == 0 && yo.chan_off == nullptr) ? 1 : 0;
-  const int64_t tiles_bn = tiles;
+  const int64_t tiles_bn = s->tiles;
   // two users of this epilogue: the BatchRenorm BACKWARD sums of a data gradient (fuse->x = the norm's input)
   // and the forward STATISTICS of the next norm (fuse->x == nullptr: crn_conv_fwd_bf3_slabs_stats), which knows nothing of
   // x / sB_x / ndsum
   const bool stats_mode = fuse && fuse->x == nullptr;
   const bool mode_ok = fuse && (stats_mode || (fuse->ndsum <= kThreads && (fuse->sB_x & 3) == 0 &&
                                                (((uintptr_t)fuse->x) & 15) == 0));
-  if (mode_ok && splits == 1 && g.vec_store && y->sW == 1 && tiles_bn <= 0x7fffffff &&
+  if (mode_ok && s->splits == 1 && g.vec_store && y->sW == 1 && tiles_bn <= 0x7fffffff &&
       fuse->ws_bytes >= (size_t)y->C * (size_t)tiles_bn * 2 * sizeof(double) && (((int64_t)y->D * y->H * y->W) & 3) == 0) {
     g.bn_x = fuse->x; g.bn_sB = fuse->sB_x; g.bn_S = (int64_t)y->D * y->H * y->W; g.bn_saved = fuse->saved;
     g.bn_pre_relu = fuse->pre_relu; g.bn_ws = fuse->ws; g.bn_dsum = fuse->dsum; g.bn_ndsum = fuse->dsum ? fuse->ndsum : 0;
     fuse->nparts = (int)tiles_bn;
   }
-  g.rowskip = (kh == 4 && kw == 4 && (g.n_groups > 0 || g.c_groups > 0)) ? 1 : 0;
-  g.half_last = (x->C % kCK >= 1 && x->C % kCK <= 4 && ZS == 1) ? 1 : 0;
+  g.rowskip = (g.kh == 4 && g.kw == 4 && (g.n_groups > 0 || g.c_groups > 0)) ? 1 : 0;
+  g.half_last = (g.x.C % kCK >= 1 && g.x.C % kCK <= 4 && s->ZS == 1) ? 1 : 0;
+  // the wave-specialised kernel (conv_bf3_ws_kernel): pre-arranged slabs, 4 x 8 x 16 tiles, N blocks of 16 / 32
+  // columns, cubic 5^3 / 4^3 windows
+  // Where it is used is measured (tools/ws_ab.sh, profiles/r03_ws_ab.txt, B = 4): it wins where a step is long -- N blocks
+  // of 32 columns on 5^3 windows (stage_6.c1 data gradient 359 -> 336 us, stage_5.c1 forward 181 -> 161 us) -- and loses
+  // on the 16-column blocks (stage_6.c1 forward 426 -> 486 us, stage_6.t1 160 -> 190 us): there a step is 2.7 k cycles of
+  // MFMA fed by 2.2 k cycles of LDS reads (one A fragment pair per three MFMAs), and the ~0.9 k cycles of DMA issue, slab
+  // wait and barrier per step cost more than two co-resident workgroups of the kernel above lose.
+  if (NSUB == 2 && g.NG == 7 && g.wslab && xmode == 1 && g.mw == 16 && g.kd == 5) {
+    const int UP = g.PH * g.pw2;
+    const int NB = NSUB * 16;
+    const size_t lds_ws = (size_t)(3 * g.ctab * 4) + 256 + (size_t)2 * kWsR * g.PHW * 16 + (size_t)4 * g.NG * 4 * NB * 16;
+    const int nch = std::min(g.chunks_per_split, g.nchunks);
+    const bool ok = 2 * UP <= kWsPL && lds_ws <= kLdsMax && nch <= 64 &&
+                    bf3_ws_timetable_ok<5>(nch);
+    if (ok) {
+      g.UP = UP; g.magic_UP = magic20b(UP);
+      s->kind = CRN_BF3_WS; s->lds = lds_ws;
+      return;
+    }
+  }
+  if (NSUB == 1 && xmode == 1 && s->ZS == 1 && bf3_half_shape(g)) s->kind = CRN_BF3_HALF;
+}
+
+int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
+                      const float* bias, int bias_sB, const crnView* y, int kd, int kh, int kw, int pd, int ph, int pw,
+                      int accumulate, const crnTapBoxes* boxes, crnStream stream, crnBnBwdFuse* fuse) {
+  if (fuse) fuse->nparts = 0;
+  Bf3FwdSel s;
+  const int rcs = bf3_fwd_select(x, tr, w, wslab, Npad, bias, bias_sB, y, kd, kh, kw, pd, ph, pw, boxes, &s);
+  if (rcs != CRN_OK) return rcs;          // before crn_splitk_begin: the arming stays for the engine the caller falls back to
+  hipStream_t st = (hipStream_t)stream;
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
+  float* scratch = nullptr;
+  if (s.splits > 1) scratch = crn_splitk_scratch((size_t)s.splits * y->B * y->C * y->D * y->H * y->W, st);
+  bf3_fwd_place(&s, scratch != nullptr, scratch, accumulate, fuse);
+  Bf3Geom& g = s.g;
+  const int NSUB = s.NSUB, xmode = s.xmode, ZS = s.ZS, splits = s.splits;
+  const size_t lds = s.lds;
 #ifdef CRN_TOOLS
   static const bool want_stamps = getenv("CRN_BF3_STAMPS") != nullptr;
 #else
@@ -1582,38 +1649,44 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
     CRN_HIP(hipMemsetAsync(g_bf3_stamps, 0, 24 * 8 * sizeof(long long), st));
     g.stamps = g_bf3_stamps;
   }
-  dim3 grid((unsigned)tiles, (unsigned)crn_cdiv(Npad, NSUB * 16), (unsigned)splits);
+  dim3 grid((unsigned)s.tiles, (unsigned)crn_cdiv(Npad, NSUB * 16), (unsigned)splits);
   int rc = CRN_EINVAL;
-  // the wave-specialised kernel (conv_bf3_ws_kernel): pre-arranged slabs, 4 x 8 x 16 tiles, N blocks of 16 / 32
-  // columns, cubic 5^3 / 4^3 windows
-  // Where it is used is measured (tools/ws_ab.sh, profiles/r03_ws_ab.txt, B = 4): it wins where a step is long -- N blocks
-  // of 32 columns on 5^3 windows (stage_6.c1 data gradient 359 -> 336 us, stage_5.c1 forward 181 -> 161 us) -- and loses
-  // on the 16-column blocks (stage_6.c1 forward 426 -> 486 us, stage_6.t1 160 -> 190 us): there a step is 2.7 k cycles of
-  // MFMA fed by 2.2 k cycles of LDS reads (one A fragment pair per three MFMAs), and the ~0.9 k cycles of DMA issue, slab
-  // wait and barrier per step cost more than two co-resident workgroups of the kernel above lose.
-  if (NSUB == 2 && g.NG == 7 && wslab && xmode == 1 && g.mw == 16 && kd == 5) {
-    Bf3Geom gw = g;
-    gw.UP = gw.PH * gw.pw2; gw.magic_UP = magic20b(gw.UP);
-    const int NB = NSUB * 16;
-    const size_t lds_ws = (size_t)(3 * gw.ctab * 4) + 256 + (size_t)2 * kWsR * gw.PHW * 16 + (size_t)4 * gw.NG * 4 * NB * 16;
-    const int nch = std::min(g.chunks_per_split, g.nchunks);
-    const bool ok = 2 * gw.UP <= kWsPL && lds_ws <= kLdsMax && nch <= 64 &&
-                    bf3_ws_timetable_ok<5>(nch);
-    if (ok) {
-      rc = launch_bf3_ws<2, 1, 7>(gw, grid, lds_ws, st);
-      if (rc == CRN_OK && g.mode == 3) rc = finish_splits();
-      return rc;
-    }
-  }
+  if (s.kind == CRN_BF3_WS) {
+    rc = launch_bf3_ws<2, 1, 7>(g, grid, lds, st);
+  } else {
 #define CRN_BF3_CASE(N, X, G, Z) if (NSUB == N && xmode == X && g.NG == G && ZS == Z) rc = launch_bf3<N, X, G, Z>(g, grid, lds, st);
-  CRN_BF3_CASE(1, 1, 7, 1) CRN_BF3_CASE(2, 1, 7, 1) CRN_BF3_CASE(4, 1, 7, 1)
-  CRN_BF3_CASE(1, 1, 4, 1) CRN_BF3_CASE(2, 1, 4, 1) CRN_BF3_CASE(4, 1, 4, 1)
-  CRN_BF3_CASE(1, 2, 4, 1) CRN_BF3_CASE(2, 2, 4, 1) CRN_BF3_CASE(4, 2, 4, 1)
+    CRN_BF3_CASES(CRN_BF3_CASE)
 #undef CRN_BF3_CASE
-  if (rc == CRN_OK && g.mode == 3) rc = finish_splits();
+  }
+  // the partial sums: added up by a reduction launch -- or, after crn_splitk_defer, by the BatchRenorm launch that reads
+  // this (dense) output next (decoder stages 2-4: statistics after c1, the norms' backward after both data gradients)
+  if (rc == CRN_OK && g.mode == 3) rc = crn_splitk_finish(s.yreal, scratch, splits, accumulate, armed, st);
   return rc;
 }
 }  // namespace
+
+extern "C" int crn_conv_fwd_bf3_plan(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
+                                     const float* bias, int bias_sB, const crnView* y,
+                                     int kd, int kh, int kw, int pd, int ph, int pw,
+                                     int accumulate, const crnTapBoxes* boxes, const crnBnBwdFuse* fuse, crnBf3Plan* out) {
+  if (!out || (w != nullptr) == (wslab != nullptr)) return CRN_EINVAL;
+  if (fuse && (!wslab || !fuse->ws || (fuse->x && !fuse->saved))) return CRN_EINVAL;
+  Bf3FwdSel s;
+  const int rcs = bf3_fwd_select(x, tr, w, wslab, Npad, bias, bias_sB, y, kd, kh, kw, pd, ph, pw, boxes, &s);
+  if (rcs != CRN_OK) return rcs;
+  crnBnBwdFuse f{};
+  if (fuse) { f = *fuse; f.nparts = 0; }
+  bf3_fwd_place(&s, true, nullptr, accumulate, fuse ? &f : nullptr);      // (a scratch is 16-byte aligned, as nullptr is)
+  const Bf3Geom& g = s.g;
+  crnBf3Plan p{};
+  p.kind = s.kind; p.nsub = s.NSUB; p.xmode = s.xmode; p.ng = g.NG; p.slabs = wslab ? 1 : 0;
+  p.td = g.TD; p.th = g.TH; p.tw = g.TW;
+  p.splits = s.splits; p.chunks = g.nchunks; p.per_split = g.chunks_per_split;
+  p.vec_store = g.vec_store; p.mode = g.mode; p.rowskip = g.rowskip; p.half_last = g.half_last; p.lead = g.lead;
+  p.n_groups = g.n_groups; p.c_groups = g.c_groups; p.nparts = f.nparts; p.lds_bytes = (int)s.lds;
+  *out = p;
+  return CRN_OK;
+}
 
 // Weight gradient on the split-bf16 MFMA engine; same contract as crn_conv_wgrad (dw zeroed by the caller or
 // zero_first).  Returns CRN_EINVAL for shapes it does not cover.
@@ -1626,19 +1699,31 @@ extern "C" int crn_conv_wgrad_bf3(const crnView* x, const crnInTransform* tr, co
 }
 // ... with the tap boxes of the output columns (transposed convolutions, conv_geometry.convt_fwd): window rows that hold only
 // structural zeros for a workgroup's columns are not multiplied (their dw entries stay what they were: zero)
-extern "C" int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
-                                        int kd, int kh, int kw, int pd, int ph, int pw, int zero_first,
-                                        const crnTapBoxes* boxes, crnStream stream) {
-  CRN_ENTRY(stream);
+namespace {
+// The instantiated weight-gradient kernels (NSUB, dy staging, tap pairs per wave, tile width).  Not among them: 8 pairs per
+// wave on a stride-2 dy, and 4 pairs per wave on a unit-stride dy with 8-wide tiles.
+#define CRN_BF3WG_CASES(X) X(1, 1, 8, 16) X(2, 1, 8, 16) X(1, 2, 4, 16) X(2, 2, 4, 16) X(1, 1, 4, 16) X(2, 1, 4, 16) \
+                           X(1, 1, 8, 8) X(2, 1, 8, 8) X(1, 2, 4, 8) X(2, 2, 4, 8)
+
+// As bf3_fwd_select: every rejection and every choice of the weight-gradient launch, host arithmetic only, shared with
+// crn_conv_wgrad_bf3_plan.
+struct Bf3WgSel {
+  Bf3WgGeom g;
+  int NSUB, dmode, TPW, TWT, splits, cblocks, nblocks;
+  size_t lds;
+};
+
+int bf3_wg_select(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                  int kd, int kh, int kw, int pd, int ph, int pw, const crnTapBoxes* boxes, Bf3WgSel* s) {
   if (boxes && (boxes->n_groups < 0 || boxes->n_groups > 8 || boxes->c_groups < 0 || boxes->c_groups > 8)) return CRN_EINVAL;
   if (!x || !dy || !dw || Npad <= 0 || (Npad & 15) || x->B != dy->B || kd < 1 || kh < 1 || kw < 1) return CRN_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
   if (!even_view(*x)) return CRN_EINVAL;
   const int dmode = even_view(*dy) ? 1 : ((dy->sW == 2 && dy->chan_off != nullptr && (dy->W & 1) == 0) ? 2 : 0);
   if (!dmode) return CRN_EINVAL;
   const int TWT = (dy->W % 16 == 0) ? 16 : 8, TDT = TWT == 16 ? 4 : 8;
   if (dy->W % TWT || dy->H < 8 || dy->D < TDT) return CRN_EINVAL;
-  Bf3WgGeom g{};
+  Bf3WgGeom& g = s->g;
+  g = Bf3WgGeom{};
   g.x = *x; g.dy = *dy;
   g.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
   g.dw = dw; g.Npad = Npad; g.ncols = std::min(Npad, dy->C);
@@ -1654,11 +1739,15 @@ extern "C" int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* 
   g.tilesD = crn_cdiv(dy->D, TDT); g.tilesH = crn_cdiv(dy->H, 8); g.tilesW = dy->W / TWT;
   g.ntiles = g.tilesD * g.tilesH * g.tilesW * dy->B;
   g.magic_pw2 = magic20b(g.pw2); g.magic_PH = magic20b(g.PH); g.magic_kw = magic20b(kw); g.magic_KHW = magic20b(g.KHW);
-  if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * g.T * Npad * 4, st));
-  int NSUB = (Npad % 32 == 0) ? 2 : 1;
+  const int NSUB = (Npad % 32 == 0) ? 2 : 1;
   const int NB = NSUB * 16;
   const size_t lds = 1024 + (size_t)2 * g.NP * 16 + (size_t)2 * kWgTile * NB * 2;
   if (lds > 160 * 1024 - 512) return CRN_EINVAL;
+  bool instantiated = false;
+#define CRN_BF3WG_CASE(N, D, P, W) instantiated = instantiated || (NSUB == N && dmode == D && TPW == P && TWT == W);
+  CRN_BF3WG_CASES(CRN_BF3WG_CASE)
+#undef CRN_BF3WG_CASE
+  if (!instantiated) return CRN_EINVAL;
   const int cblocks = crn_cdiv(x->C, kCK), nblocks = crn_cdiv(Npad, NB);
   constexpr int kBlocks = 256;
   int splits = std::max(1, std::min(g.ntiles, kBlocks / std::max(1, cblocks * nblocks)));
@@ -1671,13 +1760,45 @@ extern "C" int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* 
   if (boxes && boxes->n_groups > 0 && dy->C % boxes->n_groups == 0 && kw == 4) {
     g.boxskip = 1; g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box));
   }
-  dim3 grid((unsigned)cblocks, (unsigned)nblocks, (unsigned)splits);
-#define CRN_BF3WG_CASE(N, D, P, W) if (NSUB == N && dmode == D && TPW == P && TWT == W) return launch_bf3_wgrad<N, D, P, W>(g, grid, lds, st);
-  CRN_BF3WG_CASE(1, 1, 8, 16) CRN_BF3WG_CASE(2, 1, 8, 16)
-  CRN_BF3WG_CASE(1, 2, 4, 16) CRN_BF3WG_CASE(2, 2, 4, 16)
-  CRN_BF3WG_CASE(1, 1, 4, 16) CRN_BF3WG_CASE(2, 1, 4, 16)
-  CRN_BF3WG_CASE(1, 1, 8, 8) CRN_BF3WG_CASE(2, 1, 8, 8)
-  CRN_BF3WG_CASE(1, 2, 4, 8) CRN_BF3WG_CASE(2, 2, 4, 8)
+  s->NSUB = NSUB; s->dmode = dmode; s->TPW = TPW; s->TWT = TWT; s->splits = splits; s->cblocks = cblocks; s->nblocks = nblocks;
+  s->lds = lds;
+  return CRN_OK;
+}
+}  // namespace
+
+extern "C" int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                                        int kd, int kh, int kw, int pd, int ph, int pw, int zero_first,
+                                        const crnTapBoxes* boxes, crnStream stream) {
+  CRN_ENTRY(stream);
+  Bf3WgSel s;
+  const int rcs = bf3_wg_select(x, tr, dy, dw, Npad, kd, kh, kw, pd, ph, pw, boxes, &s);
+  if (rcs != CRN_OK) return rcs;
+  hipStream_t st = (hipStream_t)stream;
+  const Bf3WgGeom& g = s.g;
+  const int NSUB = s.NSUB, dmode = s.dmode, TPW = s.TPW, TWT = s.TWT;
+  // behind the last rejection: a rejected call writes nothing
+  if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * g.T * Npad * 4, st));
+  dim3 grid((unsigned)s.cblocks, (unsigned)s.nblocks, (unsigned)s.splits);
+#define CRN_BF3WG_CASE(N, D, P, W) if (NSUB == N && dmode == D && TPW == P && TWT == W) return launch_bf3_wgrad<N, D, P, W>(g, grid, s.lds, st);
+  CRN_BF3WG_CASES(CRN_BF3WG_CASE)
 #undef CRN_BF3WG_CASE
   return CRN_EINVAL;
+}
+
+extern "C" int crn_conv_wgrad_bf3_plan(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                                       int kd, int kh, int kw, int pd, int ph, int pw, int zero_first,
+                                       const crnTapBoxes* boxes, crnBf3Plan* out) {
+  (void)zero_first;
+  if (!out) return CRN_EINVAL;
+  Bf3WgSel s;
+  const int rcs = bf3_wg_select(x, tr, dy, dw, Npad, kd, kh, kw, pd, ph, pw, boxes, &s);
+  if (rcs != CRN_OK) return rcs;
+  const Bf3WgGeom& g = s.g;
+  crnBf3Plan p{};
+  p.nsub = s.NSUB; p.dmode = s.dmode; p.tpw = s.TPW; p.twt = s.TWT; p.pipe = bf3_wg_pipe(s.NSUB, s.TPW, s.TWT) ? 1 : 0;
+  p.td = s.TWT == 16 ? 4 : 8; p.th = 8; p.tw = s.TWT;
+  p.splits = s.splits; p.chunks = g.ntiles; p.per_split = g.tiles_per_split;
+  p.inherit = g.inherit; p.boxskip = g.boxskip; p.n_groups = g.n_groups; p.lead = g.lead; p.lds_bytes = (int)s.lds;
+  *out = p;
+  return CRN_OK;
 }

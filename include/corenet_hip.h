@@ -109,8 +109,15 @@ int crn_conv_fwd_plan(const crnView* x, const crnInTransform* tr, const float* w
  * split into two bf16 terms and a product is three v_mfma_f32_16x16x32_bf16 with fp32 accumulation
  * (hi*hi + hi*lo + lo*hi; ~2^-16 relative per product instead of fp32's 2^-24).  A throughput mode for
  * the big decoder layers (reconstruction_decoder.py:72-95), selected per layer by the host; the fp32
- * engine above stays the parity default.  Returns CRN_EINVAL for shapes it does not cover
- * (output W not a multiple of 16, views other than unit-stride / stride-2 space-to-depth, Cin > 256).   */
+ * engine above stays the parity default.  Returns CRN_EINVAL, before anything is written and without consuming the arming
+ * of crn_splitk_defer, for calls it does not cover.  Covered:
+ *   window  kd <= 8 and kh*kw in 13..16 (four tap groups) or 25..28 (seven): 4x4 and 5x5 planes, but also 2x7, 3x5, ...;
+ *           at most 1024 staging units per patch (rules out 5x5 planes with kd = 8 on 8^3 tiles and the like)
+ *   y       W a multiple of 16 with H >= 8, D >= 4 (tiles of 4 x 8 x 16 positions), or W == 8 with H even and >= 8,
+ *           D >= 8 (tiles of 8 x 8 x 8); D and H need not be whole tiles; any strides; y->C <= Npad, Npad % 16 == 0
+ *   x       unit W stride without channel table, every extent and stride even, 8-byte aligned base -- or a stride-2
+ *           view with channel table and even W (4x4 planes only); x->C <= 512; x->C * taps * Npad < 2^29
+ *   pads    any (an odd pw costs one leading patch column)                                                        */
 int crn_conv_fwd_bf3(const crnView* x, const crnInTransform* tr, const float* w, int Npad,
                      const float* bias, int bias_sB, const crnView* y,
                      int kd, int kh, int kw, int pd, int ph, int pw,
@@ -191,8 +198,11 @@ int crn_conv_wgrad_plan(const crnView* x, const crnInTransform* tr, const crnVie
                         int zero_first, const crnTapBoxes* boxes, crnConvPlan* out);
 
 /* The weight gradient on the split-bf16 MFMA engine (csrc/conv_bf3.hip; see crn_conv_fwd_bf3): same packed
- * dw, same zero_first contract; CRN_EINVAL for shapes it does not cover (windows other than 5^3 / 4^3, dy W neither
- * a multiple of 16 nor 8, views other than unit-stride x and unit-stride / stride-2 space-to-depth dy).       */
+ * dw, same zero_first contract; CRN_EINVAL, before anything is written (the zero_first memset included), for calls it
+ * does not cover.  Covered: windows of 57..64 tap pairs (5^3, 2x8x8, ...: 8 pairs per wave) on a unit-stride dy, or of
+ * 25..32 pairs (4^3, 6x3x3, 2x5x5, 1x7x8, ...: 4 per wave) on a stride-2 space-to-depth dy or a unit-stride dy whose W is a
+ * multiple of 16 (pairs = ceil(kd*kh*kw / 2)); dy W a multiple of 16 (D >= 4) or of 8 (D >= 8), H >= 8; unit-stride even x
+ * as above; at most 1024 staging units per patch.  Channel counts are free (dy->C may be smaller than Npad).     */
 int crn_conv_wgrad_bf3(const crnView* x, const crnInTransform* tr, const crnView* dy,
                        float* dw, int Npad, int kd, int kh, int kw, int pd, int ph, int pw,
                        int zero_first, crnStream stream);
@@ -201,6 +211,41 @@ int crn_conv_wgrad_bf3(const crnView* x, const crnInTransform* tr, const crnView
 int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
                              int kd, int kh, int kw, int pd, int ph, int pw, int zero_first,
                              const crnTapBoxes* boxes /* may be NULL */, crnStream stream);
+
+/* Which kernel a call of the split-bf16 engine gets, as crn_conv_fwd_plan says it for the fp32 engine: the selection the
+ * launches themselves run, host arithmetic only (no GPU needed), CRN_EINVAL where the launch returns it.
+ * Forward query: exactly one of w / wslab as for crn_conv_fwd_bf3 / _slabs; fuse NULL, or the request of
+ * crn_conv_fwd_bf3_slabs_bnbwd (fuse->x NULL: of crn_conv_fwd_bf3_slabs_stats, which reads pre_relu, ws, ws_bytes only).
+ * A launch that wants to split is described as it runs when the split-K scratch can be had.                       */
+#define CRN_BF3_PLAIN 0   /* conv_bf3_kernel */
+#define CRN_BF3_HALF 1    /* conv_bf3_half_kernel: last chunk of <= 4 channels as 8 taps x 4 channels */
+#define CRN_BF3_WS 2      /* conv_bf3_ws_kernel: wave-specialised */
+typedef struct {
+  int32_t kind;                /* forward: CRN_BF3_* */
+  int32_t nsub;                /* N block = nsub x 16 columns */
+  int32_t xmode;               /* forward: staging of x, 1 unit stride, 2 stride 2 */
+  int32_t ng;                  /* forward: groups of 4 in-plane taps (4 or 7) */
+  int32_t slabs;               /* forward: weights as pre-arranged slabs */
+  int32_t td, th, tw;          /* position tile: 4 x 8 x 16 or 8 x 8 x 8 */
+  int32_t splits;              /* over channel chunks (forward) / position tiles (weight gradient) */
+  int32_t chunks;              /* what they divide */
+  int32_t per_split;           /* chunks_per_split / tiles_per_split */
+  int32_t vec_store, mode;     /* forward: float4 epilogue; 0 store, 1 accumulate, 3 partial sums to the scratch */
+  int32_t rowskip, half_last;  /* forward */
+  int32_t lead;                /* leading patch column of an odd pw */
+  int32_t n_groups, c_groups;  /* tap-box groups applied (0: given none, or ignored) */
+  int32_t nparts;              /* forward, fuse request: parts the launch would leave (0: it declines) */
+  int32_t dmode, tpw, twt;     /* weight gradient: staging of dy (1 / 2), tap pairs per wave (8 / 4), tile width (16 / 8) */
+  int32_t pipe, inherit, boxskip; /* weight gradient */
+  int32_t lds_bytes;
+} crnBf3Plan;
+int crn_conv_fwd_bf3_plan(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
+                          const float* bias, int bias_sB, const crnView* y,
+                          int kd, int kh, int kw, int pd, int ph, int pw,
+                          int accumulate, const crnTapBoxes* boxes, const crnBnBwdFuse* fuse, crnBf3Plan* out);
+int crn_conv_wgrad_bf3_plan(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                            int kd, int kh, int kw, int pd, int ph, int pw, int zero_first,
+                            const crnTapBoxes* boxes, crnBf3Plan* out);
 
 /* Encoder engine (csrc/conv_e2d.hip): the ResNet-50 encoder's stride-1 Conv2d 1x1 / 3x3 layers (resnet50.py:49-115;
  * the stride of a down-sampling block is applied by crn_stride2_gather before its first 1x1) at batch sizes where
