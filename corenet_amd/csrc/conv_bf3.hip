@@ -28,7 +28,6 @@
 #include "bf3_common.h"
 #include <algorithm>
 #include <cstring>
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -41,7 +40,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kThreads = 512, kMSUB = 4, kCK = 8;
 constexpr int kNUX = 2;          // patch units (2 positions x 8 channels) per thread
 constexpr int kTabC = 512;       // channel tables
-constexpr int kMaxTapSlots = 32; // NG * 4
 
 struct Bf3Geom {
   crnView x, y;
@@ -67,7 +65,6 @@ struct Bf3Geom {
   unsigned magic_pw2, magic_PH, magic_kw;
   const void* wslab;       // weights pre-arranged as slab images (crn_bf3_operands, slab order), or nullptr: w is staged
   int UP;                  // wave-specialised kernel: staging units per patch plane (PH * pw2)
-  unsigned magic_UP;
   int rowskip;             // 4 x 4 window planes with tap boxes: a tap group = a window row, rows outside the box are skipped
   int half_last;           // the last chunk has <= 4 real channels: 8 taps x 4 channels per MFMA (conv_bf3_kernel, plane_half)
   long long* stamps;       // tuning aid (CRN_BF3_STAMPS=1): shader-clock stamps of workgroup 0, 4 per staging step
@@ -113,6 +110,74 @@ __device__ __forceinline__ void bn_bwd_sums_store(const Bf3Geom& g, char* smem, 
   if (g.bn_dsum && blockIdx.x == 0 && blockIdx.y == 0 && tid < g.bn_ndsum) g.bn_dsum[tid] = 0.f;
 }
 
+// Output epilogue of a forward / data-gradient workgroup: acc[ms][ns] holds D row = kk*4 + r = position (kk*4 + r) of the
+// mh x mw sub-tile wave * 4 + ms, col = i16 = channel n0 + ns * 16 + i16.  Bias (first split only), then store / accumulate
+// (mode 1) / split-K partial sums (mode 3: a dense scratch tensor [split][b][n][pos]; a reduction launch adds them up), as
+// float4 or scalar stores; with a fused BatchRenorm, this lane's share of the two sums, handed to bn_bwd_sums_store -- so every
+// wave of the workgroup that is still running must call this (two barriers there).
+template <int NSUB>
+__device__ __forceinline__ void bf3_epilogue(const Bf3Geom& g, char* smem, const f32x4 (&acc)[kMSUB][NSUB], int b, int d0, int h0,
+                                             int w0, int n0, int split, int wave, int kk, int i16, int tid) {
+  float* yb = g.y.base + (int64_t)(g.mode >= 3 ? split * g.x.B + b : b) * g.y.sB;
+  float bn_s1[NSUB], bn_s2[NSUB], bn_mu[NSUB], bn_rstd[NSUB];
+#pragma unroll
+  for (int ns = 0; ns < NSUB; ++ns) {
+    bn_s1[ns] = bn_s2[ns] = 0.f;
+    const int n = n0 + ns * 16 + i16;
+    const bool on = g.bn_x && n < g.y.C;
+    bn_mu[ns] = on ? g.bn_saved[n] : 0.f; bn_rstd[ns] = on ? g.bn_saved[g.y.C + n] : 0.f;
+  }
+#pragma unroll
+  for (int ns = 0; ns < NSUB; ++ns) {
+    const int n = n0 + ns * 16 + i16;
+    if (n >= g.y.C) continue;
+    const int64_t co = view_chan(g.y, n);
+    const float bsv = (g.bias && split == 0) ? g.bias[(int64_t)b * g.bias_sB + n] : 0.f;
+#pragma unroll
+    for (int ms = 0; ms < kMSUB; ++ms) {
+      int s_ = wave * kMSUB + ms;
+      const int sw = s_ % g.nsw; s_ /= g.nsw;
+      const int sh = s_ % g.nsh, sd = s_ / g.nsh;
+      const int p0 = kk * 4;                                        // first of this lane's 4 rows
+      const int od = d0 + sd, oh = h0 + sh * g.mh + p0 / g.mw, ow = w0 + sw * g.mw + p0 % g.mw;
+      if (od >= g.y.D || oh >= g.y.H || ow >= g.y.W) continue;    // (mw >= 4: the 4 rows are 4 consecutive W positions)
+      float* dst = yb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
+      if (g.vec_store) {
+        f32x4 v = acc[ms][ns] + bsv;
+        if (g.mode == 1) v += *reinterpret_cast<const f32x4*>(dst);
+        *reinterpret_cast<f32x4*>(dst) = v;
+        if (g.bn_x) {                            // (fused only with vector stores: dense y, dense x of the same shape)
+          const f32x4 xv = *reinterpret_cast<const f32x4*>(g.bn_x + (int64_t)b * g.bn_sB + (int64_t)n * g.bn_S +
+                                                            ((int64_t)od * g.y.H + oh) * g.y.W + ow);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float xr = g.bn_pre_relu ? fmaxf(xv[r], 0.f) : xv[r];
+            bn_s1[ns] += v[r];
+            bn_s2[ns] += v[r] * ((xr - bn_mu[ns]) * bn_rstd[ns]);
+          }
+        } else if (g.bn_ws) {                    // forward statistics of the norm BEHIND this conv: sum(y), sum(y^2) (of max(y, 0))
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float yr = g.bn_pre_relu ? fmaxf(v[r], 0.f) : v[r];
+            bn_s1[ns] += yr;
+            bn_s2[ns] += yr * yr;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (ow + r < g.y.W) {
+            float* d = dst + (int64_t)r * g.y.sW;
+            const float v = acc[ms][ns][r] + bsv;
+            *d = g.mode == 1 ? *d + v : v;
+          }
+        }
+      }
+    }
+  }
+  if (g.bn_ws) bn_bwd_sums_store<NSUB>(g, smem, bn_s1, bn_s2, wave, kk, i16, n0, tid);
+}
+
 __device__ __forceinline__ void bload2(f32x2& dst, const crn_rsrc& rs, unsigned byte_off) {
   asm volatile("s_nop 4\n\tbuffer_load_dwordx2 %0, %1, %2, 0 offen" : "=v"(dst) : "v"(byte_off), "s"(rs));
 }
@@ -124,16 +189,8 @@ __device__ __forceinline__ void wait_loads2d(VT (&v)[A][B]) {
     for (int j = 0; j < B; ++j) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[i][j]));
 }
 
-template <int N, typename VT, int A, int B>
-__device__ __forceinline__ void wait_loads2d_n(VT (&v)[A][B]) {      // ... until at most N (newer) loads are outstanding
-#pragma unroll
-  for (int i = 0; i < A; ++i)
-#pragma unroll
-    for (int j = 0; j < B; ++j) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v[i][j]) : "n"(N));
-}
-
 template <int N, typename VT, int A>
-__device__ __forceinline__ void wait_loads1d_n(VT (&v)[A]) {
+__device__ __forceinline__ void wait_loads1d_n(VT (&v)[A]) {         // ... until at most N (newer) loads are outstanding
 #pragma unroll
   for (int i = 0; i < A; ++i) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v[i]) : "n"(N));
 }
@@ -152,20 +209,136 @@ template <> struct XLoad<2> {            // stride-2 (space-to-depth) view: elem
   static __device__ __forceinline__ float e1(const T& v) { return v[2]; }
 };
 
+// ---------------------------------------------- staging steps shared by the kernels ----------------------------------------------
+// A staging unit = 2 consecutive W positions x the 8 channels of a chunk.  The rule of every helper that touches loads: registers
+// with loads in flight must not meet a control-flow merge, so nothing here branches around an issue -- a unit (or a channel)
+// that is not loaded gets the out-of-range offset, which costs an instruction slot and no traffic, and reads back as 0.
+
+// The eight loads of one unit at element offset sp.  co0 / co1 = the chunk's eight entries of the channel-offset table, which the
+// caller got with two 16-byte LDS reads (one dword read per load made every load wait for its own LDS round trip: 16 of them
+// in a row per staging step).  creal = channels of the chunk that exist (C - c0; the table repeats the last one behind them).
+template <int XM>
+__device__ __forceinline__ void bf3_unit_issue(typename XLoad<XM>::T (&pv)[kCK], const crn_rsrc& xrs, const u32x4& co0, const u32x4& co1,
+                                               unsigned sp, bool ld, int creal) {
+  unsigned off[kCK];
+#pragma unroll
+  for (int cl = 0; cl < kCK; ++cl)
+    off[cl] = (ld && cl < creal) ? ((cl < 4 ? co0[cl & 3] : co1[cl & 3]) + sp) * 4u : 0x80000000u;
+#pragma unroll
+  for (int cl = 0; cl < kCK; ++cl) XLoad<XM>::load(pv[cl], xrs, off[cl]);
+}
+
+// The chunk's eight scales and shifts from the LDS tables: four 16-byte reads
+__device__ __forceinline__ void bf3_read_scale_shift(const float* tscale8, const float* tshift8, float (&sc)[kCK], float (&sh)[kCK]) {
+  const f32x4 s0 = *reinterpret_cast<const f32x4*>(tscale8), s1 = *reinterpret_cast<const f32x4*>(tscale8 + 4);
+  const f32x4 h0 = *reinterpret_cast<const f32x4*>(tshift8), h1 = *reinterpret_cast<const f32x4*>(tshift8 + 4);
+#pragma unroll
+  for (int cl = 0; cl < kCK; ++cl) { sc[cl] = cl < 4 ? s0[cl & 3] : s1[cl & 3]; sh[cl] = cl < 4 ? h0[cl & 3] : h1[cl & 3]; }
+}
+
+// One unit from registers to LDS: the BatchRenorm-apply + ReLU of the producer layer (crnInTransform: ReLU, scale + shift, ReLU)
+// on a unit that was loaded (`in`: zero padding stays zero), the split, and the four LDS writes -- position 0 at hi[0] / lo[0],
+// position 1 at hi[1] / lo[1].  sc / sh: the chunk's eight scales and shifts; channels cl >= creal = C - c0 keep the +0 they
+// were loaded as.  The producers of the wave-specialised kernel pass kCK, no guard: their tables hold scale 0 and shift 0
+// behind the last channel (bf3_fill_tables), and max(+0, 0) * 0 + 0 is the same +0.  conv_bf3_body could do the same by that
+// arithmetic, but without the guard its NSUB 1 kernels take 3-4 registers more (the 5x5 one 131: one workgroup per CU less).
+__device__ __forceinline__ void bf3_unit_commit(float (&v0)[kCK], float (&v1)[kCK], const float (&sc)[kCK], const float (&sh)[kCK],
+                                                const crnInTransform& tr, bool in, int creal, bf16x8* hi, bf16x8* lo) {
+  if (tr.scale && in) {
+#pragma unroll
+    for (int cl = 0; cl < kCK; ++cl) {
+      if (cl < creal) {
+        float a = v0[cl], c = v1[cl];
+        if (tr.pre_relu) { a = fmaxf(a, 0.f); c = fmaxf(c, 0.f); }
+        a = a * sc[cl] + sh[cl]; c = c * sc[cl] + sh[cl];
+        if (tr.post_relu) { a = fmaxf(a, 0.f); c = fmaxf(c, 0.f); }
+        v0[cl] = a; v1[cl] = c;
+      }
+    }
+  }
+  bf16x8 h0v, l0v, h1v, l1v;
+  split8(v0, h0v, l0v);
+  split8(v1, h1v, l1v);
+  hi[0] = h0v; hi[1] = h1v;
+  lo[0] = l0v; lo[1] = l1v;
+}
+
+// ---------------------------------------------- prologue of the forward kernels ----------------------------------------------
+struct Bf3Tile { int b, d0, h0, w0, n0, split, cbeg, cend; };   // sample, tile origin, first column, split and its chunks
+template <int NB>
+__device__ __forceinline__ Bf3Tile bf3_tile(const Bf3Geom& g) {
+  Bf3Tile t;
+  int tile = xcd_remap(blockIdx.x, gridDim.x);
+  const int twi = tile % g.tilesW; tile /= g.tilesW;
+  const int thi = tile % g.tilesH; tile /= g.tilesH;
+  const int tdi = tile % g.tilesD; tile /= g.tilesD;
+  t.b = tile;
+  t.d0 = tdi * g.TD; t.h0 = thi * g.TH; t.w0 = twi * g.TW;
+  t.n0 = blockIdx.y * NB;
+  t.split = blockIdx.z;
+  t.cbeg = t.split * g.chunks_per_split; t.cend = min(t.cbeg + g.chunks_per_split, g.nchunks);
+  return t;
+}
+
+// The per-channel LDS tables [ctab]: element offset of the channel, scale and shift of the in-transform (1 / 0 without one).
+// Behind the last channel: its offset again (never loaded from: bf3_unit_issue), scale 0 and shift 0 (channels past C are
+// loaded as 0 and stay 0 whether or not a commit guards them).
+__device__ __forceinline__ void bf3_fill_tables(const Bf3Geom& g, unsigned* choff, float* tscale, float* tshift, int tid, int nthreads) {
+  for (int c = tid; c < g.ctab; c += nthreads) {
+    const int cc = min(c, g.x.C - 1);
+    choff[c] = g.x.chan_off ? (unsigned)g.x.chan_off[cc] : (unsigned)cc * (unsigned)g.x.sC;
+    tscale[c] = g.tr.scale ? (c < g.x.C ? g.tr.scale[cc] : 0.f) : 1.f;
+    tshift[c] = g.tr.scale && c < g.x.C ? g.tr.shift[cc] : 0.f;
+  }
+}
+
+// LDS offset (positions) of this lane group's tap of every group of 4 in-plane taps
+template <int NG>
+__device__ __forceinline__ void bf3_tap_offsets(const Bf3Geom& g, int kk, int (&toff)[NG]) {
+#pragma unroll
+  for (int gq = 0; gq < NG; ++gq) {
+    const int t = gq * 4 + kk < g.KHW ? gq * 4 + kk : 0;   // slots past the window carry zero weights
+    const int zh = mdiv(t, g.magic_kw), zw = t - zh * g.kw;
+    toff[gq] = zh * g.PW + zw;
+  }
+}
+
+// This lane's row of the wave's four sub-tiles: pa = its position inside a patch plane, sd = the tile plane of the sub-tile
+__device__ __forceinline__ void bf3_subtile_bases(const Bf3Geom& g, int wave, int i16, int (&pa)[kMSUB], int (&sd)[kMSUB]) {
+  const int ri = i16 / g.mw, rj = i16 - ri * g.mw;
+#pragma unroll
+  for (int ms = 0; ms < kMSUB; ++ms) {
+    int s_ = wave * kMSUB + ms;
+    const int sw = s_ % g.nsw; s_ /= g.nsw;
+    const int sh = s_ % g.nsh;
+    sd[ms] = s_ / g.nsh;
+    pa[ms] = (sh * g.mh + ri) * g.PW + sw * g.mw + rj + g.lead;
+  }
+}
+
+// zd range [z0, z1) of a chunk that can hold non-zero weights for the columns of nbox (tap boxes of transposed convolutions),
+// empty when the (h, w) box is; hr: the window ROWS zh of that range that can hold non-zero weights, h0 | h1 << 8 -- for 4 x 4
+// window planes a row is one group of four taps, and a group outside the box multiplies zeros only: `plane` skips it, g.rowskip
+__device__ __forceinline__ void bf3_chunk_zrange(const Bf3Geom& g, const TapBox& nbox, int c0, int& z0, int& z1, int& hr) {
+  const TapBox tb = box_intersect(nbox, box_union(g.c_box, g.c_groups, g.x.C, c0, min(c0 + kCK, g.x.C) - 1, g.kd, g.kh, g.kw));
+  z0 = tb.d0; z1 = tb.d1;
+  if (tb.h1 <= tb.h0 || tb.w1 <= tb.w0) z1 = z0;
+  hr = tb.h0 | (tb.h1 << 8);
+}
+
 // NG = groups of 4 in-plane taps (7: 5x5 window, 4: 4x4 window): compile time, so that the group loop is
 // straight-line code (LDS reads of the next group issue under the MFMAs of the current one) and every
 // staging loop has exactly the trip count the layer needs.
-// ZS = window planes (zd) per weight slab: the slab of one chunk is staged ZS planes at a time; with ZS = the
-// whole window depth a chunk is ONE staging step (two barriers) instead of one per plane.
+// A weight slab is ONE window plane (zd) of one chunk: a staging step (two barriers) per plane.
 // WS: the weights come pre-split and pre-arranged in the order of the LDS slab ([chunk][zd][tap slot][n] entries of
 // 8 hi + 8 lo bf16, crn_bf3_operands): staging a slab is then two 16-byte loads and two LDS writes per item instead of
 // eight dword loads, eight splits and two writes (per staging step: ~930 -> ~300 cycles of load issue and ~400 -> ~150
 // of commit, CRN_BF3_STAMPS; both sit outside the MFMA phase).
-template <int NSUB, int XM, int NG, int ZS, bool WS, bool HALF>
+template <int NSUB, int XM, int NG, bool WS, bool HALF>
 __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   crn_kernarg_touch(g);
   constexpr int NB = NSUB * 16;
-  constexpr int kSlab = ZS * NG * 4 * NB;                                 // weight items (16-byte units) per slab
+  constexpr int kSlab = NG * 4 * NB;                                      // weight items (16-byte units) per slab
   constexpr int kNWI = (kSlab + kThreads - 1) / kThreads;                 // ... per thread
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // channel tables sized for this layer (ctab = channels rounded up to 16): with 28..32 channels the k5 / N 16
@@ -176,46 +349,21 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   float* tshift = reinterpret_cast<float*>(smem + 2 * g.ctab * 4);        // [ctab]
   bf16x8* Ahi = reinterpret_cast<bf16x8*>(smem + 3 * g.ctab * 4);
   bf16x8* Alo = Ahi + g.NP;
-  bf16x8* Bhi = Alo + g.NP;                                               // [ZS][NG*4][NB]
+  bf16x8* Bhi = Alo + g.NP;                                               // [NG*4][NB]
   bf16x8* Blo = Bhi + kSlab;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i16 = lane & 15, kk = lane >> 4;
   typedef typename XLoad<XM>::T XT;
 
-  int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int twi = tile % g.tilesW; tile /= g.tilesW;
-  const int thi = tile % g.tilesH; tile /= g.tilesH;
-  const int tdi = tile % g.tilesD; tile /= g.tilesD;
-  const int b = tile;
-  const int d0 = tdi * g.TD, h0 = thi * g.TH, w0 = twi * g.TW;
-  const int n0 = blockIdx.y * NB;
-  const int split = blockIdx.z;
-  const int cbeg = split * g.chunks_per_split, cend = min(cbeg + g.chunks_per_split, g.nchunks);
-
-  for (int c = tid; c < g.ctab; c += kThreads) {
-    const int cc = min(c, g.x.C - 1);
-    choff[c] = g.x.chan_off ? (unsigned)g.x.chan_off[cc] : (unsigned)cc * (unsigned)g.x.sC;
-    tscale[c] = g.tr.scale ? g.tr.scale[cc] : 1.f;
-    tshift[c] = g.tr.scale ? g.tr.shift[cc] : 0.f;
-  }
-
-  int toff[NG];
+  const Bf3Tile tl = bf3_tile<NB>(g);
+  const int b = tl.b, d0 = tl.d0, h0 = tl.h0, w0 = tl.w0, n0 = tl.n0, split = tl.split, cbeg = tl.cbeg, cend = tl.cend;
+  bf3_fill_tables(g, choff, tscale, tshift, tid, kThreads);
+  int toff[NG], pa[kMSUB], sd[kMSUB];
+  bf3_tap_offsets<NG>(g, kk, toff);
+  bf3_subtile_bases(g, wave, i16, pa, sd);
 #pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    const int t = gq * 4 + kk < g.KHW ? gq * 4 + kk : 0;   // slots past the window carry zero weights
-    const int zh = mdiv(t, g.magic_kw), zw = t - zh * g.kw;
-    toff[gq] = zh * g.PW + zw;
-  }
-  const int ri = i16 / g.mw, rj = i16 - ri * g.mw;
-  int pa[kMSUB];
-#pragma unroll
-  for (int ms = 0; ms < kMSUB; ++ms) {
-    int s_ = wave * kMSUB + ms;
-    const int sw = s_ % g.nsw; s_ /= g.nsw;
-    const int sh = s_ % g.nsh, sd = s_ / g.nsh;
-    pa[ms] = (sd * g.PH + sh * g.mh + ri) * g.PW + sw * g.mw + rj + g.lead;
-  }
-  // (HALF: the launcher guarantees 16-wide sub-tiles on a row pitch of 20 -- a wave's four sub-tiles are four consecutive rows,
+  for (int ms = 0; ms < kMSUB; ++ms) pa[ms] += sd[ms] * g.PHW;         // the whole patch is in LDS: plane sd of it
+  // (HALF: bf3_half_shape guarantees 16-wide sub-tiles on a row pitch of 20 -- a wave's four sub-tiles are four consecutive rows,
   // so three of the four base addresses are immediates of the LDS reads: the registers this instantiation has to give back)
   auto PA = [&](int ms) -> unsigned { if constexpr (HALF) return (unsigned)pa[0] + (unsigned)(ms * 20); else return (unsigned)pa[ms]; };
   f32x4 acc[kMSUB][NSUB];
@@ -246,10 +394,6 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   };
   auto patch_issue = [&](int c0) {
     inmask = 0;
-    // the chunk's eight channel offsets with two 16-byte LDS reads (one dword read per load made every load wait for
-    // its own LDS round trip: 16 of them in a row per staging step)
-    // (NSUB 1 only: in the wider variants the 16 extra live registers cross 128 and cost the second workgroup per CU --
-    // stage_5.t1 forward 200 -> 232 us)
     u32x4 co0, co1;
     if constexpr (NSUB == 1) { co0 = *reinterpret_cast<const u32x4*>(choff + c0); co1 = *reinterpret_cast<const u32x4*>(choff + c0 + 4); }
 #pragma unroll
@@ -258,13 +402,10 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
       const bool valid = unit_of(j, pos, sp, in);
       const bool ld = valid && in;
       if (ld) inmask |= 1u << j;
+      // the chunk's eight channel offsets with two 16-byte LDS reads (bf3_unit_issue): NSUB 1 only -- in the wider variants
+      // the 16 extra live registers cross 128 and cost the second workgroup per CU (stage_5.t1 forward 200 -> 232 us)
       if constexpr (NSUB == 1) {
-        unsigned off[kCK];
-#pragma unroll
-        for (int cl = 0; cl < kCK; ++cl)
-          off[cl] = (ld && c0 + cl < g.x.C) ? ((cl < 4 ? co0[cl & 3] : co1[cl & 3]) + sp) * 4u : 0x80000000u;
-#pragma unroll
-        for (int cl = 0; cl < kCK; ++cl) XLoad<XM>::load(pv[j][cl], xrs, off[cl]);
+        bf3_unit_issue<XM>(pv[j], xrs, co0, co1, sp, ld, g.x.C - c0);
       } else {
 #pragma unroll
         for (int cl = 0; cl < kCK; ++cl) {
@@ -275,11 +416,8 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
     }
   };
   auto patch_commit = [&](int c0) {
-    f32x4 s0, s1, h0, h1;
-    if (NSUB == 1 && g.tr.scale) {
-      s0 = *reinterpret_cast<const f32x4*>(tscale + c0); s1 = *reinterpret_cast<const f32x4*>(tscale + c0 + 4);
-      h0 = *reinterpret_cast<const f32x4*>(tshift + c0); h1 = *reinterpret_cast<const f32x4*>(tshift + c0 + 4);
-    }
+    float sc[kCK], sh[kCK];                              // (NSUB 1: four 16-byte reads of the tables; wider: a dword per use)
+    if (NSUB == 1 && g.tr.scale) bf3_read_scale_shift(tscale + c0, tshift + c0, sc, sh);
 #pragma unroll
     for (int j = 0; j < kNUX; ++j) {
       if (j * kThreads < g.nunits) {                     // block-uniform
@@ -289,33 +427,18 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
           float v0[kCK], v1[kCK];
 #pragma unroll
           for (int cl = 0; cl < kCK; ++cl) { v0[cl] = XLoad<XM>::e0(pv[j][cl]); v1[cl] = XLoad<XM>::e1(pv[j][cl]); }
-          if (g.tr.scale && ((inmask >> j) & 1u)) {        // zero padding stays zero
+          if constexpr (NSUB != 1) {
 #pragma unroll
-            for (int cl = 0; cl < kCK; ++cl) {
-              if (c0 + cl < g.x.C) {
-                const float sc = NSUB == 1 ? (cl < 4 ? s0[cl & 3] : s1[cl & 3]) : tscale[c0 + cl];
-                const float sh = NSUB == 1 ? (cl < 4 ? h0[cl & 3] : h1[cl & 3]) : tshift[c0 + cl];
-                float a = v0[cl], c = v1[cl];
-                if (g.tr.pre_relu) { a = fmaxf(a, 0.f); c = fmaxf(c, 0.f); }
-                a = a * sc + sh; c = c * sc + sh;
-                if (g.tr.post_relu) { a = fmaxf(a, 0.f); c = fmaxf(c, 0.f); }
-                v0[cl] = a; v1[cl] = c;
-              }
-            }
+            for (int cl = 0; cl < kCK; ++cl) { sc[cl] = tscale[c0 + cl]; sh[cl] = tshift[c0 + cl]; }
           }
-          bf16x8 h0v, l0v, h1v, l1v;
-          split8(v0, h0v, l0v);
-          split8(v1, h1v, l1v);
-          Ahi[pos] = h0v; Ahi[pos + 1] = h1v;
-          Alo[pos] = l0v; Alo[pos + 1] = l1v;
+          bf3_unit_commit(v0, v1, sc, sh, g.tr, (inmask >> j) & 1u, g.x.C - c0, Ahi + pos, Alo + pos);
         }
       }
     }
   };
-  // ---- weight staging: item = (plane zs of the slab, in-plane tap slot tp, column n), all 8 channels ----
+  // ---- weight staging: item = (in-plane tap slot tp, column n) of window plane zd0, all 8 channels ----
   auto weights_issue = [&](int c0, int zd0) {
     if constexpr (WS) {
-      static_assert(!WS || ZS == 1, "slab operands are one window plane per slab");
       const unsigned sbase = (unsigned)((c0 / kCK) * g.kd + zd0) * (unsigned)(NG * 4);
 #pragma unroll
       for (int j = 0; j < kNWI; ++j) {
@@ -333,10 +456,9 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
     for (int j = 0; j < kNWI; ++j) {
       int it = tid + j * kThreads;
       asm volatile("" : "+v"(it));
-      const int n = it & (NB - 1), zt = it / NB;              // zt = zs * NG*4 + tp
-      const int zs = ZS == 1 ? 0 : zt / (NG * 4), tp = zt - zs * (NG * 4);
-      const bool ok = it < kSlab && tp < g.KHW && zd0 + zs < g.kd && n0 + n < g.Npad;
-      const unsigned base = (unsigned)(((zd0 + zs) * g.KHW + tp) * g.Npad + n0 + n);
+      const int n = it & (NB - 1), tp = it / NB;
+      const bool ok = it < kSlab && tp < g.KHW && zd0 < g.kd && n0 + n < g.Npad;
+      const unsigned base = (unsigned)((zd0 * g.KHW + tp) * g.Npad + n0 + n);
 #pragma unroll
       for (int cl = 0; cl < kCK; ++cl) {
         const unsigned off = (ok && c0 + cl < g.x.C) ? ((unsigned)(c0 + cl) * (unsigned)(g.T * g.Npad) + base) * 4u : 0x80000000u;
@@ -354,7 +476,7 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
           bf16x8 h, l;
           if constexpr (WS) { h = __builtin_bit_cast(bf16x8, wq[j][0]); l = __builtin_bit_cast(bf16x8, wq[j][1]); }
           else split8(wv[j], h, l);
-          Bhi[it] = h;                                   // [zs][tp][n] with n = ns*16 + n16: the fragment order
+          Bhi[it] = h;                                   // [tp][n] with n = ns*16 + n16: the fragment order
           Blo[it] = l;
         }
       }
@@ -362,22 +484,12 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   };
 
   const auto nbox = box_union(g.n_box, g.n_groups, g.y.C, n0, min(n0 + NB, g.y.C) - 1, g.kd, g.kh, g.kw);
-  // zd range of a chunk that can hold non-zero weights (tap boxes of transposed convolutions)
-  // (hr: the window ROWS zh of that range that can hold non-zero weights, h0 | h1 << 8 -- for 4 x 4 window planes a row is one
-  // group of four taps, and a group outside the box multiplies zeros only: `plane` skips it, g.rowskip)
-  auto chunk_zrange = [&](int c0, int& z0, int& z1, int& hr) {
-    const TapBox tb = box_intersect(nbox, box_union(g.c_box, g.c_groups, g.x.C, c0, min(c0 + kCK, g.x.C) - 1,
-                                                    g.kd, g.kh, g.kw));
-    z0 = tb.d0; z1 = tb.d1;
-    if (tb.h1 <= tb.h0 || tb.w1 <= tb.w0) z1 = z0;
-    hr = tb.h0 | (tb.h1 << 8);
-  };
   // first (chunk, slab) step with work at or after `chunk`
   auto first_step = [&](int chunk, int& zd, int& z1, int& hr) -> int {
     for (; chunk < cend; ++chunk) {
       int z0;
-      chunk_zrange(chunk * kCK, z0, z1, hr);
-      if (z1 > z0) { zd = ZS == 1 ? z0 : 0; return chunk; }
+      bf3_chunk_zrange(g, nbox, chunk * kCK, z0, z1, hr);
+      if (z1 > z0) { zd = z0; return chunk; }
     }
     return cend;
   };
@@ -400,7 +512,7 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   while (chunk < cstop) {
     const int c0 = chunk * kCK;
     // next step
-    int nchunk = chunk, nzd = zd + ZS, nzend = zend, nhrow = hrow;
+    int nchunk = chunk, nzd = zd + 1, nzend = zend, nhrow = hrow;
     if (nzd >= zend) nchunk = first_step(chunk + 1, nzd, nzend, nhrow);
     mark(0);
     wait_loads2d(pv);
@@ -490,21 +602,8 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
         }
       }
     };
-    if constexpr (ZS == 1) {
-      if constexpr (kHalf) plane_half(zd, Bhi, Blo);
-      else plane(zd, Bhi, Blo);
-    } else {
-      int z0, z1, hr_;
-      chunk_zrange(c0, z0, z1, hr_);
-      const int zlo = max(zd, z0), zhi = min(zd + ZS, zend);
-#pragma unroll 1
-      for (int z = zlo; z < zhi; ++z) {
-        int zz = z;
-        asm volatile("" : "+v"(zz));                    // keep the planes a real loop (registers: one plane in flight)
-        plane(zz, Bhi + (zz - zd) * (NG * 4 * NB), Blo + (zz - zd) * (NG * 4 * NB));
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    if constexpr (kHalf) plane_half(zd, Bhi, Blo);
+    else plane(zd, Bhi, Blo);
     mark(6);
     ++step_no;
     fresh = nchunk != chunk;
@@ -515,82 +614,15 @@ __device__ __forceinline__ void conv_bf3_body(const Bf3Geom& g) {
   run_steps(std::false_type(), chalf);
   if constexpr (HALF) run_steps(std::true_type(), cend);
 
-  // epilogue: D row = kk*4 + r = position (kk*4 + r) of the mh x mw sub-tile, col = i16 = channel.
-  // mode 3: split-K partial sums go to a dense scratch tensor [split][b][n][pos]; a reduction launch adds them up
-  float* yb = g.y.base + (int64_t)(g.mode >= 3 ? split * g.x.B + b : b) * g.y.sB;
-  float bn_s1[NSUB], bn_s2[NSUB], bn_mu[NSUB], bn_rstd[NSUB];
-#pragma unroll
-  for (int ns = 0; ns < NSUB; ++ns) {
-    bn_s1[ns] = bn_s2[ns] = 0.f;
-    const int n = n0 + ns * 16 + i16;
-    const bool on = g.bn_x && n < g.y.C;
-    bn_mu[ns] = on ? g.bn_saved[n] : 0.f; bn_rstd[ns] = on ? g.bn_saved[g.y.C + n] : 0.f;
-  }
-#pragma unroll
-  for (int ns = 0; ns < NSUB; ++ns) {
-    const int n = n0 + ns * 16 + i16;
-    if (n >= g.y.C) continue;
-    const int64_t co = view_chan(g.y, n);
-    const float bsv = (g.bias && split == 0) ? g.bias[(int64_t)b * g.bias_sB + n] : 0.f;
-#pragma unroll
-    for (int ms = 0; ms < kMSUB; ++ms) {
-      int s_ = wave * kMSUB + ms;
-      const int sw = s_ % g.nsw; s_ /= g.nsw;
-      const int sh = s_ % g.nsh, sd = s_ / g.nsh;
-      const int p0 = kk * 4;                                        // first of this lane's 4 rows
-      const int od = d0 + sd, oh = h0 + sh * g.mh + p0 / g.mw, ow = w0 + sw * g.mw + p0 % g.mw;
-      if (od >= g.y.D || oh >= g.y.H || ow >= g.y.W) continue;    // (mw >= 4: the 4 rows are 4 consecutive W positions)
-      float* dst = yb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
-      if (g.vec_store) {
-        f32x4 v = acc[ms][ns] + bsv;
-        if (g.mode == 1) v += *reinterpret_cast<const f32x4*>(dst);
-        *reinterpret_cast<f32x4*>(dst) = v;
-        if (g.bn_x) {                            // (fused only with vector stores: dense y, dense x of the same shape)
-          const f32x4 xv = *reinterpret_cast<const f32x4*>(g.bn_x + (int64_t)b * g.bn_sB + (int64_t)n * g.bn_S +
-                                                            ((int64_t)od * g.y.H + oh) * g.y.W + ow);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float xr = g.bn_pre_relu ? fmaxf(xv[r], 0.f) : xv[r];
-            bn_s1[ns] += v[r];
-            bn_s2[ns] += v[r] * ((xr - bn_mu[ns]) * bn_rstd[ns]);
-          }
-        } else if (g.bn_ws) {                    // forward statistics of the norm BEHIND this conv: sum(y), sum(y^2) (of max(y, 0))
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float yr = g.bn_pre_relu ? fmaxf(v[r], 0.f) : v[r];
-            bn_s1[ns] += yr;
-            bn_s2[ns] += yr * yr;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (ow + r < g.y.W) {
-            float* d = dst + (int64_t)r * g.y.sW;
-            const float v = acc[ms][ns][r] + bsv;
-            *d = g.mode == 1 ? *d + v : v;
-          }
-        }
-      }
-    }
-  }
-  if (g.bn_ws) bn_bwd_sums_store<NSUB>(g, smem, bn_s1, bn_s2, wave, kk, i16, n0, tid);
+  bf3_epilogue<NSUB>(g, smem, acc, b, d0, h0, w0, n0, split, wave, kk, i16, tid);
 }
 
-template <int NSUB, int XM, int NG, int ZS, bool WS>
-__global__ __launch_bounds__(kThreads) void conv_bf3_kernel(Bf3Geom g) { conv_bf3_body<NSUB, XM, NG, ZS, WS, false>(g); }
+template <int NSUB, int XM, int NG, bool WS>
+__global__ __launch_bounds__(kThreads) void conv_bf3_kernel(Bf3Geom g) { conv_bf3_body<NSUB, XM, NG, WS, false>(g); }
 // ... with a half last chunk (plane_half): two workgroups per CU are worth more than the two registers the second copy of the
 // step loop costs: its sub-tile addresses are immediates (PA), 123 registers
-template <int NSUB, int XM, int NG, int ZS, bool WS>
-__global__ __launch_bounds__(kThreads) void conv_bf3_half_kernel(Bf3Geom g) { conv_bf3_body<NSUB, XM, NG, ZS, WS, true>(g); }
-
-template <typename G>
-__host__ __device__ __forceinline__ void bf3_chunk_zrange(const G& g, const TapBox& nbox, int c0, int& z0, int& z1) {
-  const int chi = (c0 + kCK < g.x.C ? c0 + kCK : g.x.C) - 1;
-  const TapBox tb = box_intersect(nbox, box_union(g.c_box, g.c_groups, g.x.C, c0, chi, g.kd, g.kh, g.kw));
-  z0 = tb.d0; z1 = tb.d1;
-  if (tb.h1 <= tb.h0 || tb.w1 <= tb.w0) z1 = z0;
-}
+template <int NSUB, int XM, int NG, bool WS>
+__global__ __launch_bounds__(kThreads) void conv_bf3_half_kernel(Bf3Geom g) { conv_bf3_body<NSUB, XM, NG, WS, true>(g); }
 
 // ------------------------------------ wave-specialised forward / data gradient --------------------------------
 // The kernel above spends ~55 % of a staging step outside its MFMA phase, and what it waits for is not work but the
@@ -640,8 +672,6 @@ __host__ __device__ __forceinline__ Bf3WsPlanes bf3_ws_planes_at(int T, int nch)
   return w;
 }
 
-typedef __attribute__((address_space(3))) void lds_void;
-
 template <int NSUB, int XM, int NG>
 __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
   crn_kernarg_touch(g);
@@ -664,29 +694,17 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
   const bool producer = wave >= kWsConsumers;
   typedef typename XLoad<XM>::T XT;
 
-  int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int twi = tile % g.tilesW; tile /= g.tilesW;
-  const int thi = tile % g.tilesH; tile /= g.tilesH;
-  const int tdi = tile % g.tilesD; tile /= g.tilesD;
-  const int b = tile;
-  const int d0 = tdi * g.TD, h0 = thi * g.TH, w0 = twi * g.TW;
-  const int n0 = blockIdx.y * NB;
-  const int split = blockIdx.z;
-  const int cbeg = split * g.chunks_per_split, cend = min(cbeg + g.chunks_per_split, g.nchunks);
+  const Bf3Tile tl = bf3_tile<NB>(g);
+  const int b = tl.b, d0 = tl.d0, h0 = tl.h0, w0 = tl.w0, n0 = tl.n0, split = tl.split, cbeg = tl.cbeg, cend = tl.cend;
   const int nch = cend - cbeg, nsteps = nch * KD;
   const int niter = (nsteps + 3 + 2) / 3 * 3;        // iterations (= barriers) of both roles: a multiple of three
 
-  for (int c = tid; c < g.ctab; c += kWsThreads) {
-    const int cc = min(c, g.x.C - 1);
-    choff[c] = g.x.chan_off ? (unsigned)g.x.chan_off[cc] : (unsigned)cc * (unsigned)g.x.sC;
-    tscale[c] = g.tr.scale ? (c < g.x.C ? g.tr.scale[cc] : 0.f) : 1.f;      // (channels past C are loaded as 0 and stay 0)
-    tshift[c] = g.tr.scale && c < g.x.C ? g.tr.shift[cc] : 0.f;
-  }
+  bf3_fill_tables(g, choff, tscale, tshift, tid, kWsThreads);
 
   if (tid < nch) {       // window planes of each chunk that can hold non-zero weights (tap boxes of transposed convs)
     const TapBox nbox = box_union(g.n_box, g.n_groups, g.y.C, n0, min(n0 + NB, g.y.C) - 1, g.kd, g.kh, g.kw);
-    int z0, z1;
-    bf3_chunk_zrange(g, nbox, (cbeg + tid) * kCK, z0, z1);
+    int z0, z1, hr;
+    bf3_chunk_zrange(g, nbox, (cbeg + tid) * kCK, z0, z1, hr);
     zrtab[tid] = z0 | (z1 << 8);
   }
   __syncthreads();       // the tables are in LDS (the producers read them before the first barrier of the loops)
@@ -716,14 +734,8 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
       msk = ld ? 1u : 0u;
       const int c0 = (cbeg + c) * kCK;
       const unsigned sp = (unsigned)gd * (unsigned)g.x.sD + sp_hw;
-      // the chunk's eight channel offsets: two 16-byte LDS reads (one address for the whole plane)
       const u32x4 co0 = *reinterpret_cast<const u32x4*>(choff + c0), co1 = *reinterpret_cast<const u32x4*>(choff + c0 + 4);
-      unsigned off[kCK];
-#pragma unroll
-      for (int cl = 0; cl < kCK; ++cl)
-        off[cl] = (ld && c0 + cl < g.x.C) ? ((cl < 4 ? co0[cl & 3] : co1[cl & 3]) + sp) * 4u : 0x80000000u;
-#pragma unroll
-      for (int cl = 0; cl < kCK; ++cl) XLoad<XM>::load(pvs[cl], xrs, off[cl]);
+      bf3_unit_issue<XM>(pvs, xrs, co0, co1, sp, ld, g.x.C - c0);          // (one table address for the whole plane)
     };
     auto commit = [&](int T, XT (&pvs)[kCK], unsigned msk) {
       const Bf3WsPlanes w = bf3_ws_planes_at<KD>(T, nch);
@@ -733,25 +745,10 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
         float v0[kCK], v1[kCK];
 #pragma unroll
         for (int cl = 0; cl < kCK; ++cl) { v0[cl] = XLoad<XM>::e0(pvs[cl]); v1[cl] = XLoad<XM>::e1(pvs[cl]); }
-        if (g.tr.scale && msk) {                                            // zero padding stays zero
-          const f32x4 s0 = *reinterpret_cast<const f32x4*>(tscale + c0), s1 = *reinterpret_cast<const f32x4*>(tscale + c0 + 4);
-          const f32x4 h0 = *reinterpret_cast<const f32x4*>(tshift + c0), h1 = *reinterpret_cast<const f32x4*>(tshift + c0 + 4);
-#pragma unroll
-          for (int cl = 0; cl < kCK; ++cl) {
-            const float sc = cl < 4 ? s0[cl & 3] : s1[cl & 3], sh = cl < 4 ? h0[cl & 3] : h1[cl & 3];
-            float a = v0[cl], e = v1[cl];
-            if (g.tr.pre_relu) { a = fmaxf(a, 0.f); e = fmaxf(e, 0.f); }
-            a = a * sc + sh; e = e * sc + sh;
-            if (g.tr.post_relu) { a = fmaxf(a, 0.f); e = fmaxf(e, 0.f); }
-            v0[cl] = a; v1[cl] = e;
-          }
-        }
-        bf16x8 h0v, l0v, h1v, l1v;
-        split8(v0, h0v, l0v);
-        split8(v1, h1v, l1v);
+        float sc[kCK], sh[kCK];
+        bf3_read_scale_shift(tscale + c0, tshift + c0, sc, sh);
         const int lpos = ((PD * c + p) & (kWsR - 1)) * g.PHW + lpos_hw;
-        Ahi[lpos] = h0v; Ahi[lpos + 1] = h1v;
-        Alo[lpos] = l0v; Alo[lpos + 1] = l1v;
+        bf3_unit_commit(v0, v1, sc, sh, g.tr, msk != 0, kCK, Ahi + lpos, Alo + lpos);
       }
     };
     // iteration t: issue the loads of the planes committed at t + 2 into set (t + 2) % 3, then commit the planes of
@@ -785,27 +782,11 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
   }
 
   // -------------------------------------------------- consumers --------------------------------------------------
-  int toff[NG];
-  int pa[kMSUB];
-  int sd_w = 0;
+  int toff[NG], pa[kMSUB], sd[kMSUB];
   f32x4 acc[kMSUB][NSUB];
-#pragma unroll
-  for (int gq = 0; gq < NG; ++gq) {
-    const int t = gq * 4 + kk < g.KHW ? gq * 4 + kk : 0;       // slots past the window carry zero weights
-    const int zh = mdiv(t, g.magic_kw), zw = t - zh * g.kw;
-    toff[gq] = zh * g.PW + zw;
-  }
-  {
-    const int ri = i16 / g.mw, rj = i16 - ri * g.mw;
-#pragma unroll
-    for (int ms = 0; ms < kMSUB; ++ms) {
-      int s_ = wave * kMSUB + ms;
-      const int sw = s_ % g.nsw; s_ /= g.nsw;
-      const int sh = s_ % g.nsh;
-      sd_w = s_ / g.nsh;                                       // (nsw * nsh is a multiple of kMSUB: the same for all ms)
-      pa[ms] = (sh * g.mh + ri) * g.PW + sw * g.mw + rj + g.lead;
-    }
-  }
+  bf3_tap_offsets<NG>(g, kk, toff);
+  bf3_subtile_bases(g, wave, i16, pa, sd);
+  const int sd_w = sd[kMSUB - 1];                              // (nsw * nsh is a multiple of kMSUB: the same for all ms)
 #pragma unroll
   for (int ms = 0; ms < kMSUB; ++ms)
 #pragma unroll
@@ -895,65 +876,7 @@ __global__ __launch_bounds__(kWsThreads) void conv_bf3_ws_kernel(Bf3Geom g) {
     cmark(t, 3);
   }
 
-  // epilogue: D row = kk*4 + r = position (kk*4 + r) of the mh x mw sub-tile, col = i16 = channel
-  float* yb = g.y.base + (int64_t)(g.mode >= 3 ? split * g.x.B + b : b) * g.y.sB;
-  float bn_s1[NSUB], bn_s2[NSUB], bn_mu[NSUB], bn_rstd[NSUB];
-#pragma unroll
-  for (int ns = 0; ns < NSUB; ++ns) {
-    bn_s1[ns] = bn_s2[ns] = 0.f;
-    const int n = n0 + ns * 16 + i16;
-    const bool on = g.bn_x && n < g.y.C;
-    bn_mu[ns] = on ? g.bn_saved[n] : 0.f; bn_rstd[ns] = on ? g.bn_saved[g.y.C + n] : 0.f;
-  }
-#pragma unroll
-  for (int ns = 0; ns < NSUB; ++ns) {
-    const int n = n0 + ns * 16 + i16;
-    if (n >= g.y.C) continue;
-    const int64_t co = view_chan(g.y, n);
-    const float bsv = (g.bias && split == 0) ? g.bias[(int64_t)b * g.bias_sB + n] : 0.f;
-#pragma unroll
-    for (int ms = 0; ms < kMSUB; ++ms) {
-      int s_ = wave * kMSUB + ms;
-      const int sw = s_ % g.nsw; s_ /= g.nsw;
-      const int sh = s_ % g.nsh, sd = s_ / g.nsh;
-      const int p0 = kk * 4;
-      const int od = d0 + sd, oh = h0 + sh * g.mh + p0 / g.mw, ow = w0 + sw * g.mw + p0 % g.mw;
-      if (od >= g.y.D || oh >= g.y.H || ow >= g.y.W) continue;
-      float* dst = yb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
-      if (g.vec_store) {
-        f32x4 v = acc[ms][ns] + bsv;
-        if (g.mode == 1) v += *reinterpret_cast<const f32x4*>(dst);
-        *reinterpret_cast<f32x4*>(dst) = v;
-        if (g.bn_x) {                            // (fused only with vector stores: dense y, dense x of the same shape)
-          const f32x4 xv = *reinterpret_cast<const f32x4*>(g.bn_x + (int64_t)b * g.bn_sB + (int64_t)n * g.bn_S +
-                                                            ((int64_t)od * g.y.H + oh) * g.y.W + ow);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float xr = g.bn_pre_relu ? fmaxf(xv[r], 0.f) : xv[r];
-            bn_s1[ns] += v[r];
-            bn_s2[ns] += v[r] * ((xr - bn_mu[ns]) * bn_rstd[ns]);
-          }
-        } else if (g.bn_ws) {                    // forward statistics of the norm BEHIND this conv: sum(y), sum(y^2) (of max(y, 0))
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float yr = g.bn_pre_relu ? fmaxf(v[r], 0.f) : v[r];
-            bn_s1[ns] += yr;
-            bn_s2[ns] += yr * yr;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (ow + r < g.y.W) {
-            float* d = dst + (int64_t)r * g.y.sW;
-            const float v = acc[ms][ns][r] + bsv;
-            *d = g.mode == 1 ? *d + v : v;
-          }
-        }
-      }
-    }
-  }
-  if (g.bn_ws) bn_bwd_sums_store<NSUB>(g, smem, bn_s1, bn_s2, wave, kk, i16, n0, tid);
+  bf3_epilogue<NSUB>(g, smem, acc, b, d0, h0, w0, n0, split, wave, kk, i16, tid);
 }
 
 // MEASURED AND REMOVED: a "sliding" variant of the kernel above (K = 4 (zd, zw) tap pairs x 8 channels, the zh taps
@@ -1094,9 +1017,10 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
   // of stage_6.c1 was 3.75 x the tensor -- every tile re-read its 5^3 halo -- and half of a tile's staging instructions went
   // into planes the workgroup had staged one tile earlier).  ubase / ucount: the unit range a tile stages.
   int ubase = 0;                                               // units of the planes the tile inherits (0: a full patch)
-#define ucount (g.nunits - ubase)
-  // (the 32-column instances on stride-2 dy views without the software pipeline sit at 250-252 registers: the extra state of
-  // the inherited planes would spill their staging registers -- a correctness hazard with loads in flight -- so they stage full patches)
+  auto ucount = [&]() { return g.nunits - ubase; };
+  // (the 32-column instances on stride-2 dy views without the software pipeline sat at 250-252 registers when this was decided --
+  // 196-198 in today's build --: the extra state of the inherited planes would spill their staging registers -- a correctness
+  // hazard with loads in flight -- so they stage full patches)
   constexpr bool kInherit = !(NSUB == 2 && DM == 2 && !PIPE);
   auto tile_reuses = [&](int tl) { return kInherit && g.inherit && tl > tbeg && (tl % g.tilesD) != 0; };
   auto tile_origin = [&](int tl) {
@@ -1114,6 +1038,7 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
       b = tile; d0 = tdi * TDT; h0 = thi * 8; w0 = twi * TWT;
     }
   };
+  // (the forward's unit_of with ubase and a unit-stride x; shared, it cost the forward kernels a register at the 128 line)
   auto unit_of = [&](int jx, int& pos, unsigned& sp, bool& in) -> bool {
     const int ul = tid + jx * kThreads;                         // index inside the tile's unit range
     int u = ubase + ul;
@@ -1124,7 +1049,7 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
     in = (unsigned)gd < (unsigned)g.x.D && (unsigned)gh < (unsigned)g.x.H && (unsigned)gw < (unsigned)g.x.W;
     sp = (unsigned)gd * (unsigned)g.x.sD + (unsigned)gh * (unsigned)g.x.sH + (unsigned)gw;
     pos = row * g.PW + 2 * pp;
-    return ul < ucount;
+    return ul < ucount();
   };
   // dy unit: (position pair pq of the 256 of a tile, octet o of the NB columns); thread -> (o = jd, pq = tid & 255) ...
   // 512 threads: pair = tid & 255, octet = (tid >> 8) + 2 * jd
@@ -1185,30 +1110,15 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
     }
 #pragma unroll
     for (int jx = 0; jx < kNUX; ++jx) {
-      if (jx * kThreads < ucount) {
+      if (jx * kThreads < ucount()) {
         int pos; unsigned sp; bool in;
         if (unit_of(jx, pos, sp, in)) {
           float v0[kCK], v1[kCK];
 #pragma unroll
           for (int cl = 0; cl < kCK; ++cl) { v0[cl] = pv[jx][cl][0]; v1[cl] = pv[jx][cl][1]; }
-          if (g.tr.scale && ((inmask >> jx) & 1u)) {
-#pragma unroll
-            for (int cl = 0; cl < kCK; ++cl) {
-              if (c0 + cl < g.x.C) {
-                const float sc = tsc[cl], sh = tsh[cl];
-                float a = v0[cl], c = v1[cl];
-                if (g.tr.pre_relu) { a = fmaxf(a, 0.f); c = fmaxf(c, 0.f); }
-                a = a * sc + sh; c = c * sc + sh;
-                if (g.tr.post_relu) { a = fmaxf(a, 0.f); c = fmaxf(c, 0.f); }
-                v0[cl] = a; v1[cl] = c;
-              }
-            }
-          }
-          bf16x8 h0v, l0v, h1v, l1v;
-          split8(v0, h0v, l0v);
-          split8(v1, h1v, l1v);
-          *reinterpret_cast<bf16x8*>(Xhi + (size_t)pos * 16) = h0v; *reinterpret_cast<bf16x8*>(Xhi + (size_t)pos * 16 + 16) = h1v;
-          *reinterpret_cast<bf16x8*>(Xlo + (size_t)pos * 16) = l0v; *reinterpret_cast<bf16x8*>(Xlo + (size_t)pos * 16 + 16) = l1v;
+          // (tsc / tsh repeat the last channel behind it: the guard stays, creal = C - c0)
+          bf3_unit_commit(v0, v1, tsc, tsh, g.tr, (inmask >> jx) & 1u, g.x.C - c0,
+                          reinterpret_cast<bf16x8*>(Xhi) + pos, reinterpret_cast<bf16x8*>(Xlo) + pos);
         }
       }
     }
@@ -1253,24 +1163,34 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
     stage_commit();
     __syncthreads();
     if (tl + 1 < tend) { tile_origin(tl + 1); stage_issue(); }
+    auto kbx_of = [&](int kb) {
+      return TWT == 16 ? (((kb >> 2) * g.PH + (kb & 3) * 2) * g.PW) << 4      // K block kb = (d, H row pair)
+                       : (((kb >> 1) * g.PH + (kb & 1) * 4) * g.PW) << 4;     //            = (d, H row quad)
+    };
+    auto ldB = [&](int kb, bf16x8 (&bh)[NSUB], bf16x8 (&bl)[NSUB]) {          // the dy fragments of K block kb
+      const char* yb = Yhi + ybase + kb * (32 * NB * 2);
+#pragma unroll
+      for (int ns = 0; ns < NSUB; ++ns) {
+        bh[ns] = cat(trd(yb + ns * 32), trd(yb + ns * 32 + 4 * NB * 2));
+        bl[ns] = cat(trd(yb + ylo + ns * 32), trd(yb + ylo + ns * 32 + 4 * NB * 2));
+      }
+    };
+    auto ldA = [&](int kbx, int ti, bf16x8& ah, bf16x8& al) {                 // the patch fragments of tap pair ti
+      const char* xa = Xhi + abase + toffL[ti] + kbx;
+      ah = cat(trd(xa), trd(xa + 64));
+      al = cat(trd(xa + xlo), trd(xa + xlo + 64));
+    };
     if constexpr (!PIPE) {
       // the compiler's own schedule of the reads (measured faster for the 4^3 windows, TPW 4)
       for (int kb = 0; kb < 16; ++kb) {
-        const int kbx = TWT == 16 ? (((kb >> 2) * g.PH + (kb & 3) * 2) * g.PW) << 4
-                                  : (((kb >> 1) * g.PH + (kb & 1) * 4) * g.PW) << 4;
-        const char* yb = Yhi + ybase + kb * (32 * NB * 2);
+        const int kbx = kbx_of(kb);
         bf16x8 bh[NSUB], bl[NSUB];
-#pragma unroll
-        for (int ns = 0; ns < NSUB; ++ns) {
-          bh[ns] = cat(trd(yb + ns * 32), trd(yb + ns * 32 + 4 * NB * 2));
-          bl[ns] = cat(trd(yb + ylo + ns * 32), trd(yb + ylo + ns * 32 + 4 * NB * 2));
-        }
+        ldB(kb, bh, bl);
 #pragma unroll
         for (int ti = 0; ti < TPW; ++ti) {
           if (ti >= tpwe) continue;                            // (workgroup-uniform: boxskip)
-          const char* xa = Xhi + abase + toffL[ti] + kbx;
-          const bf16x8 ah = cat(trd(xa), trd(xa + 64));
-          const bf16x8 al = cat(trd(xa + xlo), trd(xa + xlo + 64));
+          bf16x8 ah, al;
+          ldA(kbx, ti, ah, al);
 #pragma unroll
           for (int ns = 0; ns < NSUB; ++ns) {
             mfma3(acc[ti][ns], ah, al, bh[ns], bl[ns]);
@@ -1283,32 +1203,15 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
     // the last tap pair of a K block, of the next block's B fragments) are issued before the MFMAs of the current one.
     // The workgroup is alone on its CU (95 KB of LDS), two waves per SIMD: with the compiler's own schedule (read,
     // wait lgkmcnt(0), multiply) every MFMA triple paid an LDS round trip (MfmaUtil 40 %, profiles/r02_conv_mfma_pmc_bf16x3_wgrad.txt).
-    auto kbx_of = [&](int kb) {
-      return TWT == 16 ? (((kb >> 2) * g.PH + (kb & 3) * 2) * g.PW) << 4      // K block kb = (d, H row pair)
-                       : (((kb >> 1) * g.PH + (kb & 1) * 4) * g.PW) << 4;     //            = (d, H row quad)
-    };
     bf16x8 bh[2][NSUB], bl[2][NSUB], ah[2], al[2];
-    auto ldB = [&](int kb, int qb) {
-      const char* yb = Yhi + ybase + kb * (32 * NB * 2);
-#pragma unroll
-      for (int ns = 0; ns < NSUB; ++ns) {
-        bh[qb][ns] = cat(trd(yb + ns * 32), trd(yb + ns * 32 + 4 * NB * 2));
-        bl[qb][ns] = cat(trd(yb + ylo + ns * 32), trd(yb + ylo + ns * 32 + 4 * NB * 2));
-      }
-    };
-    auto ldA = [&](int kbx, int ti, int q) {
-      const char* xa = Xhi + abase + toffL[ti] + kbx;
-      ah[q] = cat(trd(xa), trd(xa + 64));
-      al[q] = cat(trd(xa + xlo), trd(xa + xlo + 64));
-    };
     auto block = [&](int kb, auto QB_) {
       constexpr int qb = decltype(QB_)::value;
       const int kbx = kbx_of(kb);
 #pragma unroll
       for (int ti = 0; ti < TPW; ++ti) {
         const int q = ti & 1;                                  // (TPW is even: every K block starts on buffer 0)
-        if (ti + 1 < TPW) ldA(kbx, ti + 1, q ^ 1);
-        else { const int kn = min(kb + 1, 15); ldB(kn, qb ^ 1); ldA(kbx_of(kn), 0, 0); }
+        if (ti + 1 < TPW) ldA(kbx, ti + 1, ah[q ^ 1], al[q ^ 1]);
+        else { const int kn = min(kb + 1, 15); ldB(kn, bh[qb ^ 1], bl[qb ^ 1]); ldA(kbx_of(kn), 0, ah[0], al[0]); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ns = 0; ns < NSUB; ++ns) {
@@ -1318,8 +1221,8 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
       }
     };
     static_assert(TPW % 2 == 0, "");
-    ldB(0, 0);
-    ldA(kbx_of(0), 0, 0);
+    ldB(0, bh[0], bl[0]);
+    ldA(kbx_of(0), 0, ah[0], al[0]);
     for (int kb = 0; kb < 16; kb += 2) {
       block(kb, std::integral_constant<int, 0>());
       block(kb + 1, std::integral_constant<int, 1>());
@@ -1343,36 +1246,55 @@ __global__ __launch_bounds__(kThreads) void conv_bf3_wgrad_kernel(Bf3WgGeom g) {
     }
 }
 
-#undef ucount
-
 // software-pipelined LDS reads: measured per variant (profiles/r03_wgrad_pipe_ab.txt)
 constexpr bool bf3_wg_pipe(int NSUB, int TPW, int TWT) { return NSUB == 1 || (TPW == 8 && TWT == 16); }
 
-template <int NSUB, int DM, int TPW, int TWT>
-int launch_bf3_wgrad(const Bf3WgGeom& g, dim3 grid, size_t lds, hipStream_t st) {
-  constexpr bool pipe = bf3_wg_pipe(NSUB, TPW, TWT);
-  auto k = conv_bf3_wgrad_kernel<NSUB, DM, TPW, TWT, pipe>;
-  return crn_launch(k, grid, dim3(kThreads), lds, st, g);
+// ------------------------------------ host: kernel tables, shared checks and patch geometry --------------------------------
+// The instantiated forward kernels: plain (NSUB, x staging, NG), each with staged weights and with slabs -- stride-2 staging
+// exists for 4x4 planes only --; the half kernels for NSUB 1 on unit-stride x (instantiated where a model layer needs it:
+// stage_6.c1, 28 channels); the wave-specialised kernel.  One table serves the selector's rejection and the launch.
+typedef void (*Bf3FwdKernel)(Bf3Geom);
+struct Bf3FwdEntry { int nsub, xmode, ng, slabs, kind; Bf3FwdKernel kernel; };
+#define CRN_BF3_ROWS(K, KIND, N, X, G) {N, X, G, 0, KIND, K<N, X, G, false>}, {N, X, G, 1, KIND, K<N, X, G, true>}
+const Bf3FwdEntry kBf3FwdKernels[] = {
+    CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 1, 1, 7), CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 2, 1, 7),
+    CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 4, 1, 7), CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 1, 1, 4),
+    CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 2, 1, 4), CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 4, 1, 4),
+    CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 1, 2, 4), CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 2, 2, 4),
+    CRN_BF3_ROWS(conv_bf3_kernel, CRN_BF3_PLAIN, 4, 2, 4),
+    CRN_BF3_ROWS(conv_bf3_half_kernel, CRN_BF3_HALF, 1, 1, 7), CRN_BF3_ROWS(conv_bf3_half_kernel, CRN_BF3_HALF, 1, 1, 4),
+    {2, 1, 7, 1, CRN_BF3_WS, conv_bf3_ws_kernel<2, 1, 7>},
+};
+#undef CRN_BF3_ROWS
+// -> nullptr: not instantiated
+Bf3FwdKernel bf3_fwd_kernel(int nsub, int xmode, int ng, int slabs, int kind) {
+  for (const Bf3FwdEntry& e : kBf3FwdKernels)
+    if (e.nsub == nsub && e.xmode == xmode && e.ng == ng && e.slabs == slabs && e.kind == kind) return e.kernel;
+  return nullptr;
+}
+
+// The instantiated weight-gradient kernels (NSUB, dy staging, tap pairs per wave, tile width).  Not among them: 8 pairs per
+// wave on a stride-2 dy, and 4 pairs per wave on a unit-stride dy with 8-wide tiles.
+typedef void (*Bf3WgKernel)(Bf3WgGeom);
+struct Bf3WgEntry { int nsub, dmode, tpw, twt; Bf3WgKernel kernel; };
+#define CRN_BF3WG_ROW(N, D, P, W) {N, D, P, W, conv_bf3_wgrad_kernel<N, D, P, W, bf3_wg_pipe(N, P, W)>}
+const Bf3WgEntry kBf3WgKernels[] = {
+    CRN_BF3WG_ROW(1, 1, 8, 16), CRN_BF3WG_ROW(2, 1, 8, 16), CRN_BF3WG_ROW(1, 2, 4, 16), CRN_BF3WG_ROW(2, 2, 4, 16),
+    CRN_BF3WG_ROW(1, 1, 4, 16), CRN_BF3WG_ROW(2, 1, 4, 16), CRN_BF3WG_ROW(1, 1, 8, 8),  CRN_BF3WG_ROW(2, 1, 8, 8),
+    CRN_BF3WG_ROW(1, 2, 4, 8),  CRN_BF3WG_ROW(2, 2, 4, 8),
+};
+#undef CRN_BF3WG_ROW
+Bf3WgKernel bf3_wg_kernel(int nsub, int dmode, int tpw, int twt) {
+  for (const Bf3WgEntry& e : kBf3WgKernels)
+    if (e.nsub == nsub && e.dmode == dmode && e.tpw == tpw && e.twt == twt) return e.kernel;
+  return nullptr;
 }
 
 unsigned magic20b(int d) { return (unsigned)(((1u << 20) + d - 1) / d); }
 
-// the geometry conv_bf3_half_kernel is written for (of the NSUB 1, unit-stride, ZS 1 kernels)
+// the geometry conv_bf3_half_kernel is written for
 bool bf3_half_shape(const Bf3Geom& g) {
   return g.half_last && g.PW == 20 && g.mw == 16 && g.mh == 1 && g.nsw == 1 && g.nsh == 8;
-}
-
-template <int NSUB, int XM, int NG, int ZS>
-int launch_bf3(const Bf3Geom& g, dim3 grid, size_t lds, hipStream_t st) {
-  auto k = g.wslab ? conv_bf3_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_kernel<NSUB, XM, NG, ZS, false>;
-  if constexpr (NSUB == 1 && XM == 1 && ZS == 1)         // (instantiated where a model layer needs it: stage_6.c1, 28 channels)
-    if (bf3_half_shape(g)) k = g.wslab ? conv_bf3_half_kernel<NSUB, XM, NG, ZS, true> : conv_bf3_half_kernel<NSUB, XM, NG, ZS, false>;
-  return crn_launch(k, grid, dim3(kThreads), lds, st, g);
-}
-
-template <int NSUB, int XM, int NG>
-int launch_bf3_ws(const Bf3Geom& g, dim3 grid, size_t lds, hipStream_t st) {
-  return crn_launch(conv_bf3_ws_kernel<NSUB, XM, NG>, grid, dim3(kWsThreads), lds, st, g);
 }
 
 // The producers' timetable, run on the host: every plane a step reads was written (by an earlier iteration) and still
@@ -1408,6 +1330,30 @@ bool bf3_ws_timetable_ok(int nch) {
 bool even_view(const crnView& v) {       // 8-byte staging of position pairs on a unit-stride view
   return v.chan_off == nullptr && v.sW == 1 && (v.W & 1) == 0 && (v.sH & 1) == 0 && (v.sD & 1) == 0 && (v.sC & 1) == 0 &&
          (v.sB & 1) == 0 && (((uintptr_t)v.base) & 7) == 0;
+}
+
+// How a view is staged (x of the forward, dy of the weight gradient).  1: unit stride, position pairs as 8-byte loads;
+// 2: stride 2 through a channel table (a space-to-depth view), elements 0 and 2 of a 12-byte load; 0: not by this engine.
+int bf3_stage_mode(const crnView& v) {
+  return even_view(v) ? 1 : ((v.sW == 2 && v.chan_off != nullptr && (v.W & 1) == 0) ? 2 : 0);
+}
+
+bool bf3_boxes_ok(const crnTapBoxes* boxes) {
+  return !boxes || (boxes->n_groups >= 0 && boxes->n_groups <= 8 && boxes->c_groups >= 0 && boxes->c_groups <= 8);
+}
+
+// The input patch of a TD x TH x TW tile under a kd x kh x kw window, for Bf3Geom and Bf3WgGeom alike: the window, the patch
+// dims, its staging units and the magic numbers of their decode.  false: more units than the threads stage (kNUX each).
+template <typename G>
+bool bf3_patch_geom(G& g, int TD, int TH, int TW, int kd, int kh, int kw, int pd, int ph, int pw) {
+  g.lead = ((pw % 2) + 2) % 2;                       // patch rows start on an even column: 8-byte loads stay aligned
+  g.kd = kd; g.kh = kh; g.kw = kw; g.pd = pd; g.ph = ph; g.pw = pw + g.lead;
+  g.T = kd * kh * kw; g.KHW = kh * kw;
+  g.PD = TD + kd - 1; g.PH = TH + kh - 1; g.PW = (g.lead + TW + kw - 1 + 1) & ~1;
+  g.PHW = g.PH * g.PW; g.NP = g.PD * g.PHW;
+  g.pw2 = g.PW / 2; g.nunits = g.PD * g.PH * g.pw2;
+  g.magic_pw2 = magic20b(g.pw2); g.magic_PH = magic20b(g.PH); g.magic_kw = magic20b(kw);
+  return g.nunits <= kNUX * kThreads;
 }
 
 constexpr size_t kLdsMax = 160 * 1024 - 512;
@@ -1471,19 +1417,14 @@ extern "C" int crn_conv_fwd_bf3_slabs_stats(const crnView* x, const crnInTransfo
 }
 
 namespace {
-// The instantiated forward kernels (NSUB, x staging, NG, ZS), each with staged weights and with slabs; NSUB 1 on unit-stride
-// x also as conv_bf3_half_kernel (launch_bf3).  Stride-2 staging exists for 4x4 planes only.
-#define CRN_BF3_CASES(X) X(1, 1, 7, 1) X(2, 1, 7, 1) X(4, 1, 7, 1) X(1, 1, 4, 1) X(2, 1, 4, 1) X(4, 1, 4, 1) \
-                         X(1, 2, 4, 1) X(2, 2, 4, 1) X(4, 2, 4, 1)
-
-// What a forward launch is: everything between the argument checks and the kernel ladder, host arithmetic on the views
+// What a forward launch is: everything between the argument checks and the kernel launch, host arithmetic on the views
 // (no HIP call), shared by conv_fwd_bf3_impl and crn_conv_fwd_bf3_plan so that there is one copy of the selection.
 // bf3_fwd_select holds every rejection; bf3_fwd_place finishes the geometry once the launch knows whether it has the
 // split-K scratch.
 struct Bf3FwdSel {
   Bf3Geom g;
   crnView yreal;
-  int xmode, NSUB, ZS, splits, kind;       // kind: CRN_BF3_PLAIN / HALF / WS
+  int xmode, NSUB, splits, kind;           // kind: CRN_BF3_PLAIN / HALF / WS
   int64_t tiles;
   size_t lds;
 };
@@ -1491,20 +1432,17 @@ struct Bf3FwdSel {
 int bf3_fwd_select(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
                    const float* bias, int bias_sB, const crnView* y, int kd, int kh, int kw, int pd, int ph, int pw,
                    const crnTapBoxes* boxes, Bf3FwdSel* s) {
-  if (boxes && (boxes->n_groups < 0 || boxes->n_groups > 8 || boxes->c_groups < 0 || boxes->c_groups > 8)) return CRN_EINVAL;
+  if (!bf3_boxes_ok(boxes)) return CRN_EINVAL;
   if (!x || !y || (!w && !wslab) || Npad <= 0 || (Npad & 15) || x->B != y->B || kd < 1 || kh < 1 || kw < 1) return CRN_EINVAL;
   if (y->C > Npad || x->C > kTabC) return CRN_EINVAL;
-  const int xmode = even_view(*x) ? 1 : ((x->sW == 2 && x->chan_off != nullptr && (x->W & 1) == 0) ? 2 : 0);
+  const int xmode = bf3_stage_mode(*x);
   if (!xmode) return CRN_EINVAL;
   Bf3Geom& g = s->g;
   g = Bf3Geom{};
   g.x = *x; g.y = *y;
   g.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
   g.w = w; g.wslab = wslab; g.bias = bias; g.Npad = Npad; g.bias_sB = bias_sB;
-  g.lead = ((pw % 2) + 2) % 2;                       // patch rows start on an even column: 8-byte loads stay aligned
-  g.kd = kd; g.kh = kh; g.kw = kw; g.pd = pd; g.ph = ph; g.pw = pw + g.lead;
-  g.T = kd * kh * kw; g.KHW = kh * kw;
-  g.NG = (g.KHW + 3) / 4;
+  g.NG = (kh * kw + 3) / 4;
   if ((g.NG != 4 && g.NG != 7) || kd > 8) return CRN_EINVAL;           // instantiated: 4x4 and 5x5 window planes
   // tile: 32 sub-tiles of 16 positions.  W >= 16: sub-tile = 16 W positions, tile 4 x 8 x 16; W == 8: sub-tile =
   // 2 x 8 (two H rows), tile 8 x 8 x 8 (a whole 8^3 sample)
@@ -1512,13 +1450,9 @@ int bf3_fwd_select(const crnView* x, const crnInTransform* tr, const float* w, c
   else if (y->W == 8 && y->H % 2 == 0 && y->H >= 8 && y->D >= 8) { g.mw = 8; g.mh = 2; g.nsw = 1; g.nsh = 4; g.TD = 8; }
   else return CRN_EINVAL;
   g.TH = g.nsh * g.mh; g.TW = g.nsw * g.mw;
-  g.PD = g.TD + kd - 1; g.PH = g.TH + kh - 1; g.PW = (g.lead + g.TW + kw - 1 + 1) & ~1;
-  g.PHW = g.PH * g.PW; g.NP = g.PD * g.PHW;
-  g.pw2 = g.PW / 2; g.nunits = g.PD * g.PH * g.pw2;
-  if (g.nunits > kNUX * kThreads) return CRN_EINVAL;
+  if (!bf3_patch_geom(g, g.TD, g.TH, g.TW, kd, kh, kw, pd, ph, pw)) return CRN_EINVAL;
   g.tilesD = crn_cdiv(y->D, g.TD); g.tilesH = crn_cdiv(y->H, g.TH); g.tilesW = crn_cdiv(y->W, g.TW);
   g.nchunks = crn_cdiv(x->C, kCK);
-  g.magic_pw2 = magic20b(g.pw2); g.magic_PH = magic20b(g.PH); g.magic_kw = magic20b(kw);
   bool have_nbox = false;
   if (boxes) {
     if (boxes->n_groups > 0 && y->C % boxes->n_groups == 0) { g.n_groups = boxes->n_groups; memcpy(g.n_box, boxes->n_box, sizeof(g.n_box)); have_nbox = true; }
@@ -1526,7 +1460,7 @@ int bf3_fwd_select(const crnView* x, const crnInTransform* tr, const float* w, c
   }
   const int64_t tiles = (int64_t)g.tilesD * g.tilesH * g.tilesW * y->B;
   g.ctab = (x->C + 15) & ~15;
-  auto lds_of = [&](int nsub, int zs) { return (size_t)(3 * g.ctab * 4) + (size_t)2 * g.NP * 16 + (size_t)2 * zs * g.NG * 4 * nsub * 16 * 16; };
+  auto lds_of = [&](int nsub) { return (size_t)(3 * g.ctab * 4) + (size_t)2 * g.NP * 16 + (size_t)2 * g.NG * 4 * nsub * 16 * 16; };
   // N block (NSUB x 16 columns per workgroup), measured per layer with the pre-arranged weight slabs (tools/bf3bench.sh
   // with NSUB = 1 / 2 / 4, profiles/r02_bf3_nsub_sweep.txt): wide blocks re-use the staged patch, narrow ones
   // keep two workgroups on a CU and (transposed convolutions) skip more structural zeros.  32 columns is within 10 %
@@ -1538,7 +1472,7 @@ int bf3_fwd_select(const crnView* x, const crnInTransform* tr, const float* w, c
   if (Npad <= 16) NSUB = 1;
   else if (Npad <= 32) NSUB = 2;
   else NSUB = ((g.mw == 16 && tiles <= 64) || (!have_nbox && x->C <= 32)) ? 4 : 2;
-  while (NSUB > 1 && lds_of(NSUB, 1) > kLdsMax) NSUB >>= 1;
+  while (NSUB > 1 && lds_of(NSUB) > kLdsMax) NSUB >>= 1;
   // Whole-window slabs (ZS = kd: one staging step per chunk instead of one per window plane) were measured
   // SLOWER than plane-by-plane slabs (s6c1 fwd 584 vs 464 us, s5t1 fwd 343 vs 270 us): the long commit phase
   // stalls all eight waves at once, while short steps let the two waves of a SIMD overlap.  ZS stays 1.
@@ -1550,23 +1484,19 @@ int bf3_fwd_select(const crnView* x, const crnInTransform* tr, const float* w, c
   // Round 3, again with the pre-arranged slabs (a commit is two LDS writes per item) on the 4^3 windows of the transposed
   // convolutions (us, ZS 1 -> 4, B = 4, alone): data gradients stage_6.t1 153 -> 147, stage_5.t1 168 -> 165, 14 classes
   // 909 -> 841; forwards 154 -> 185, 194 -> 229, 817 -> 996; inside the step ZS = 4 on the data gradients alone: 7.72 vs
-  // 7.62 ms (the 24 KiB of extra LDS meet the weight-gradient kernels of the other stream).  ZS stays 1.
-  const int ZS = 1;
-  const size_t lds = lds_of(NSUB, ZS);
+  // 7.62 ms (the 24 KiB of extra LDS meet the weight-gradient kernels of the other stream).  ZS stays 1
+  // (the kernels no longer carry the parameter: a slab is one window plane).
+  const size_t lds = lds_of(NSUB);
   if (lds > kLdsMax) return CRN_EINVAL;
   if ((int64_t)x->C * g.T * Npad >= ((int64_t)1 << 29)) return CRN_EINVAL;
-  bool instantiated = false;
-#define CRN_BF3_CASE(N, X, G, Z) instantiated = instantiated || (NSUB == N && xmode == X && g.NG == G && ZS == Z);
-  CRN_BF3_CASES(CRN_BF3_CASE)
-#undef CRN_BF3_CASE
-  if (!instantiated) return CRN_EINVAL;               // a stride-2 x under 5x5 window planes
+  if (!bf3_fwd_kernel(NSUB, xmode, g.NG, wslab ? 1 : 0, CRN_BF3_PLAIN)) return CRN_EINVAL;   // a stride-2 x under 5x5 window planes
   // split-K over the channel chunks: partial sums to the shared scratch, one reduction launch
   const int64_t blocks = tiles * crn_cdiv(Npad, NSUB * 16);
   int splits = 1;
   if (blocks < 192) splits = (int)std::min<int64_t>(std::min(g.nchunks, 16), crn_cdiv(256, blocks));
   g.chunks_per_split = crn_cdiv(g.nchunks, splits);
   splits = crn_cdiv(g.nchunks, g.chunks_per_split);
-  s->yreal = *y; s->xmode = xmode; s->NSUB = NSUB; s->ZS = ZS; s->splits = splits; s->kind = CRN_BF3_PLAIN;
+  s->yreal = *y; s->xmode = xmode; s->NSUB = NSUB; s->splits = splits; s->kind = CRN_BF3_PLAIN;
   s->tiles = tiles; s->lds = lds;
   return CRN_OK;
 }
@@ -1598,7 +1528,7 @@ void bf3_fwd_place(Bf3FwdSel* s, bool have_scratch, float* scratch, int accumula
     fuse->nparts = (int)tiles_bn;
   }
   g.rowskip = (g.kh == 4 && g.kw == 4 && (g.n_groups > 0 || g.c_groups > 0)) ? 1 : 0;
-  g.half_last = (g.x.C % kCK >= 1 && g.x.C % kCK <= 4 && s->ZS == 1) ? 1 : 0;
+  g.half_last = (g.x.C % kCK >= 1 && g.x.C % kCK <= 4) ? 1 : 0;
   // the wave-specialised kernel (conv_bf3_ws_kernel): pre-arranged slabs, 4 x 8 x 16 tiles, N blocks of 16 / 32
   // columns, cubic 5^3 / 4^3 windows
   // Where it is used is measured (tools/ws_ab.sh, profiles/r03_ws_ab.txt, B = 4): it wins where a step is long -- N blocks
@@ -1606,7 +1536,8 @@ void bf3_fwd_place(Bf3FwdSel* s, bool have_scratch, float* scratch, int accumula
   // on the 16-column blocks (stage_6.c1 forward 426 -> 486 us, stage_6.t1 160 -> 190 us): there a step is 2.7 k cycles of
   // MFMA fed by 2.2 k cycles of LDS reads (one A fragment pair per three MFMAs), and the ~0.9 k cycles of DMA issue, slab
   // wait and barrier per step cost more than two co-resident workgroups of the kernel above lose.
-  if (NSUB == 2 && g.NG == 7 && g.wslab && xmode == 1 && g.mw == 16 && g.kd == 5) {
+  const int slabs = g.wslab ? 1 : 0;
+  if (bf3_fwd_kernel(NSUB, xmode, g.NG, slabs, CRN_BF3_WS) && g.mw == 16 && g.kd == 5) {
     const int UP = g.PH * g.pw2;
     const int NB = NSUB * 16;
     const size_t lds_ws = (size_t)(3 * g.ctab * 4) + 256 + (size_t)2 * kWsR * g.PHW * 16 + (size_t)4 * g.NG * 4 * NB * 16;
@@ -1614,12 +1545,12 @@ void bf3_fwd_place(Bf3FwdSel* s, bool have_scratch, float* scratch, int accumula
     const bool ok = 2 * UP <= kWsPL && lds_ws <= kLdsMax && nch <= 64 &&
                     bf3_ws_timetable_ok<5>(nch);
     if (ok) {
-      g.UP = UP; g.magic_UP = magic20b(UP);
+      g.UP = UP;
       s->kind = CRN_BF3_WS; s->lds = lds_ws;
       return;
     }
   }
-  if (NSUB == 1 && xmode == 1 && s->ZS == 1 && bf3_half_shape(g)) s->kind = CRN_BF3_HALF;
+  if (bf3_half_shape(g) && bf3_fwd_kernel(NSUB, xmode, g.NG, slabs, CRN_BF3_HALF)) s->kind = CRN_BF3_HALF;
 }
 
 int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w, const void* wslab, int Npad,
@@ -1637,8 +1568,7 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
   if (s.splits > 1) scratch = crn_splitk_scratch((size_t)s.splits * y->B * y->C * y->D * y->H * y->W, st);
   bf3_fwd_place(&s, scratch != nullptr, scratch, accumulate, fuse);
   Bf3Geom& g = s.g;
-  const int NSUB = s.NSUB, xmode = s.xmode, ZS = s.ZS, splits = s.splits;
-  const size_t lds = s.lds;
+  const int splits = s.splits;
 #ifdef CRN_TOOLS
   static const bool want_stamps = getenv("CRN_BF3_STAMPS") != nullptr;
 #else
@@ -1649,15 +1579,9 @@ int conv_fwd_bf3_impl(const crnView* x, const crnInTransform* tr, const float* w
     CRN_HIP(hipMemsetAsync(g_bf3_stamps, 0, 24 * 8 * sizeof(long long), st));
     g.stamps = g_bf3_stamps;
   }
-  dim3 grid((unsigned)s.tiles, (unsigned)crn_cdiv(Npad, NSUB * 16), (unsigned)splits);
-  int rc = CRN_EINVAL;
-  if (s.kind == CRN_BF3_WS) {
-    rc = launch_bf3_ws<2, 1, 7>(g, grid, lds, st);
-  } else {
-#define CRN_BF3_CASE(N, X, G, Z) if (NSUB == N && xmode == X && g.NG == G && ZS == Z) rc = launch_bf3<N, X, G, Z>(g, grid, lds, st);
-    CRN_BF3_CASES(CRN_BF3_CASE)
-#undef CRN_BF3_CASE
-  }
+  dim3 grid((unsigned)s.tiles, (unsigned)crn_cdiv(Npad, s.NSUB * 16), (unsigned)splits);
+  int rc = crn_launch(bf3_fwd_kernel(s.NSUB, s.xmode, g.NG, g.wslab ? 1 : 0, s.kind), grid,
+                      dim3(s.kind == CRN_BF3_WS ? kWsThreads : kThreads), s.lds, st, g);
   // the partial sums: added up by a reduction launch -- or, after crn_splitk_defer, by the BatchRenorm launch that reads
   // this (dense) output next (decoder stages 2-4: statistics after c1, the norms' backward after both data gradients)
   if (rc == CRN_OK && g.mode == 3) rc = crn_splitk_finish(s.yreal, scratch, splits, accumulate, armed, st);
@@ -1700,11 +1624,6 @@ extern "C" int crn_conv_wgrad_bf3(const crnView* x, const crnInTransform* tr, co
 // ... with the tap boxes of the output columns (transposed convolutions, conv_geometry.convt_fwd): window rows that hold only
 // structural zeros for a workgroup's columns are not multiplied (their dw entries stay what they were: zero)
 namespace {
-// The instantiated weight-gradient kernels (NSUB, dy staging, tap pairs per wave, tile width).  Not among them: 8 pairs per
-// wave on a stride-2 dy, and 4 pairs per wave on a unit-stride dy with 8-wide tiles.
-#define CRN_BF3WG_CASES(X) X(1, 1, 8, 16) X(2, 1, 8, 16) X(1, 2, 4, 16) X(2, 2, 4, 16) X(1, 1, 4, 16) X(2, 1, 4, 16) \
-                           X(1, 1, 8, 8) X(2, 1, 8, 8) X(1, 2, 4, 8) X(2, 2, 4, 8)
-
 // As bf3_fwd_select: every rejection and every choice of the weight-gradient launch, host arithmetic only, shared with
 // crn_conv_wgrad_bf3_plan.
 struct Bf3WgSel {
@@ -1715,10 +1634,10 @@ struct Bf3WgSel {
 
 int bf3_wg_select(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
                   int kd, int kh, int kw, int pd, int ph, int pw, const crnTapBoxes* boxes, Bf3WgSel* s) {
-  if (boxes && (boxes->n_groups < 0 || boxes->n_groups > 8 || boxes->c_groups < 0 || boxes->c_groups > 8)) return CRN_EINVAL;
+  if (!bf3_boxes_ok(boxes)) return CRN_EINVAL;
   if (!x || !dy || !dw || Npad <= 0 || (Npad & 15) || x->B != dy->B || kd < 1 || kh < 1 || kw < 1) return CRN_EINVAL;
   if (!even_view(*x)) return CRN_EINVAL;
-  const int dmode = even_view(*dy) ? 1 : ((dy->sW == 2 && dy->chan_off != nullptr && (dy->W & 1) == 0) ? 2 : 0);
+  const int dmode = bf3_stage_mode(*dy);
   if (!dmode) return CRN_EINVAL;
   const int TWT = (dy->W % 16 == 0) ? 16 : 8, TDT = TWT == 16 ? 4 : 8;
   if (dy->W % TWT || dy->H < 8 || dy->D < TDT) return CRN_EINVAL;
@@ -1727,27 +1646,17 @@ int bf3_wg_select(const crnView* x, const crnInTransform* tr, const crnView* dy,
   g.x = *x; g.dy = *dy;
   g.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
   g.dw = dw; g.Npad = Npad; g.ncols = std::min(Npad, dy->C);
-  g.lead = ((pw % 2) + 2) % 2;
-  g.kd = kd; g.kh = kh; g.kw = kw; g.pd = pd; g.ph = ph; g.pw = pw + g.lead;
-  g.T = kd * kh * kw; g.KHW = kh * kw;
-  g.PD = TDT + kd - 1; g.PH = 8 + kh - 1; g.PW = (g.lead + TWT + kw - 1 + 1) & ~1;
-  g.PHW = g.PH * g.PW; g.NP = g.PD * g.PHW;
-  g.pw2 = g.PW / 2; g.nunits = g.PD * g.PH * g.pw2;
-  if (g.nunits > kNUX * kThreads) return CRN_EINVAL;
+  if (!bf3_patch_geom(g, TDT, 8, TWT, kd, kh, kw, pd, ph, pw)) return CRN_EINVAL;
   const int TPW = (((g.T + 1) / 2) + 7) / 8;                  // tap pairs per wave
   if (TPW != 8 && TPW != 4) return CRN_EINVAL;                // instantiated: 5^3 (63 pairs) and 4^3 (32 pairs) windows
   g.tilesD = crn_cdiv(dy->D, TDT); g.tilesH = crn_cdiv(dy->H, 8); g.tilesW = dy->W / TWT;
   g.ntiles = g.tilesD * g.tilesH * g.tilesW * dy->B;
-  g.magic_pw2 = magic20b(g.pw2); g.magic_PH = magic20b(g.PH); g.magic_kw = magic20b(kw); g.magic_KHW = magic20b(g.KHW);
+  g.magic_KHW = magic20b(g.KHW);
   const int NSUB = (Npad % 32 == 0) ? 2 : 1;
   const int NB = NSUB * 16;
   const size_t lds = 1024 + (size_t)2 * g.NP * 16 + (size_t)2 * kWgTile * NB * 2;
-  if (lds > 160 * 1024 - 512) return CRN_EINVAL;
-  bool instantiated = false;
-#define CRN_BF3WG_CASE(N, D, P, W) instantiated = instantiated || (NSUB == N && dmode == D && TPW == P && TWT == W);
-  CRN_BF3WG_CASES(CRN_BF3WG_CASE)
-#undef CRN_BF3WG_CASE
-  if (!instantiated) return CRN_EINVAL;
+  if (lds > kLdsMax) return CRN_EINVAL;
+  if (!bf3_wg_kernel(NSUB, dmode, TPW, TWT)) return CRN_EINVAL;
   const int cblocks = crn_cdiv(x->C, kCK), nblocks = crn_cdiv(Npad, NB);
   constexpr int kBlocks = 256;
   int splits = std::max(1, std::min(g.ntiles, kBlocks / std::max(1, cblocks * nblocks)));
@@ -1775,14 +1684,10 @@ extern "C" int crn_conv_wgrad_bf3_boxes(const crnView* x, const crnInTransform* 
   if (rcs != CRN_OK) return rcs;
   hipStream_t st = (hipStream_t)stream;
   const Bf3WgGeom& g = s.g;
-  const int NSUB = s.NSUB, dmode = s.dmode, TPW = s.TPW, TWT = s.TWT;
   // behind the last rejection: a rejected call writes nothing
   if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * g.T * Npad * 4, st));
   dim3 grid((unsigned)s.cblocks, (unsigned)s.nblocks, (unsigned)s.splits);
-#define CRN_BF3WG_CASE(N, D, P, W) if (NSUB == N && dmode == D && TPW == P && TWT == W) return launch_bf3_wgrad<N, D, P, W>(g, grid, s.lds, st);
-  CRN_BF3WG_CASES(CRN_BF3WG_CASE)
-#undef CRN_BF3WG_CASE
-  return CRN_EINVAL;
+  return crn_launch(bf3_wg_kernel(s.NSUB, s.dmode, s.TPW, s.TWT), grid, dim3(kThreads), s.lds, st, g);
 }
 
 extern "C" int crn_conv_wgrad_bf3_plan(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,

@@ -207,6 +207,10 @@ CASES = [
        odims=(6, 10, 32), bias=False, slabs=True, fuse='bnbwd'),
     _c('s_bnbwd_ws', dict(kind='ws', nsub=2, splits=1, vec_store=1, nparts=8), B=2, cin=8, cout=24, k=(5, 5, 5), pad=P5,
        odims=(5, 9, 16), bias=False, slabs=True, fuse='bnbwd'),
+    _c('s_stats_half', dict(kind='half', nsub=1, half_last=1, splits=1, vec_store=1, nparts=8), B=2, cin=3, cout=10, k=(5, 5, 5), pad=P5,
+       odims=(5, 9, 16), tr='pre', slabs=True, fuse='stats'),                                       # (the epilogue is shared: the half kernel too)
+    _c('s_bnbwd_half', dict(kind='half', nsub=1, half_last=1, splits=1, vec_store=1, nparts=8), B=2, cin=3, cout=10, k=(5, 5, 5), pad=P5,
+       odims=(5, 9, 16), bias=False, slabs=True, fuse='bnbwd'),
     _c('s_decl_splits', dict(splits=2, nparts=0), B=2, cin=13, cout=80, k=(5, 5, 5), pad=P5, odims=(5, 9, 16), slabs=True, fuse='stats'),
     _c('s_decl_scalar_store', dict(splits=1, vec_store=0, nparts=0), B=2, cin=6, cout=80, k=(5, 5, 5), pad=P5, odims=(5, 9, 16),
        yview='off1', slabs=True, fuse='stats'),
