@@ -160,6 +160,8 @@ _SIGS = {
     "crn_loss_fwd_bwd": [i32, vp, vp, vp, i32, i32, i64, vp, vp, f32, vp, sz, vp],
     "crn_argmax_confusion": [vp, vp, i32, i32, i64, vp, vp, vp],
     "crn_softmax_superres": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
+    "crn_eval_labels": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "crn_eval_labels_cpu": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32],
     "crn_adam_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp],
     "crn_adam_set_hyper": [vp, f32, f32, f32, f32, f32, i32, vp],
     "crn_adam_step_hyper": [vp, vp, vp, vp, i64, vp, vp],

@@ -492,6 +492,12 @@ class HipBackend:
   def argmax_confusion(self, logits, gt_i32, B, Cn, S, labels, cm):
     self.lib.crn_argmax_confusion(ptr(logits), ptr(gt_i32), B, Cn, S, ptr(labels), ptr(cm), _lib.stream())
 
+  def eval_labels(self, scores, gt_i32, scene_class, B, Cn, K, D, H, W, m, n, labels, cm, bad):
+    """One native pass of an x m evaluation: argmax of scores [B, Cn, D, H, W] -> sub-lattice n of labels [B, mD, mH, mW],
+    counted against gt_i32 into cm int64 [K, K] / bad int32 [1] (crn_eval_labels; gt_i32, scene_class, labels may be None)."""
+    self.lib.crn_eval_labels(ptr(scores), ptr(gt_i32), ptr(scene_class), B, Cn, K, D, H, W, m, n, ptr(labels), ptr(cm), ptr(bad),
+                             _lib.stream())
+
   def adam_step(self, p, g, m, v, n, lr, b1, b2, eps, grad_scale, step):
     self.lib.crn_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), n, lr, b1, b2, eps, grad_scale, step,
                            _lib.stream())

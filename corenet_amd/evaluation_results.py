@@ -10,16 +10,24 @@ both give identical images.  TensorBoard output is out of scope (DESIGN section 
 
 Quantitative surface results (no counterpart in the reference, which reports voxel IoU only): surface_metrics_for_batch
 measures the same marching-cubes surfaces against the ground truth with Chamfer distance and F-score
-(corenet_amd.mesh_metrics) and SurfaceResults accumulates them over an evaluation run."""
+(corenet_amd.mesh_metrics) and SurfaceResults accumulates them over an evaluation run.
+
+Quantitative voxel results (evaluation_results.py:185-279): QuantitativeResults accumulates the confusion matrix over the
+dataset's classes on the device (`crn_eval_labels`: from a pmf, or streamed pass by pass at the resolution of the ground
+truth), compute_voxel_metrics turns it into the reference's table (iou / precision / recall per class
+plus the class-agnostic `__global__` column) and MetricsTable.to_csv writes what pandas writes for it, without pandas."""
 from __future__ import annotations
 
+import csv
+import io
 import os
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import PIL.Image
 import torch as t
 
-from corenet_amd import mesh_metrics
+from corenet_amd import distributed as dist_util
+from corenet_amd import mesh_metrics, voxel_metrics
 from corenet_amd.geometry import transformations
 from corenet_amd.visualization import artifacts as vis
 from corenet_amd.visualization import colors, render
@@ -167,6 +175,10 @@ class QualitativeResults:
     fn = os.path.join(self.image_output_dir, "img_%s.png" % scene_id.replace("/", "_"))
     os.makedirs(os.path.dirname(fn) or ".", exist_ok=True)
     PIL.Image.fromarray(image.cpu().numpy()).save(fn, format="png")
+
+  def wants(self, ex) -> bool:
+    """Whether add_batch would draw anything of this batch (callers that can score without a pmf compute one only then)."""
+    return any(v in self.disk_result_ids for v in ex.scene_id)
 
   def add_batch(self, pmf: t.Tensor, ex):
     """Renders and writes the batch elements whose scene is of interest."""
@@ -321,3 +333,116 @@ class SurfaceResults:
               "num_rows": int((~t.isnan(cd[sel])).sum())}
     return {"thresholds": list(self.thresholds), "overall": entry(t.ones_like(cls, dtype=t.bool)),
             "per_class": {int(c): entry(cls == c) for c in sorted(set(cls.tolist()))}}
+
+
+GLOBAL_CLASS_NAME = "__global__"
+METRIC_NAMES = ("iou", "precision", "recall")
+
+
+class MetricsTable(NamedTuple):
+  """The reference's metrics data frame (evaluation_results.py:188-210): one row per metric, one column per class and a
+  last column `__global__` with the class-agnostic foreground / background result."""
+  rows: Tuple[str, ...]        # ("iou", "precision", "recall")
+  columns: Tuple[str, ...]     # class names + ("__global__",)
+  values: t.Tensor             # f64 [3, K + 1] on the host; NaN: no true positive
+
+  def row(self, name: str) -> t.Tensor:
+    return self.values[self.rows.index(name)]
+
+  def to_csv(self) -> str:
+    """Byte for byte what pandas' DataFrame.to_csv gives for the reference's frame: an empty first header cell, floats in
+    their shortest round-trip form (repr), NaN as an empty field, minimal quoting, "\n" line ends."""
+    out = io.StringIO()
+    w = csv.writer(out, lineterminator="\n", quoting=csv.QUOTE_MINIMAL)
+    w.writerow(("",) + tuple(self.columns))
+    for name, vals in zip(self.rows, self.values.tolist()):
+      w.writerow([name] + ["" if v != v else repr(float(v)) for v in vals])
+    return out.getvalue()
+
+
+def compute_voxel_metrics(cm: t.Tensor, classes: Sequence[str]) -> MetricsTable:
+  """The metrics table of a confusion matrix [K, K] (ground truth, predicted) over `classes` (K names)
+  (evaluation_results.py:188-210)."""
+  classes = [str(c) for c in classes]
+  cm = t.as_tensor(cm).detach().cpu()
+  if cm.dim() != 2 or cm.shape[0] != cm.shape[1] or cm.shape[0] != len(classes):
+    raise ValueError(f"compute_voxel_metrics: matrix {tuple(cm.shape)} for {len(classes)} classes")
+  per_class = voxel_metrics.compute_voxel_metrics(voxel_metrics.compute_tfpn(cm))
+  fg = voxel_metrics.compute_voxel_metrics(voxel_metrics.compute_tfpn_fg(cm))
+  values = t.stack([t.cat([getattr(per_class, k), getattr(fg, k).reshape(1)]) for k in METRIC_NAMES])
+  return MetricsTable(METRIC_NAMES, tuple(classes) + (GLOBAL_CLASS_NAME,), values)
+
+
+def scene_classes_of(ex) -> t.Tensor:
+  """int32 [B] on the host: the single mesh label of every scene of a batch, the factor fg_bg evaluation scales
+  prediction and ground truth with (evaluation_results.py:42-54).  A scene with another number of meshes has no such
+  label: ValueError."""
+  out = []
+  for scene_id, v in zip(ex.scene_id, ex.mesh_labels):
+    v = t.as_tensor(v).reshape(-1)
+    if v.numel() != 1:
+      raise ValueError(f"fg_bg evaluation needs exactly one mesh per scene; scene {scene_id!r} has {v.numel()}")
+    out.append(int(v[0]))
+  return t.tensor(out, dtype=t.int32)
+
+
+class QuantitativeResults:
+  """Accumulates the confusion matrix of an evaluation run over the dataset's classes and reduces it to the reference's
+  table (evaluation_results.py:241-271, without TensorBoard).  The matrix (int64 [K, K]) and the count of voxels whose
+  label or prediction fell outside [0, K) live on the device of the first batch; nothing is read back before
+  compute_metrics."""
+
+  def __init__(self, classes: Sequence[str], task_type="fg_bg"):
+    self.classes = [str(c) for c in classes]
+    self.task = _task(task_type)
+    self.confusion_matrix: Optional[t.Tensor] = None
+    self.bad: Optional[t.Tensor] = None
+    self.metrics: Optional[MetricsTable] = None
+
+  def _batch_args(self, ex, dev):
+    K = len(self.classes)
+    if self.confusion_matrix is None:
+      self.confusion_matrix = t.zeros((K, K), dtype=t.int64, device=dev)
+      self.bad = t.zeros((1,), dtype=t.int32, device=dev)
+    scene = scene_classes_of(ex).to(dev) if self.task == "fg_bg" else None
+    return ex.grid.to(dev, t.int32).contiguous(), K, scene
+
+  def add_batch(self, pmf: t.Tensor, ex) -> t.Tensor:
+    """Counts a batch from its pmf f32 [B, C, D, H, W] (the reference's contract); returns the predicted labels."""
+    gt, K, scene = self._batch_args(ex, pmf.device)
+    return voxel_metrics.label_confusion(pmf, gt, K, scene, cm=self.confusion_matrix, bad=self.bad)[0]
+
+  def add_batch_streaming(self, inference, ex) -> t.Tensor:
+    """Counts a batch without a pmf: `inference.predict_labels` (SuperResolutionInference) at the resolution of ex.grid,
+    the matrix accumulated pass by pass; returns the predicted labels int32 [B, mD, mH, mW]."""
+    gt, K, scene = self._batch_args(ex, ex.grid.device)
+    with t.no_grad():
+      return inference.predict_labels(ex.input_image, ex.camera_transform, ex.v2x_transform, ex.grid_sampling_offset,
+                                      tuple(gt.shape[1:]), gt=gt, num_classes=K, scene_classes=scene,
+                                      cm=self.confusion_matrix, bad=self.bad)
+
+  def compute_metrics(self, dst: int = 0, group=None) -> Optional[MetricsTable]:
+    """Sums the matrix over the ranks onto rank dst (evaluation_results.py:255-260), then reads this rank's out-of-range
+    count -- the run's first device -> host synchronisation -- and raises ValueError when it is not 0.  Returns the table
+    on rank dst (None elsewhere)."""
+    if self.confusion_matrix is None:
+      raise ValueError("QuantitativeResults.compute_metrics: no batch was added")
+    dist_util.reduce_confusion_matrix(self.confusion_matrix, dst, group)
+    bad = int(self.bad.item())
+    if bad:
+      raise ValueError(f"{bad} voxels had a label or a prediction outside the {len(self.classes)} classes of the dataset")
+    if dist_util.dist.is_initialized() and dist_util.dist.get_rank(group) != dst:
+      return None                                   # the sum lives on rank dst alone
+    self.metrics = compute_voxel_metrics(self.confusion_matrix, self.classes)
+    return self.metrics
+
+  def get_mean_iou(self) -> float:
+    """Mean IoU over the non-void classes, NaNs skipped, NaN when every class is NaN (evaluation_results.py:262-266)."""
+    iou = self.metrics.row("iou")[1:-1]
+    keep = ~t.isnan(iou)
+    return float(iou[keep].mean()) if bool(keep.any()) else float("nan")
+
+  def write_csv(self, path: str):
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+      f.write(self.metrics.to_csv())

@@ -337,14 +337,10 @@ class CoreNet(nn.Module):
     return plan.logits.clone()
 
   # multi-offset inference (super_resolution.py:114-129) ------------------------------------
-  def multi_offset_pmf(self, image: t.Tensor, voxel_projection_matrix: t.Tensor, grid_offsets: t.Tensor,
-                       resolution_multiplier: int = 0) -> t.Tensor:
-    """softmax(model(image, v2s, offset)) for every offset in grid_offsets [n, B, 3].
-    The reference re-runs the whole network per offset (super_resolution.py:123-125); in eval mode the
-    encoder does not depend on the offset, so it runs ONCE here and only the skip compression, the
-    ray sampling and the 3D decoder run per offset -- identical results, n-1 encoder passes saved.
-    resolution_multiplier m > 0 (with n == m^3 in the reference's offset order): returns the interleaved
-    [B, C, m*D, m*H, m*W] grid directly; 0: returns [n, B, C, D, H, W] like MultiOffsetInferenceFn."""
+  def _multi_offset_encoder(self, image: t.Tensor, voxel_projection_matrix: t.Tensor, grid_offsets: t.Tensor,
+                            resolution_multiplier: int):
+    """The checks and the offset-independent part of multi-offset inference: runs the encoder once (packing the weights
+    when they changed) and returns (plan, v2s, offsets [n, B, 3], n, m); the caller runs plan.forward_decoder per offset."""
     assert not self.training, "multi-offset inference is an eval-mode path (running BatchRenorm statistics)"
     self._check_image(image)
     B = image.shape[0]
@@ -362,12 +358,25 @@ class CoreNet(nn.Module):
     plan = self.engine.plan(B, image.shape[2:])
     v2s = voxel_projection_matrix.to(t.float32).contiguous()
     offs = grid_offsets.to(t.float32).contiguous()
-    C = self.engine.num_classes
-    D, H, W = plan.logits.shape[2:]
     with t.no_grad():
       plan.forward_encoder(image.contiguous(), training=False)      # packs encoder AND decoder weights when they are dirty
       if not self.engine.weights_dirty:
         self._packed_version = ver
+    return plan, v2s, offs, n, m
+
+  def multi_offset_pmf(self, image: t.Tensor, voxel_projection_matrix: t.Tensor, grid_offsets: t.Tensor,
+                       resolution_multiplier: int = 0) -> t.Tensor:
+    """softmax(model(image, v2s, offset)) for every offset in grid_offsets [n, B, 3].
+    The reference re-runs the whole network per offset (super_resolution.py:123-125); in eval mode the
+    encoder does not depend on the offset, so it runs ONCE here and only the skip compression, the
+    ray sampling and the 3D decoder run per offset -- identical results, n-1 encoder passes saved.
+    resolution_multiplier m > 0 (with n == m^3 in the reference's offset order): returns the interleaved
+    [B, C, m*D, m*H, m*W] grid directly; 0: returns [n, B, C, D, H, W] like MultiOffsetInferenceFn."""
+    plan, v2s, offs, n, m = self._multi_offset_encoder(image, voxel_projection_matrix, grid_offsets, resolution_multiplier)
+    B = image.shape[0]
+    C = self.engine.num_classes
+    D, H, W = plan.logits.shape[2:]
+    with t.no_grad():
       stash = t.empty((n, B, C, D, H, W), dtype=plan.logits.dtype, device=plan.logits.device)
       for i in range(n):
         stash[i].copy_(plan.forward_decoder(v2s, offs[i], training=False))
@@ -379,6 +388,38 @@ class CoreNet(nn.Module):
       out = t.empty_like(stash)
       be.softmax_superres(stash, 1, n * B, C, D, H, W, out)      # plain channel softmax
       return out
+
+  def multi_offset_labels(self, image: t.Tensor, voxel_projection_matrix: t.Tensor, grid_offsets: t.Tensor,
+                          resolution_multiplier: int, gt: Optional[t.Tensor] = None, num_classes: Optional[int] = None,
+                          scene_classes: Optional[t.Tensor] = None, cm: Optional[t.Tensor] = None,
+                          bad: Optional[t.Tensor] = None) -> t.Tensor:
+    """The label grid int32 [B, m*D, m*H, m*W] of an x m inference (m = resolution_multiplier >= 1, m^3 offsets in the
+    reference's order), without the pmf: the encoder runs once, and after every decoder pass `crn_eval_labels` takes the
+    argmax of that pass's logits (softmax does not move it) straight to the pass's sub-lattice of the label grid.  No
+    stash of the m^3 passes and no pmf is allocated: the label grid is the only tensor of the output's size.
+    With gt int32 [B, m*D, m*H, m*W] the confusion matrix cm int64 [K, K] (gt, predicted; K = num_classes, default the
+    number of logits) and the count bad int32 [1] of voxels whose label or prediction falls outside [0, K) are accumulated
+    in the same pass (both required with gt); scene_classes int32 [B] multiplies prediction and label (fg_bg: the scene's
+    mesh label, evaluation_results.py:42-54).  Same checks, eval-mode and weight handling as multi_offset_pmf."""
+    m = int(resolution_multiplier)
+    if m < 1:
+      raise ValueError("resolution_multiplier >= 1 expected")
+    if gt is not None and (cm is None or bad is None):
+      raise ValueError("multi_offset_labels: cm and bad are required with gt")
+    from corenet_amd import voxel_metrics
+    # the tensors are checked once, before anything runs; the passes then go to the kernel directly
+    B, C = image.shape[0], self.engine.num_classes
+    D, H, W = self.engine.resolution
+    K = voxel_metrics.check_eval_labels_args((B, C, D, H, W), image.device, gt, num_classes, scene_classes, m, None, cm, bad)
+    plan, v2s, offs, n, m = self._multi_offset_encoder(image, voxel_projection_matrix, grid_offsets, m)
+    assert plan.logits.shape == (B, C, D, H, W) and plan.logits.is_contiguous()
+    labels = t.empty((B, m * D, m * H, m * W), dtype=t.int32, device=plan.logits.device)
+    be = self.engine.be
+    with t.no_grad():
+      for i in range(n):
+        logits = plan.forward_decoder(v2s, offs[i], training=False)
+        be.eval_labels(logits, gt, scene_classes, B, C, K, D, H, W, m, i, labels, cm, bad)
+    return labels
 
   # fused training step (bench.py / the train hot loop pipeline.py:215-240) ------
   def train_step(self, image: t.Tensor, voxel_projection_matrix: t.Tensor,

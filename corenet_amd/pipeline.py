@@ -1,9 +1,11 @@
 """The training / evaluation hot loop around the model (`corenet.pipeline`, pipeline.py:100-242,311-325):
-data loader, ground-truth voxelization settings, and one training step from a list of dataset elements.
-Configuration objects, TensorBoard, checkpoint management and the progress UI of the reference pipeline
+data loader, ground-truth voxelization settings, one training step from a list of dataset elements, and the evaluation
+run over a dataset (`EvalPipeline.run_eval`, pipeline.py:292-343).
+Configuration objects, TensorBoard, checkpoint management, `DatasetManager` and the progress UI of the reference pipeline
 are out of scope; their values arrive here as plain arguments."""
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Tuple
 
 import torch as t
@@ -79,3 +81,49 @@ def evaluate_batch(inference_fn, batch: List[dataset_lib.DatasetElement], task_t
   with t.no_grad():
     pmf = inference_fn(ex.input_image, ex.camera_transform, ex.v2x_transform, ex.grid_sampling_offset, resolution)
   return pmf, ex
+
+
+def run_eval(inference, dataset, output_dir: str, task_type: str, batch_size: int, global_rank: int = 0,
+             global_world_size: int = 1, resolution: Tuple[int, int, int] = (128, 128, 128), qualitative=None,
+             num_data_workers: int = 0, device="cuda", **voxelization) -> Optional[float]:
+  """One evaluation run over this rank's share of `dataset` (EvalPipeline.run_eval, pipeline.py:292-343): per batch the
+  ground truth is voxelized at `resolution` and scored into the confusion matrix over dataset.classes; at the end the
+  matrix is summed over the ranks and rank 0 writes <output_dir>/voxel_metrics.csv and returns the mean IoU over the
+  non-void classes (the other ranks return None).
+
+  inference: called as inference(image, camera_transform, v2x_transform, grid_offsets, resolution) -> pmf, like the
+  reference's InferenceFn.  When it also has `predict_labels` (SuperResolutionInference over a CoreNet) the batch is
+  scored without a pmf, pass by pass (evaluation_results.QuantitativeResults.add_batch_streaming); the pmf is then
+  computed only for the batches a given `qualitative` (evaluation_results.QualitativeResults) wants to draw.  Such a
+  batch runs the network twice, encoder and all m^3 decoder passes: once for the pmf to draw and once for the labels.
+  device: where the batches and the confusion matrix are put, as in evaluate_batch.
+  voxelization: the keyword arguments of voxelize_batch other than task_type and resolution."""
+  from corenet_amd import evaluation_results as results_lib
+  loader = create_distributed_loader(dataset, batch_size, global_rank, global_world_size,
+                                     num_data_workers=num_data_workers, pad_data=False)
+  quantitative = results_lib.QuantitativeResults(dataset.classes, task_type)
+  resolution = tuple(int(v) for v in resolution)
+  streaming = hasattr(inference, "predict_labels")
+  for batch in loader:
+    ex = batched_example.batch(batch, device=device)
+    ex = voxelize_batch(ex, task_type, resolution=resolution, **voxelization)
+    draw = qualitative is not None and qualitative.wants(ex)
+    pmf = None
+    if draw or not streaming:
+      with t.no_grad():
+        pmf = inference(ex.input_image, ex.camera_transform, ex.v2x_transform, ex.grid_sampling_offset, resolution)
+    if streaming:
+      quantitative.add_batch_streaming(inference, ex)
+    else:
+      quantitative.add_batch(pmf, ex)
+    if draw:
+      qualitative.add_batch(pmf, ex)
+  if quantitative.confusion_matrix is None:           # a rank without a batch still takes part in the sum
+    K = len(quantitative.classes)
+    quantitative.confusion_matrix = t.zeros((K, K), dtype=t.int64, device=device)
+    quantitative.bad = t.zeros((1,), dtype=t.int32, device=device)
+  quantitative.compute_metrics()
+  if global_rank != 0:
+    return None
+  quantitative.write_csv(os.path.join(output_dir, "voxel_metrics.csv"))
+  return quantitative.get_mean_iou()

@@ -6,9 +6,10 @@ Same classes, argument meaning and errors as the reference.  The MI355X-specific
 `super_resolution_from_state`: its inference function runs the offset-independent ResNet-50 encoder
 once per image batch and only the decoder per offset (`CoreNet.multi_offset_pmf`), and the softmax +
 stack + reshape + permute + reshape of super_resolution.py:105-112,124 is one HIP kernel with coalesced
-writes (`crn_softmax_superres`).
+writes (`crn_softmax_superres`).  `predict_labels` is the evaluation form: labels and confusion matrix per pass
+(`crn_eval_labels`), no stash of the passes and no pmf.
 """
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch as t
 
@@ -59,13 +60,19 @@ class SuperResolutionInference:
     unit = self._unit_offsets(output_resolution, m).to(grid_offsets.device)
     return unit.unsqueeze(1) + grid_offsets.unsqueeze(0) / m
 
-  def __call__(self, input_image: t.Tensor, camera_transform: t.Tensor, view_to_voxel_transform: t.Tensor,
-               grid_offsets: t.Tensor, output_resolution: Tuple[int, int, int]) -> t.Tensor:
-    """pmf f32[B, C, m*D, m*H, m*W] (super_resolution.py:92-112)."""
+  def _native_passes(self, view_to_voxel_transform: t.Tensor, grid_offsets: t.Tensor,
+                     output_resolution: Tuple[int, int, int]):
+    """(m, offsets f32[m^3, B, 3], view -> voxel transform of the native grid) of an output resolution."""
     m = self.get_resolution_multiplier(output_resolution)
     offsets = self.get_native_offsets(output_resolution, grid_offsets)
     # the native grid spans the same volume with m times fewer voxels per axis
     v2x_native = view_to_voxel_transform @ transformations.scale([1.0 / m] * 3).to(view_to_voxel_transform.device)
+    return m, offsets, v2x_native
+
+  def __call__(self, input_image: t.Tensor, camera_transform: t.Tensor, view_to_voxel_transform: t.Tensor,
+               grid_offsets: t.Tensor, output_resolution: Tuple[int, int, int]) -> t.Tensor:
+    """pmf f32[B, C, m*D, m*H, m*W] (super_resolution.py:92-112)."""
+    m, offsets, v2x_native = self._native_passes(view_to_voxel_transform, grid_offsets, output_resolution)
     fused = getattr(self.inference_fn, "interleaved", None)
     if fused is not None:       # HIP path: softmax + interleave in one kernel, [B, C, mD, mH, mW] directly
       return fused(input_image, camera_transform, v2x_native, offsets, m)
@@ -74,6 +81,23 @@ class SuperResolutionInference:
     # [iz, iy, ix, B, C, D, H, W] -> [B, C, D, iz, H, iy, W, ix] -> fine voxel = coarse voxel * m + sub-position
     fine = pmfs.reshape(m, m, m, B, C, D, H, W).permute(3, 4, 5, 0, 6, 1, 7, 2)
     return fine.reshape(B, C, m * D, m * H, m * W)
+
+  def predict_labels(self, input_image: t.Tensor, camera_transform: t.Tensor, view_to_voxel_transform: t.Tensor,
+                     grid_offsets: t.Tensor, output_resolution: Tuple[int, int, int], gt: Optional[t.Tensor] = None,
+                     num_classes: Optional[int] = None, scene_classes: Optional[t.Tensor] = None,
+                     cm: Optional[t.Tensor] = None, bad: Optional[t.Tensor] = None) -> t.Tensor:
+    """Predicted labels int32[B, m*D, m*H, m*W] at the output resolution (the argmax of __call__'s pmf, times the scene
+    class when given) without the pmf: every native pass goes from logits to its sub-lattice of the label grid, and with
+    gt int32[B, m*D, m*H, m*W] into the confusion matrix cm int64[K, K] / the out-of-range count bad int32[1] on the way
+    (`CoreNet.multi_offset_labels`).  The native resolution (m = 1) takes the same path.  TypeError when the wrapped
+    inference function cannot stream labels."""
+    streaming = getattr(self.inference_fn, "labels", None)
+    if streaming is None:
+      raise TypeError(f"{type(self.inference_fn).__name__} has no labels(): predict_labels needs an inference function that "
+                      "streams labels (CoreNetMultiOffset)")
+    m, offsets, v2x_native = self._native_passes(view_to_voxel_transform, grid_offsets, output_resolution)
+    return streaming(input_image, camera_transform, v2x_native, offsets, m, gt=gt, num_classes=num_classes,
+                     scene_classes=scene_classes, cm=cm, bad=bad)
 
 
 class CoreNetMultiOffset(MultiOffsetInferenceFn):
@@ -92,6 +116,12 @@ class CoreNetMultiOffset(MultiOffsetInferenceFn):
   def interleaved(self, input_image, camera_transform, view_to_voxel_transform, grid_offsets, m):
     return self.model.multi_offset_pmf(input_image, self._v2s(camera_transform, view_to_voxel_transform),
                                        grid_offsets, resolution_multiplier=m)
+
+  def labels(self, input_image, camera_transform, view_to_voxel_transform, grid_offsets, m, gt=None, num_classes=None,
+             scene_classes=None, cm=None, bad=None):
+    """int32[B, m*D, m*H, m*W] labels of the m^3 passes, streamed (`CoreNet.multi_offset_labels`)."""
+    return self.model.multi_offset_labels(input_image, self._v2s(camera_transform, view_to_voxel_transform), grid_offsets,
+                                          m, gt=gt, num_classes=num_classes, scene_classes=scene_classes, cm=cm, bad=bad)
 
 
 def super_resolution_from_state(state) -> SuperResolutionInference:

@@ -536,6 +536,27 @@ int crn_argmax_confusion(const float* logits, const int32_t* gt, int B, int C, i
 int crn_softmax_superres(const float* logits, int m, int B, int C, int D, int H, int W, float* out,
                          crnStream s);
 
+/* Streaming evaluation epilogue (evaluation_results.py:42-54,249-253 + super_resolution.py:92-112 without the pmf;
+ * csrc/eval_labels.hip, host twin csrc/eval_labels_cpu.cpp).  scores [B][C][D][H][W] are the logits
+ * (or any per-class scores) of ONE native pass of an x m inference, pass n = (iz*m + iy)*m + ix in the offset order of
+ * crn_softmax_superres: coarse voxel (b, z, y, x) is fine voxel (b, z*m+iz, y*m+iy, x*m+ix) of the [B][mD][mH][mW] grids.
+ *   pred    index of the first maximum over c (only a strictly larger score replaces the running best: a NaN never
+ *           does, a NaN at class 0 stays), times scene_class[b] when scene_class is given (fg_bg: the scene's label)
+ *   labels  (may be NULL) receives pred (as int32) at the fine voxel; the other m^3 - 1 sub-lattices are not touched
+ *   gt      (may be NULL) the fine-grid label, times scene_class[b] when given: both it and pred in [0, K) ->
+ *           cm[g*K + pred] += 1, otherwise bad[0] += 1 and nothing is counted.  cm int64 [K][K] and bad int32 [1] are
+ *           ACCUMULATED (required with gt); integer sums: the same inputs give the same bits on every run
+ * m = 1, n = 0, K = C, scene_class NULL computes what crn_argmax_confusion computes.  1 <= C <= 32, 1 <= K <= 64, m >= 1,
+ * 0 <= n < m^3, B, D, H, W >= 1 (the GPU call: B <= 65535), the byte sizes of scores and of the fine grid
+ * (4 * B * D * H * W * m^3) within int64, scores and one of gt / labels given: anything else returns
+ * CRN_EINVAL, launches nothing and writes nothing.  The GPU call does not wait for the GPU; the twin takes HOST memory. */
+#define CRN_EVAL_MAX_CLASSES 32
+#define CRN_EVAL_MAX_BINS 64
+int crn_eval_labels(const float* scores, const int32_t* gt, const int32_t* scene_class, int B, int C, int K, int D, int H,
+                    int W, int m, int n, int32_t* labels, int64_t* cm, int32_t* bad, crnStream s);
+int crn_eval_labels_cpu(const float* scores, const int32_t* gt, const int32_t* scene_class, int B, int C, int K, int D, int H,
+                        int W, int m, int n, int32_t* labels, int64_t* cm, int32_t* bad, int num_threads);
+
 /* ---------------- optimizer --------------------------------------------------
  * torch.optim.Adam step (state.py:65; train hot loop pipeline.py:230) on a flat
  * fp32 parameter slab.  grad_scale multiplies the gradient first (1/world).   */
