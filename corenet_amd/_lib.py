@@ -53,7 +53,15 @@ class CrnBf3Plan(C.Structure):
                                         "dmode", "tpw", "twt", "pipe", "inherit", "boxskip", "lds_bytes")]
 
 
+class CrnE2dPlan(C.Structure):
+  """Mirror of crnE2dPlan (include/corenet_hip.h)."""
+  _fields_ = [(n, C.c_int32) for n in ("kernel", "tiles", "nblk", "nchunks", "per_split", "splits", "mode", "tab", "lds_bytes",
+                                        "grid_x", "grid_y", "grid_z", "row_tiles", "col_tiles", "ksteps", "per_block")] + [
+                                            ("zero_bytes", C.c_int64)]
+
+
 BF3_KINDS = {0: "plain", 1: "half", 2: "ws"}
+E2D_KERNELS = {1: "k1", 2: "k3w16", 3: "k3w8", 4: "wg1", 5: "wg3"}
 PLAN_PATHS = {1: "dense_cols", 2: "dense_rows", 3: "dense_wgrad", 4: "pointwise", 5: "generic"}
 
 
@@ -123,6 +131,10 @@ _SIGS = {
                               i32, i32, vp],
     "crn_conv2d_bf3": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32, C.POINTER(CrnView),
                        i32, i32, i32, i32, i32, vp],
+    "crn_conv2d_bf3_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32, C.POINTER(CrnView),
+                            i32, i32, i32, i32, i32, vp],
+    "crn_conv_wgrad_2d_bf3_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), C.POINTER(CrnView), vp, i32, i32, i32, i32,
+                                   i32, i32, vp],
     "crn_copy_tiles_f32": [vp, vp, vp, vp, vp, i64, i32, vp],
     "crn_copy_mats_f32": [vp, vp, vp, i64, i32, vp],
     "crn_gather_f32": [vp, vp, vp, i64, vp],

@@ -239,6 +239,30 @@ class HipBackend:
     self.lib.crn_conv2d_bf3(C.byref(_cview(x)), _ctr(tr), ptr(wop), npad, ptr(bias), bias_sB, C.byref(_cview(y)),
                             window[1], window[2], pad_lo[1], pad_lo[2], int(accumulate), _lib.stream())
 
+  @staticmethod
+  def _e2d_plan_dict(p) -> dict:
+    d = {n: int(getattr(p, n)) for n, _ in p._fields_}
+    d["kernel"] = _lib.E2D_KERNELS[d["kernel"]]
+    return d
+
+  def conv2d_bf3_plan(self, x: View, tr: Optional[Transform], wop: t.Tensor, npad: int, bias: Optional[t.Tensor],
+                      bias_sB: int, y: View, window, pad_lo, accumulate: bool = False) -> dict:
+    """What conv2d_bf3 would launch (crn_conv2d_bf3_plan): a dict of the crnE2dPlan fields, kernel by name.  Host arithmetic
+    only, as conv_fwd_plan; a rejected call raises HipError."""
+    assert window[0] == 1 and pad_lo[0] == 0
+    p = _lib.CrnE2dPlan()
+    self.lib.crn_conv2d_bf3_plan(C.byref(_cview(x)), _ctr(tr), ptr(wop), npad, ptr(bias), bias_sB, C.byref(_cview(y)),
+                                 window[1], window[2], pad_lo[1], pad_lo[2], int(accumulate), C.addressof(p))
+    return self._e2d_plan_dict(p)
+
+  def conv_wgrad_2d_bf3_plan(self, x: View, tr: Optional[Transform], dy: View, dw: t.Tensor, npad: int, window, pad_lo,
+                             zero_first: bool = True) -> dict:
+    """What conv_wgrad(math="bf16x3_2d") would launch (crn_conv_wgrad_2d_bf3_plan); see conv2d_bf3_plan."""
+    p = _lib.CrnE2dPlan()
+    self.lib.crn_conv_wgrad_2d_bf3_plan(C.byref(_cview(x)), _ctr(tr), C.byref(_cview(dy)), ptr(dw), npad, window[1],
+                                        window[2], pad_lo[1], pad_lo[2], int(zero_first), C.addressof(p))
+    return self._e2d_plan_dict(p)
+
   def _ximage(self, xp: int, sB: int, B: int, D: int, H: int, W: int, tr: Optional[Transform], alloc) -> t.Tensor:
     """T(x) transformed and split once (crn_convt_s2k7_ximage) instead of in every workgroup of the four parity pairs of the
     weight gradient; xp: address of x [B,16,D,H,W], dense inside a sample; alloc(bytes) -> the uint8 buffer of the image."""

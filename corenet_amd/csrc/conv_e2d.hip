@@ -724,37 +724,39 @@ template <int T, int CB, int TW>
 int launch_e2d(const E2dGeom& g, dim3 grid, size_t lds, hipStream_t st) {
   return crn_launch(conv_e2d_kernel<T, CB, TW>, grid, dim3(256), lds, st, g);
 }
-}  // namespace
 
-extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const void* wop, int Npad, const float* bias,
-                              int bias_sB, const crnView* y, int kh, int kw, int ph, int pw, int accumulate,
-                              crnStream stream) {
+// Everything crn_conv2d_bf3 decides -- every rejection, the LDS bound included, the kernel, the split and the grid -- as host
+// arithmetic (no HIP call), shared by the launch and crn_conv2d_bf3_plan so that there is one copy of the selection.
+struct E2dFwdSel {
+  E2dGeom g;               // y = the caller's view, mode = 3 for a split (the launch redirects y to the scratch)
+  int kernel;              // CRN_E2D_K1 / K3W16 / K3W8
+  int64_t tiles, S;
+  int splits;
+  size_t lds;
+  unsigned grid[3];
+};
+
+int e2d_fwd_select(const crnView* x, const crnInTransform* tr, const void* wop, int Npad, const float* bias, int bias_sB,
+                   const crnView* y, int kh, int kw, int ph, int pw, int accumulate, E2dFwdSel* s) {
   if (!x || !y || !wop || x->B != y->B || x->B < 1) return CRN_EINVAL;
   if (!dense_2d(*x) || !dense_2d(*y)) return CRN_EINVAL;
-  if ((x->C & 31) || (y->C & 63) || Npad != y->C) return CRN_EINVAL;
-  if (x->D != y->D || x->H != y->H || x->W != y->W) return CRN_EINVAL;
+  if (x->C < 32 || (x->C & 31) || y->C < 64 || (y->C & 63) || Npad != y->C) return CRN_EINVAL;
+  if (x->D != y->D || x->H != y->H || x->W != y->W || x->D < 1 || x->H < 1 || x->W < 1) return CRN_EINVAL;
   const bool k3 = kh == 3 && kw == 3, k1 = kh == 1 && kw == 1;
   if (!k3 && !k1) return CRN_EINVAL;
   if (k1 && (ph || pw)) return CRN_EINVAL;
   const int64_t S = (int64_t)x->D * x->H * x->W;
-  if (S * x->C * 4 >= ((int64_t)1 << 31)) return CRN_EINVAL;           // one sample inside the 2 GiB buffer range
-  hipStream_t st = (hipStream_t)stream;
-  int rcf;
-  const bool armed = crn_splitk_begin(st, &rcf);
-  if (rcf != CRN_OK) return rcf;
-  E2dGeom g{};
+  // one sample inside the 2 GiB buffer range: the last channel plane ends at (C - 1) * sC + S (sC >= S is not required of a
+  // view, so both are looked at); the operand blocks of the layer (Cin * taps * Npad floats) inside their own range as well
+  if (S * x->C * 4 >= ((int64_t)1 << 31) || ((int64_t)(x->C - 1) * x->sC + S) * 4 >= ((int64_t)1 << 31) || x->sC < 0)
+    return CRN_EINVAL;
+  if ((int64_t)x->C * (k3 ? 9 : 1) * Npad >= ((int64_t)1 << 29)) return CRN_EINVAL;
+  E2dGeom& g = s->g;
+  g = E2dGeom{};
   g.x = *x; g.y = *y;
   if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
   g.wop = wop; g.bias = bias; g.bias_sB = bias_sB;
   g.ntn = Npad / 16; g.nblk = x->C / 32; g.ph = ph; g.pw = pw;
-#ifdef CRN_TOOLS
-  static const bool want_stamps = getenv("CRN_E2D_DBG") && (atoi(getenv("CRN_E2D_DBG")) & 16);
-  if (want_stamps) {
-    if (!g_stamps) CRN_HIP(hipMalloc(&g_stamps, 32 * sizeof(long long)));
-    g.stamps = g_stamps;
-    g.dbg = 16;
-  }
-#endif
   int TW = 16, CB = 1;
   int64_t tiles;
   if (k3) {
@@ -779,26 +781,68 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
   g.chunks_per_split = (g.nchunks + splits - 1) / splits;
   splits = (g.nchunks + g.chunks_per_split - 1) / g.chunks_per_split;
   g.tab = g.tr.scale ? g.chunks_per_split * CB * 32 : 0;
-  const crnView yreal = *y;
-  float* scratch = nullptr;
-  if (splits > 1) {
-    scratch = crn_splitk_scratch((size_t)splits * x->B * y->C * S, st);
-    if (!scratch) return CRN_ENOMEM;
-    g.y = crn_splitk_scratch_view(yreal, scratch);
-    g.mode = 3;
-  } else {
-    g.mode = accumulate ? 1 : 0;
-  }
+  g.mode = splits > 1 ? 3 : (accumulate ? 1 : 0);
   const size_t plane_bytes = (size_t)(k3 ? 4 * (128 + 4) : 16 * (64 + 4)) * 16;   // conv_e2d_kernel: PLANE
   const size_t lds = (size_t)g.tab * 8 + 4 * plane_bytes;
   if (lds > 160 * 1024) return CRN_EINVAL;
-  const dim3 grid((unsigned)(tiles * x->B), (unsigned)(y->C / 64), (unsigned)splits);
+  if (tiles * x->B > 0x7fffffff) return CRN_EINVAL;
+  s->kernel = k1 ? CRN_E2D_K1 : TW == 16 ? CRN_E2D_K3W16 : CRN_E2D_K3W8;
+  s->tiles = tiles; s->S = S; s->splits = splits; s->lds = lds;
+  s->grid[0] = (unsigned)(tiles * x->B); s->grid[1] = (unsigned)(y->C / 64); s->grid[2] = (unsigned)splits;
+  return CRN_OK;
+}
+}  // namespace
+
+extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const void* wop, int Npad, const float* bias,
+                              int bias_sB, const crnView* y, int kh, int kw, int ph, int pw, int accumulate,
+                              crnStream stream) {
+  E2dFwdSel s;
+  const int rcs = e2d_fwd_select(x, tr, wop, Npad, bias, bias_sB, y, kh, kw, ph, pw, accumulate, &s);
+  if (rcs != CRN_OK) return rcs;          // before crn_splitk_begin: the arming stays for the engine the caller falls back to
+  hipStream_t st = (hipStream_t)stream;
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
+  E2dGeom& g = s.g;
+#ifdef CRN_TOOLS
+  static const bool want_stamps = getenv("CRN_E2D_DBG") && (atoi(getenv("CRN_E2D_DBG")) & 16);
+  if (want_stamps) {
+    if (!g_stamps) CRN_HIP(hipMalloc(&g_stamps, 32 * sizeof(long long)));
+    g.stamps = g_stamps;
+    g.dbg = 16;
+  }
+#endif
+  const int splits = s.splits;
+  const crnView yreal = *y;
+  float* scratch = nullptr;
+  if (splits > 1) {
+    scratch = crn_splitk_scratch((size_t)splits * x->B * y->C * s.S, st);
+    if (!scratch) return CRN_ENOMEM;
+    g.y = crn_splitk_scratch_view(yreal, scratch);
+  }
+  const dim3 grid(s.grid[0], s.grid[1], s.grid[2]);
   int rc;
-  if (k1) rc = launch_e2d<1, 4, 16>(g, grid, lds, st);
-  else if (TW == 16) rc = launch_e2d<9, 1, 16>(g, grid, lds, st);
-  else rc = launch_e2d<9, 1, 8>(g, grid, lds, st);
+  if (s.kernel == CRN_E2D_K1) rc = launch_e2d<1, 4, 16>(g, grid, s.lds, st);
+  else if (s.kernel == CRN_E2D_K3W16) rc = launch_e2d<9, 1, 16>(g, grid, s.lds, st);
+  else rc = launch_e2d<9, 1, 8>(g, grid, s.lds, st);
   if (rc == CRN_OK && splits > 1) rc = crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st);
   return rc;
+}
+
+extern "C" int crn_conv2d_bf3_plan(const crnView* x, const crnInTransform* tr, const void* wop, int Npad, const float* bias,
+                                   int bias_sB, const crnView* y, int kh, int kw, int ph, int pw, int accumulate,
+                                   crnE2dPlan* out) {
+  if (!out) return CRN_EINVAL;
+  E2dFwdSel s;
+  const int rcs = e2d_fwd_select(x, tr, wop, Npad, bias, bias_sB, y, kh, kw, ph, pw, accumulate, &s);
+  if (rcs != CRN_OK) return rcs;
+  const E2dGeom& g = s.g;
+  crnE2dPlan p{};
+  p.kernel = s.kernel; p.tiles = (int)s.tiles; p.nblk = g.nblk; p.nchunks = g.nchunks; p.per_split = g.chunks_per_split;
+  p.splits = s.splits; p.mode = g.mode; p.tab = g.tab; p.lds_bytes = (int)s.lds;
+  p.grid_x = (int)s.grid[0]; p.grid_y = (int)s.grid[1]; p.grid_z = (int)s.grid[2];
+  *out = p;
+  return CRN_OK;
 }
 
 // tuning aid (CRN_E2D_DBG=16): the shader-clock stamps of the last crn_conv2d_bf3 call (synchronises the device)
@@ -820,52 +864,90 @@ extern "C" int crn_conv_wgrad_1x1_bf3(const crnView* x, const crnInTransform* tr
   return crn_conv_wgrad_2d_bf3(x, tr, dy, dw, Npad, 1, 1, 0, 0, zero_first, stream);
 }
 
-extern "C" int crn_conv_wgrad_2d_bf3(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
-                                     int kh, int kw, int ph, int pw, int zero_first, crnStream stream) {
-  CRN_ENTRY(stream);
+namespace {
+// As e2d_fwd_select, for crn_conv_wgrad_2d_bf3 and crn_conv_wgrad_2d_bf3_plan: every rejection and every choice, no HIP call.
+struct E2dWgSel {
+  int kernel;              // CRN_E2D_WG1 / WG3
+  Wg1Geom g1;
+  Wg3Geom g3;
+  int row_tiles, col_tiles, splits, ksteps, per_block;
+  size_t dw_bytes;         // what zero_first clears
+};
+
+int e2d_wg_select(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad, int kh, int kw, int ph,
+                  int pw, E2dWgSel* s) {
   if (!x || !dy || !dw || Npad <= 0 || (Npad & 15) || x->B != dy->B || dy->C > Npad) return CRN_EINVAL;
+  if (x->B < 1 || x->C < 1 || dy->C < 1 || x->D < 1 || x->H < 1 || x->W < 1) return CRN_EINVAL;
   if (!dense_2d(*x) || !dense_2d(*dy)) return CRN_EINVAL;
   if (x->D != dy->D || x->H != dy->H || x->W != dy->W) return CRN_EINVAL;
   const int64_t S = (int64_t)x->D * x->H * x->W;
   if (S % 32 || x->sC != S || dy->sC != S) return CRN_EINVAL;
   if (S * x->C * 4 >= ((int64_t)1 << 31) || S * dy->C * 4 >= ((int64_t)1 << 31)) return CRN_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (kh == 3 && kw == 3) {
+  if ((int64_t)x->B * S / 32 > 0x7fffffff) return CRN_EINVAL;
+  const bool k3 = kh == 3 && kw == 3;
+  if (k3) {
     if (ph != 1 || pw != 1 || x->D != 1 || (x->W & 7)) return CRN_EINVAL;
-    if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * 9 * Npad * 4, st));
-    Wg3Geom g{};
+  } else if (kh != 1 || kw != 1 || ph || pw) {
+    return CRN_EINVAL;
+  }
+  const int ksteps = (int)((int64_t)x->B * S / 32);
+  const int row_tiles = k3 ? crn_cdiv(3 * x->C, 32) : crn_cdiv(x->C, 64), col_tiles = crn_cdiv(dy->C, 32);
+  const int tiles = row_tiles * col_tiles;
+  constexpr int kFill = 512;
+  int splits = std::max(1, std::min(ksteps / 8, crn_cdiv(kFill, tiles)));         // >= 2 K steps per wave
+  if (crn_deterministic()) splits = 1;
+  const int per_block = crn_cdiv(ksteps, splits);
+  splits = crn_cdiv(ksteps, per_block);
+  s->kernel = k3 ? CRN_E2D_WG3 : CRN_E2D_WG1;
+  s->row_tiles = row_tiles; s->col_tiles = col_tiles; s->splits = splits; s->ksteps = ksteps; s->per_block = per_block;
+  s->dw_bytes = (size_t)x->C * (k3 ? 9 : 1) * Npad * 4;
+  if (k3) {
+    Wg3Geom& g = s->g3;
+    g = Wg3Geom{};
     g.x = x->base; g.dy = dy->base; g.dw = dw;
     g.scale = tr ? tr->scale : nullptr; g.shift = tr ? tr->shift : nullptr;
     g.pre_relu = tr ? tr->pre_relu : 0; g.post_relu = tr ? tr->post_relu : 0;
     g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S; g.H = x->H; g.W = x->W;
-    g.ksteps = (int)((int64_t)x->B * S / 32);
-    const int tiles = crn_cdiv(3 * x->C, 32) * crn_cdiv(dy->C, 32);
-    constexpr int kFill3 = 512;
-    int splits = std::max(1, std::min(g.ksteps / 8, crn_cdiv(kFill3, tiles)));
-    if (crn_deterministic()) splits = 1;
-    g.ksteps_per_block = crn_cdiv(g.ksteps, splits);
-    splits = crn_cdiv(g.ksteps, g.ksteps_per_block);
-    const dim3 grid((unsigned)crn_cdiv(3 * x->C, 32), (unsigned)crn_cdiv(dy->C, 32), (unsigned)splits);
-    hipLaunchKernelGGL(wgrad3x3_bf3_kernel, grid, dim3(256), 0, st, g);
-    CRN_CHECK_LAUNCH();
-    return CRN_OK;
+    g.ksteps = ksteps; g.ksteps_per_block = per_block;
+  } else {
+    Wg1Geom& g = s->g1;
+    g = Wg1Geom{};
+    g.x = x->base; g.dy = dy->base; g.dw = dw;
+    g.scale = tr ? tr->scale : nullptr; g.shift = tr ? tr->shift : nullptr;
+    g.pre_relu = tr ? tr->pre_relu : 0; g.post_relu = tr ? tr->post_relu : 0;
+    g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S;
+    g.ksteps = ksteps; g.ksteps_per_block = per_block;
   }
-  if (kh != 1 || kw != 1 || ph || pw) return CRN_EINVAL;
-  if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * Npad * 4, st));
-  Wg1Geom g{};
-  g.x = x->base; g.dy = dy->base; g.dw = dw;
-  g.scale = tr ? tr->scale : nullptr; g.shift = tr ? tr->shift : nullptr;
-  g.pre_relu = tr ? tr->pre_relu : 0; g.post_relu = tr ? tr->post_relu : 0;
-  g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S;
-  g.ksteps = (int)((int64_t)x->B * S / 32);
-  const int tiles = crn_cdiv(x->C, 64) * crn_cdiv(dy->C, 32);
-  constexpr int kFill = 512;
-  int splits = std::max(1, std::min(g.ksteps / 8, crn_cdiv(kFill, tiles)));       // >= 2 K steps per wave
-  if (crn_deterministic()) splits = 1;
-  g.ksteps_per_block = crn_cdiv(g.ksteps, splits);
-  splits = crn_cdiv(g.ksteps, g.ksteps_per_block);
-  const dim3 grid((unsigned)crn_cdiv(x->C, 64), (unsigned)crn_cdiv(dy->C, 32), (unsigned)splits);
-  hipLaunchKernelGGL(wgrad1x1_bf3_kernel, grid, dim3(256), 0, st, g);
+  return CRN_OK;
+}
+}  // namespace
+
+extern "C" int crn_conv_wgrad_2d_bf3(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                                     int kh, int kw, int ph, int pw, int zero_first, crnStream stream) {
+  CRN_ENTRY(stream);
+  E2dWgSel s;
+  const int rcs = e2d_wg_select(x, tr, dy, dw, Npad, kh, kw, ph, pw, &s);
+  if (rcs != CRN_OK) return rcs;
+  hipStream_t st = (hipStream_t)stream;
+  // behind the last rejection: a rejected call writes nothing
+  if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, s.dw_bytes, st));
+  const dim3 grid((unsigned)s.row_tiles, (unsigned)s.col_tiles, (unsigned)s.splits);
+  if (s.kernel == CRN_E2D_WG3) hipLaunchKernelGGL(wgrad3x3_bf3_kernel, grid, dim3(256), 0, st, s.g3);
+  else hipLaunchKernelGGL(wgrad1x1_bf3_kernel, grid, dim3(256), 0, st, s.g1);
   CRN_CHECK_LAUNCH();
+  return CRN_OK;
+}
+
+extern "C" int crn_conv_wgrad_2d_bf3_plan(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                                          int kh, int kw, int ph, int pw, int zero_first, crnE2dPlan* out) {
+  if (!out) return CRN_EINVAL;
+  E2dWgSel s;
+  const int rcs = e2d_wg_select(x, tr, dy, dw, Npad, kh, kw, ph, pw, &s);
+  if (rcs != CRN_OK) return rcs;
+  crnE2dPlan p{};
+  p.kernel = s.kernel; p.row_tiles = s.row_tiles; p.col_tiles = s.col_tiles; p.ksteps = s.ksteps; p.per_block = s.per_block;
+  p.splits = s.splits; p.zero_bytes = zero_first ? (int64_t)s.dw_bytes : 0;
+  p.grid_x = s.row_tiles; p.grid_y = s.col_tiles; p.grid_z = s.splits;
+  *out = p;
   return CRN_OK;
 }

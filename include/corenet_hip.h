@@ -267,7 +267,9 @@ int crn_bf3_operands(const float* packed, const int64_t* desc, int nlayers, int6
  * bias contract as crn_conv_fwd; forward pass, or data gradient with the packed data-gradient weights).
  * Covers: window 1x1 (pads 0) or 3x3, dense NC(D)HW views (unit W stride, rows and planes back to back), x and y of
  * the same extent, Cin % 32 == 0, Cout % 64 == 0 (= Npad), H*W a multiple of 64 (3x3: W % 8 == 0 and tiles of
- * 4x16 / 8x8 positions divide the image); CRN_EINVAL otherwise (callers keep such layers on crn_conv_fwd).
+ * 4x16 / 8x8 positions divide the image), 3x3 pads 0..2 per axis, one sample of x and the layer's operand blocks below
+ * 2 GiB each; CRN_EINVAL otherwise, before anything is written and without consuming the arming of crn_splitk_defer
+ * (callers keep such layers on crn_conv_fwd).
  * Split-K partial sums use the per-stream scratch shared with crn_conv_fwd (crn_splitk_reserve).                */
 int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const void* wop, int Npad, const float* bias,
                    int bias_sB, const crnView* y, int kh, int kw, int ph, int pw, int accumulate, crnStream stream);
@@ -282,6 +284,33 @@ int crn_conv_wgrad_1x1_bf3(const crnView* x, const crnInTransform* tr, const crn
  * input row come from one aligned 8-position load plus its two edge elements (dw row = c*9 + zh*3 + zw).        */
 int crn_conv_wgrad_2d_bf3(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
                           int kh, int kw, int ph, int pw, int zero_first, crnStream stream);
+
+/* Which kernel a call of the encoder engine gets and how it is laid out, as crn_conv_fwd_bf3_plan says it for the decoder
+ * engine: the selection the launches themselves run, host arithmetic only (no GPU needed), CRN_EINVAL where the launch
+ * returns it.  A launch that wants to split is described as it runs when the split-K scratch can be had.          */
+#define CRN_E2D_K1 1      /* conv_e2d_kernel<1, 4, 16>: 1x1, chunks of 128 channels */
+#define CRN_E2D_K3W16 2   /* conv_e2d_kernel<9, 1, 16>: 3x3, tiles of 4 x 16 positions */
+#define CRN_E2D_K3W8 3    /* conv_e2d_kernel<9, 1, 8>: 3x3, tiles of 8 x 8 positions */
+#define CRN_E2D_WG1 4     /* wgrad1x1_bf3_kernel */
+#define CRN_E2D_WG3 5     /* wgrad3x3_bf3_kernel */
+typedef struct {
+  int32_t kernel;              /* CRN_E2D_* */
+  int32_t tiles;               /* forward: position tiles of 64 per sample */
+  int32_t nblk;                /* forward: 32-channel blocks of x */
+  int32_t nchunks;             /* forward: chunks (3x3: one block, 1x1: four) */
+  int32_t per_split, splits;   /* forward: chunks per split, splits = ceil(nchunks / per_split); weight gradient: splits of K */
+  int32_t mode;                /* forward: 0 store, 1 accumulate, 3 partial sums to the scratch */
+  int32_t tab;                 /* forward: entries of the scale / shift tables in LDS (0 without a transform) */
+  int32_t lds_bytes;           /* forward: dynamic LDS */
+  int32_t grid_x, grid_y, grid_z;
+  int32_t row_tiles, col_tiles;   /* weight gradient: tiles of 64 channels (3x3: 32 (c, zh) pairs) x 32 columns */
+  int32_t ksteps, per_block;   /* weight gradient: K steps of 32 positions, per workgroup along z */
+  int64_t zero_bytes;          /* weight gradient: what zero_first clears (0: the caller cleared dw) */
+} crnE2dPlan;
+int crn_conv2d_bf3_plan(const crnView* x, const crnInTransform* tr, const void* wop, int Npad, const float* bias,
+                        int bias_sB, const crnView* y, int kh, int kw, int ph, int pw, int accumulate, crnE2dPlan* out);
+int crn_conv_wgrad_2d_bf3_plan(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
+                               int kh, int kw, int ph, int pw, int zero_first, crnE2dPlan* out);
 
 /* dst[i] = idx[i] >= 0 ? src[idx[i]] : 0        (weight packing)            */
 /* Tiled index copy between a reference-layout buffer and a packed buffer (weight pack / gradient un-pack).

@@ -280,17 +280,22 @@ def build(c: Case):
     desc, blocks = G.operand_table([(0, 0, geo, True)])
     b.slab = t.zeros(G.slab_entries(geo) * 32, dtype=t.uint8)
     _EMU.bf3_operands(b.wp, (t.as_tensor(desc), blocks), b.slab)
-  b.bias_sB = 0
-  if c.bias_b:                          # rows of [B][Npad]; columns past Cout are never read for a real output
-    b.bp = t.randn(c.B, b.npad, generator=g)
-    b.bp[:, b.ycout:] = 0
-    b.bias_sB = b.npad
+  sample_bias(b, g)
   if c.fuse == "bnbwd":                 # the BatchRenorm whose output gradient y is: its input (before the ReLU) and mu, rstd, r, d
     S = c.odims[0] * c.odims[1] * c.odims[2]
     b.bn_x = t.randn(c.B * b.ycout * S + 4, generator=g)
     b.bn_saved = t.cat([t.rand(b.ycout, generator=g) * 0.4, 1.0 / (t.rand(b.ycout, generator=g) * 0.5 + 0.3),
                         t.rand(b.ycout, generator=g) * 0.5 + 0.75, t.randn(b.ycout, generator=g) * 0.1]).contiguous()
   return b
+
+
+def sample_bias(b, g):
+  """Sets b.bias_sB, and for a bias_b row replaces the shared bias row by one row per sample (bias_sB = Npad)."""
+  b.bias_sB = 0
+  if b.case.bias_b:                     # rows of [B][Npad]; columns past Cout are never read for a real output
+    b.bp = t.randn(b.case.B, b.npad, generator=g)
+    b.bp[:, b.ycout:] = 0
+    b.bias_sB = b.npad
 
 
 def bias_logical(b, dtype=t.float64):
