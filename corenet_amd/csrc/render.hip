@@ -9,7 +9,8 @@
 //   -- the caller reads the total (the one synchronisation) and sizes the tile lists --
 //   fill    same threads as setup: every overlapped tile gets the record id at offset + (atomic decrement of its count)
 //   raster  one workgroup per (image, tile), one pixel per lane: walk the tile's list, keep the winning (z, record id)
-//           in registers, then shade the winner once and store uint8 RGB.
+//           in registers, then shade the winner once and store uint8 RGB.  With textures a second instantiation runs,
+//           which multiplies the winner's diffuse colour by one bilinear fetch (4 x 32-bit RGBA8 loads) before shading.
 // The order inside a list is whatever the atomics made it; the winner is min z then max record id (GL LEQUAL in
 // submission order), a total order, so the image does not depend on it: two runs and the host twin agree bit for bit.
 //
@@ -118,11 +119,15 @@ __global__ __launch_bounds__(256) void rd_fill_kernel(const crnRenderImage* __re
     }
 }
 
-__global__ __launch_bounds__(RD_THREADS) void rd_raster_kernel(const float* __restrict__ tri, const float* __restrict__ nrm,
-                                                               const int32_t* __restrict__ mids, const float* __restrict__ mats,
-                                                               int M, const crnRenderImage* __restrict__ imgs, int H, int W,
-                                                               const float* __restrict__ recs, const int64_t* __restrict__ offs,
-                                                               const int32_t* __restrict__ list, uint8_t* __restrict__ out) {
+// One pixel per lane.  TEX only adds the fetch in front of rd_shade: the untextured instantiation is the kernel as it
+// was, and only the winning fragment of a pixel samples.
+template <bool TEX>
+__device__ __forceinline__ void rd_raster_pixel(const float* __restrict__ tri, const float* __restrict__ nrm,
+                                                const int32_t* __restrict__ mids, const float* __restrict__ mats, int M,
+                                                const crnRenderImage* __restrict__ imgs, int H, int W,
+                                                const float* __restrict__ recs, const int64_t* __restrict__ offs,
+                                                const int32_t* __restrict__ list, uint8_t* __restrict__ out,
+                                                const crnRdTex& tex) {
   const int i = blockIdx.y;
   const crnRenderImage& im = imgs[i];
   const int tx = (W + RD_T - 1) / RD_T, ntiles = tx * ((H + RD_T - 1) / RD_T);
@@ -164,9 +169,34 @@ __global__ __launch_bounds__(RD_THREADS) void rd_raster_kernel(const float* __re
   const bool has_mat = m >= 0 && m < M;
   if (has_mat)
     for (int q = 0; q < 10; ++q) mat[q] = mats[10 * (int64_t)m + q];
+  if constexpr (TEX) {
+    const int32_t layer = has_mat ? tex.ids[m] : -1;
+    if (layer >= 0 && layer < tex.L) {
+      float uv[6];
+      if (tex.uv)
+        for (int q = 0; q < 6; ++q) uv[q] = tex.uv[6 * t + q];
+      rd_tex_diffuse(E, tex.uv ? uv : nullptr, tex.texels, tex.Ht, tex.Wt, layer, mat);
+    }
+  }
   uint8_t rgb[3];
   rd_shade(im, p, n, has_mat ? mat : nullptr, E, rgb);
   o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
+}
+
+__global__ __launch_bounds__(RD_THREADS) void rd_raster_kernel(const float* __restrict__ tri, const float* __restrict__ nrm,
+                                                               const int32_t* __restrict__ mids, const float* __restrict__ mats,
+                                                               int M, const crnRenderImage* __restrict__ imgs, int H, int W,
+                                                               const float* __restrict__ recs, const int64_t* __restrict__ offs,
+                                                               const int32_t* __restrict__ list, uint8_t* __restrict__ out) {
+  rd_raster_pixel<false>(tri, nrm, mids, mats, M, imgs, H, W, recs, offs, list, out, crnRdTex{});
+}
+
+__global__ __launch_bounds__(RD_THREADS) void rd_raster_tex_kernel(
+    const float* __restrict__ tri, const float* __restrict__ nrm, const int32_t* __restrict__ mids,
+    const float* __restrict__ mats, int M, const crnRenderImage* __restrict__ imgs, int H, int W,
+    const float* __restrict__ recs, const int64_t* __restrict__ offs, const int32_t* __restrict__ list,
+    uint8_t* __restrict__ out, crnRdTex tex) {
+  rd_raster_pixel<true>(tri, nrm, mids, mats, M, imgs, H, W, recs, offs, list, out, tex);
 }
 
 // ---------------- voxel faces ----------------
@@ -325,8 +355,18 @@ extern "C" int crn_render_raster(const float* triangles, const float* normals, c
                                  const float* materials, int M, const crnRenderImage* images, int I, int H, int W,
                                  int max_len, const float* records, int32_t* bin_counts, const int64_t* bin_offsets,
                                  int32_t* bin_list, uint8_t* out, crnStream s) {
+  return crn_render_raster_tex(triangles, normals, material_ids, materials, M, images, I, H, W, max_len, records,
+                               bin_counts, bin_offsets, bin_list, out, nullptr, nullptr, nullptr, 0, 0, 0, s);
+}
+
+extern "C" int crn_render_raster_tex(const float* triangles, const float* normals, const int32_t* material_ids,
+                                     const float* materials, int M, const crnRenderImage* images, int I, int H, int W,
+                                     int max_len, const float* records, int32_t* bin_counts, const int64_t* bin_offsets,
+                                     int32_t* bin_list, uint8_t* out, const float* texcoords, const int32_t* texture_ids,
+                                     const uint8_t* textures, int L, int Ht, int Wt, crnStream s) {
   if (!rd_args_ok(images, I, H, W, max_len) || !bin_counts || !bin_offsets || !out || M < 0) return CRN_EINVAL;
   if (max_len > 0 && (!triangles || !material_ids || !records || !bin_list)) return CRN_EINVAL;
+  if (textures && (!rd_tex_dims_ok(L, Ht, Wt) || ((uintptr_t)textures & 3))) return CRN_EINVAL;
   hipStream_t st = (hipStream_t)s;
   const int ntiles = ((W + RD_T - 1) / RD_T) * ((H + RD_T - 1) / RD_T);
   if (max_len > 0) {
@@ -334,8 +374,14 @@ extern "C" int crn_render_raster(const float* triangles, const float* normals, c
                        records, bin_counts, bin_offsets, bin_list);
     CRN_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(rd_raster_kernel, dim3((unsigned)ntiles, (unsigned)I), dim3(RD_THREADS), 0, st, triangles, normals,
-                     material_ids, materials, M, images, H, W, records, bin_offsets, bin_list, out);
+  if (textures && texture_ids && M > 0) {
+    const crnRdTex tex = {texcoords, texture_ids, reinterpret_cast<const uint32_t*>(textures), L, Ht, Wt};
+    hipLaunchKernelGGL(rd_raster_tex_kernel, dim3((unsigned)ntiles, (unsigned)I), dim3(RD_THREADS), 0, st, triangles,
+                       normals, material_ids, materials, M, images, H, W, records, bin_offsets, bin_list, out, tex);
+  } else {
+    hipLaunchKernelGGL(rd_raster_kernel, dim3((unsigned)ntiles, (unsigned)I), dim3(RD_THREADS), 0, st, triangles, normals,
+                       material_ids, materials, M, images, H, W, records, bin_offsets, bin_list, out);
+  }
   CRN_CHECK_LAUNCH();
   return 0;
 }

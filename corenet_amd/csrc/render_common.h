@@ -178,6 +178,72 @@ CRN_RD_HD void rd_shade(const crnRenderImage& im, const float* p, const float* n
   }
 }
 
+// ---------------- diffuse textures (point_light_illumination.frag: diffuse * texture(textures, (s, t, layer))) --------
+// GL's rule for the array the reference binds: GL_LINEAR both ways, no mip-maps, GL_REPEAT, unsigned-normalised bytes.
+// One axis of n texels at coordinate s:  s' = s - floorf(s), and s' = 0 unless 0 <= s' < 1 (NaN, infinity, a rounding to
+// 1); u = s' * n - 0.5 in [-0.5, n - 0.5); i0 = floorf(u), weight a = u - i0 of i1 = i0 + 1; i0 = -1 wraps to n - 1 and
+// i1 = n to 0.  Both indices are in [0, n) for every s and every n >= 1 (the clamp below never acts for n <= 2^14; it
+// makes that independent of the rounding argument).
+CRN_RD_HD void rd_tex_axis(float s, int n, int& i0, int& i1, float& a) {
+  float f = s - floorf(s);
+  if (!(f >= 0.f && f < 1.f)) f = 0.f;
+  const float u = f * (float)n - 0.5f;
+  const float fl = floorf(u);
+  a = u - fl;
+  i0 = rd_clampi((int)fl, -1, n - 1);
+  i1 = i0 + 1;
+  if (i0 < 0) i0 = n - 1;
+  if (i1 >= n) i1 = 0;
+}
+
+// tex: RGBA8 texels as little-endian words [L][Ht][Wt] (R in the low byte, alpha ignored), row 0 is t = 0.  The caller
+// guarantees 0 <= layer < L.  A channel is byte / 255.f; the four texels are blended as two lerps along s and one along
+// t, each written x + w * (y - x):  top = c00 + a (c10 - c00), bot = c01 + a (c11 - c01), tau = top + b (bot - top)
+// (c_ij: column i_, row j_).  That is the bilinear blend with weights (1-a)(1-b), a(1-b), (1-a)b, ab, in an order that
+// returns equal texels unchanged: an all-255 texture gives tau == 1.0f exactly.
+CRN_RD_HD void rd_tex_fetch(const uint32_t* tex, int Ht, int Wt, int layer, float s, float t, float tau[3]) {
+  int i0, i1, j0, j1;
+  float a, b;
+  rd_tex_axis(s, Wt, i0, i1, a);
+  rd_tex_axis(t, Ht, j0, j1, b);
+  const uint32_t* r0 = tex + ((int64_t)layer * Ht + j0) * Wt;
+  const uint32_t* r1 = tex + ((int64_t)layer * Ht + j1) * Wt;
+  const uint32_t w00 = r0[i0], w10 = r0[i1], w01 = r1[i0], w11 = r1[i1];
+  for (int q = 0; q < 3; ++q) {
+    const float c00 = (float)((w00 >> (8 * q)) & 255u) / 255.f, c10 = (float)((w10 >> (8 * q)) & 255u) / 255.f;
+    const float c01 = (float)((w01 >> (8 * q)) & 255u) / 255.f, c11 = (float)((w11 >> (8 * q)) & 255u) / 255.f;
+    const float top = c00 + a * (c10 - c00), bot = c01 + a * (c11 - c01);
+    tau[q] = top + b * (bot - top);
+  }
+}
+
+// The texture arguments of a render call (contract: include/corenet_hip.h); texels == NULL: nothing is textured.
+struct crnRdTex {
+  const float* uv;          // [T][3][2] or NULL (all zero)
+  const int32_t* ids;       // [M]
+  const uint32_t* texels;   // RGBA8 words [L][Ht][Wt]
+  int L, Ht, Wt;
+};
+
+// L, Ht, Wt of a texture array the entry points accept (2^14 per side, like an image: n and s' * n are exact floats)
+CRN_RD_HD bool rd_tex_dims_ok(int L, int Ht, int Wt) {
+  return L >= 1 && Ht >= 1 && Wt >= 1 && L <= (1 << 14) && Ht <= (1 << 14) && Wt <= (1 << 14);
+}
+
+// The textured material of the winning fragment: (s, t) interpolated like position from the triangle's 6 texture
+// coordinates uv (NULL: all zero), then mat's diffuse colour (mat[3..5]) times tau.  The rest of rd_shade is unchanged.
+CRN_RD_HD void rd_tex_diffuse(const float E[3], const float* uv, const uint32_t* tex, int Ht, int Wt, int layer,
+                              float* mat) {
+  float st[2] = {0.f, 0.f};
+  if (uv) {
+    const float s = (E[0] + E[1]) + E[2];
+    for (int q = 0; q < 2; ++q) st[q] = ((E[0] * uv[q] + E[1] * uv[2 + q]) + E[2] * uv[4 + q]) / s;
+  }
+  float tau[3];
+  rd_tex_fetch(tex, Ht, Wt, layer, st[0], st[1], tau);
+  for (int q = 0; q < 3; ++q) mat[3 + q] = mat[3 + q] * tau[q];
+}
+
 // ---------------- voxel faces (voxel_renderer.geom) ----------------
 // A label is drawn iff it indexes the palette and its colour has no negative channel.
 CRN_RD_HD bool vx_drawn(int32_t l, const float* pal, int P) {

@@ -33,7 +33,7 @@ void for_tasks(int n, int num_threads, F fn) {
 }
 
 void render_image(const float* tri, const float* nrm, const int32_t* mids, const float* mats, int M,
-                  const crnRenderImage& im, int H, int W, uint8_t* out) {
+                  const crnRenderImage& im, int H, int W, uint8_t* out, const crnRdTex& tex) {
   const int64_t np = (int64_t)H * W;
   std::vector<float> bz(np, 0.f);
   std::vector<int32_t> bid(np, -1);
@@ -67,7 +67,15 @@ void render_image(const float* tri, const float* nrm, const int32_t* mids, const
       const int64_t t = (int64_t)im.t0 + k;
       const int32_t m = mids[t];
       const bool has_mat = m >= 0 && m < M;
-      rd_shade(im, tri + 9 * t, nrm ? nrm + 9 * t : nullptr, has_mat ? mats + 10 * (int64_t)m : nullptr, E, o);
+      const float* mat = has_mat ? mats + 10 * (int64_t)m : nullptr;
+      float tmat[10];
+      const int32_t layer = has_mat && tex.texels ? tex.ids[m] : -1;
+      if (layer >= 0 && layer < tex.L) {
+        for (int q = 0; q < 10; ++q) tmat[q] = mat[q];
+        rd_tex_diffuse(E, tex.uv ? tex.uv + 6 * t : nullptr, tex.texels, tex.Ht, tex.Wt, layer, tmat);
+        mat = tmat;
+      }
+      rd_shade(im, tri + 9 * t, nrm ? nrm + 9 * t : nullptr, mat, E, o);
     }
 }
 
@@ -76,14 +84,25 @@ void render_image(const float* tri, const float* nrm, const int32_t* mids, const
 extern "C" int crn_render_cpu(const float* triangles, const float* normals, const int32_t* material_ids,
                               const float* materials, int M, const crnRenderImage* images, int I, int H, int W,
                               uint8_t* out, int num_threads) {
+  return crn_render_cpu_tex(triangles, normals, material_ids, materials, M, images, I, H, W, out, nullptr, nullptr,
+                            nullptr, 0, 0, 0, num_threads);
+}
+
+extern "C" int crn_render_cpu_tex(const float* triangles, const float* normals, const int32_t* material_ids,
+                                  const float* materials, int M, const crnRenderImage* images, int I, int H, int W,
+                                  uint8_t* out, const float* texcoords, const int32_t* texture_ids,
+                                  const uint8_t* textures, int L, int Ht, int Wt, int num_threads) {
   if (!images || I < 1 || H < 1 || W < 1 || !out || M < 0) return CRN_EINVAL;
+  if (textures && (!rd_tex_dims_ok(L, Ht, Wt) || ((uintptr_t)textures & 3))) return CRN_EINVAL;
+  crnRdTex tex = {nullptr, nullptr, nullptr, 0, 0, 0};
+  if (textures && texture_ids) tex = {texcoords, texture_ids, reinterpret_cast<const uint32_t*>(textures), L, Ht, Wt};
   for (int i = 0; i < I; ++i) {
     if (images[i].t1 < images[i].t0) return CRN_EINVAL;
     if (images[i].t1 > images[i].t0 && (!triangles || !material_ids)) return CRN_EINVAL;
     if (images[i].normal_mode != 0 && images[i].t1 > images[i].t0 && !normals) return CRN_EINVAL;
   }
   for_tasks(I, num_threads, [&](int i) {
-    render_image(triangles, normals, material_ids, materials, M, images[i], H, W, out + (int64_t)i * H * W * 3);
+    render_image(triangles, normals, material_ids, materials, M, images[i], H, W, out + (int64_t)i * H * W * 3, tex);
   });
   return 0;
 }

@@ -18,12 +18,20 @@ Contract, GL's rules for one draw of triangles without MSAA:
     ambient_light diffuse + specular light_colour max(dot(R, V), 0)^shininess, clamped to [0, 1], rint(255 c).
     Uncovered pixels get the clear colour.
   * cam = inverse(VP) . (0, 0, -1, 1), dehomogenised, in float32 on the host; the light defaults to it.
-  * Textures are not supported.
+  * Diffuse textures (the fragment shader's `diffuse * texture(textures, (s, t, layer))` on a texture array with GL's
+    defaults: GL_LINEAR, no mip-maps, GL_REPEAT, unsigned-normalised bytes).  (s, t) is interpolated perspective-correct
+    like position.  Per axis of n texels: s' = s - floor(s) (0 if that is not in [0, 1): NaN, infinity); u = s' n - 0.5;
+    i0 = floor(u), i1 = i0 + 1 with weight a = u - i0, and -1 wraps to n - 1, n to 0.  A texel channel is byte / 255;
+    tau = lerp(lerp(c00, c10, a), lerp(c01, c11, a), b) with lerp(x, y, w) = x + w (y - x), so equal texels come back
+    unchanged and an all-255 texture is the untextured image bit for bit.  Texture row 0 is t = 0 (GL's first row, which
+    is why load_textures flips images).  Material m is textured iff 0 <= texture_indices[m] < L; its diffuse colour is
+    then diffuse * tau in the formula above.  Only the winning fragment of a pixel samples.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple, Optional, Sequence, Tuple
+import io
+from typing import Iterable, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch as t
@@ -72,10 +80,52 @@ def make_materials(diffuse, ambient=0.05, specular=(0.0, 0.0, 0.0), shininess=20
   return t.cat([a, d, s, sh[:, None]], 1).contiguous()
 
 
+class _Textures(NamedTuple):
+  coords: Optional[t.Tensor]   # f32 [T, 3, 2] on the render device, or None (all zero)
+  ids: t.Tensor                # int32 [M]
+  texels: t.Tensor             # uint8 [L, Ht, Wt, 4], RGBA8
+
+  def abi(self):
+    L, Ht, Wt = self.texels.shape[:3]
+    return (None if self.coords is None else self.coords.data_ptr(), self.ids.data_ptr(), self.texels.data_ptr(),
+            L, Ht, Wt)
+
+
+def _texture_args(tex_coords, textures, texture_indices, T: int, M: int, dev) -> Optional[_Textures]:
+  """Checks render_batch's texture arguments and brings them to the C ABI's layout on dev; None: nothing is textured."""
+  if tex_coords is not None:
+    tex_coords = t.as_tensor(tex_coords)
+    if tex_coords.dtype != t.float32 or tuple(tex_coords.shape) != (T, 3, 2):
+      raise ValueError(f"render: tex_coords must be float32 [{T}, 3, 2], got {tex_coords.dtype} "
+                       f"{tuple(tex_coords.shape)}")
+  if (textures is None) != (texture_indices is None):
+    raise ValueError("render: textures and texture_indices come together")
+  if textures is None:
+    return None
+  textures = t.as_tensor(textures)
+  if textures.dtype != t.uint8 or textures.dim() != 4 or textures.shape[3] != 3 or 0 in textures.shape:
+    raise ValueError(f"render: textures must be a non-empty uint8 [L, Ht, Wt, 3], got {textures.dtype} "
+                     f"{tuple(textures.shape)}")
+  if max(textures.shape[:3]) > 1 << 14:
+    raise ValueError("render: at most 2^14 texture layers, rows and columns")
+  ids = t.as_tensor(texture_indices).detach().cpu()
+  if ids.dtype not in (t.int8, t.int16, t.int32, t.int64, t.uint8) or tuple(ids.shape) != (M,):
+    raise ValueError(f"render: texture_indices must be an integer [{M}], got {ids.dtype} {tuple(ids.shape)}")
+  if M and int(ids.max()) >= textures.shape[0]:
+    raise ValueError(f"render: texture index {int(ids.max())} with {textures.shape[0]} texture layers")
+  if M == 0 or int(ids.max()) < 0:
+    return None
+  textures = textures.to(dev)
+  texels = t.cat([textures, t.full_like(textures[..., :1], 255)], -1).contiguous()      # RGBA8: one load per texel
+  return _Textures(None if tex_coords is None else tex_coords.to(dev).contiguous(), ids.to(dev, t.int32).contiguous(),
+                   texels)
+
+
 def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tensor, ranges, view_projections,
                  image_size: Tuple[int, int], normals: Optional[t.Tensor] = None, normal_modes=None,
                  light_positions=None, light_colors=(1.0, 1.0, 1.0), ambient_light_colors=(0.2, 0.2, 0.2),
-                 clear_colors=(0.0, 0.0, 0.0), cull_back_facing=False) -> t.Tensor:
+                 clear_colors=(0.0, 0.0, 0.0), cull_back_facing=False, *, tex_coords: Optional[t.Tensor] = None,
+                 textures: Optional[t.Tensor] = None, texture_indices=None) -> t.Tensor:
   """Renders I images of image_size = (H, W) in one call -> uint8 [I, H, W, 3] on the triangles' device.
 
   Image i draws triangles ranges[i] = [t0, t1) of the shared buffers: triangles f32 [T, 3, 3] (world space),
@@ -84,7 +134,11 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
   geometric normal normalize(cross(normalize(v1 - v0), normalize(v2 - v0))); default 1 with normals, 0 without.
   view_projections [I, 4, 4]; light_positions None (each image's camera) or [I, 3]; light_colors,
   ambient_light_colors, clear_colors [3] or [I, 3]; cull_back_facing a bool or [I] (culls when the signed NDC area is
-  <= 0).  On the GPU the call synchronises once: a read of the number of (tile, triangle) pairs."""
+  <= 0).  Diffuse textures (module docstring): textures uint8 [L, Ht, Wt, 3] (row 0 is t = 0) with texture_indices
+  int [M], the layer of each material or -1 for none, and tex_coords f32 [T, 3, 2] (None: all (0, 0)); textures and
+  texture_indices come together, tex_coords alone has no effect.  Wrong shapes or types and an index >= L raise
+  ValueError before anything is launched.  On the GPU the call synchronises once: a read of the number of
+  (tile, triangle) pairs."""
   H, W = (int(v) for v in image_size)
   dev = triangles.device
   triangles = t.as_tensor(triangles, dtype=t.float32).contiguous()
@@ -99,6 +153,7 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
     normals = t.as_tensor(normals, dtype=t.float32).to(dev).contiguous()
     if normals.shape != triangles.shape:
       raise ValueError("render: normals must have the triangles' shape")
+  tex = _texture_args(tex_coords, textures, texture_indices, T, materials.shape[0], dev)
   ranges = _host(ranges, t.int64).reshape(-1, 2)
   I = ranges.shape[0]
   if I < 1 or H < 1 or W < 1:
@@ -149,15 +204,26 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
     total = int(offsets[-1].item())                                     # the call's one synchronisation
     bins = t.empty(max(total, 1), dtype=t.int32, device=dev)
     out = t.empty((I, H, W, 3), dtype=t.uint8, device=dev)
-    lib.crn_render_raster(triangles.data_ptr(), None if normals is None else normals.data_ptr(), material_ids.data_ptr(),
-                          materials.data_ptr(), M, images.data_ptr(), I, H, W, max_len, records.data_ptr(),
-                          counts.data_ptr(), offsets.data_ptr(), bins.data_ptr(), out.data_ptr(), s)
+    if tex is None:
+      lib.crn_render_raster(triangles.data_ptr(), None if normals is None else normals.data_ptr(),
+                            material_ids.data_ptr(), materials.data_ptr(), M, images.data_ptr(), I, H, W, max_len,
+                            records.data_ptr(), counts.data_ptr(), offsets.data_ptr(), bins.data_ptr(), out.data_ptr(), s)
+    else:
+      lib.crn_render_raster_tex(triangles.data_ptr(), None if normals is None else normals.data_ptr(),
+                                material_ids.data_ptr(), materials.data_ptr(), M, images.data_ptr(), I, H, W, max_len,
+                                records.data_ptr(), counts.data_ptr(), offsets.data_ptr(), bins.data_ptr(),
+                                out.data_ptr(), *tex.abi(), s)
     return out
   if dev.type != "cpu":
     raise ValueError(f"render: unsupported device {dev}")
   out = t.empty((I, H, W, 3), dtype=t.uint8)
-  lib.crn_render_cpu(triangles.data_ptr(), None if normals is None else normals.data_ptr(), material_ids.data_ptr(),
-                     materials.data_ptr(), M, images.data_ptr(), I, H, W, out.data_ptr(), t.get_num_threads())
+  if tex is None:
+    lib.crn_render_cpu(triangles.data_ptr(), None if normals is None else normals.data_ptr(), material_ids.data_ptr(),
+                       materials.data_ptr(), M, images.data_ptr(), I, H, W, out.data_ptr(), t.get_num_threads())
+  else:
+    lib.crn_render_cpu_tex(triangles.data_ptr(), None if normals is None else normals.data_ptr(),
+                           material_ids.data_ptr(), materials.data_ptr(), M, images.data_ptr(), I, H, W, out.data_ptr(),
+                           *tex.abi(), t.get_num_threads())
   return out
 
 
@@ -248,12 +314,13 @@ def render_scene(vertex_positions, view_projection_matrix=None, image_size: Tupl
                  normals=None, material_ids=None, diffuse_coefficients=None, specular_coefficient=None,
                  ambient_coefficients=None, cull_back_facing=True, light_position=None, light_color=(1.0, 1.0, 1.0),
                  ambient_light_color=(0.2, 0.2, 0.2), clear_color=(0, 0, 0, 1), output_type=t.uint8,
-                 return_rgb=True) -> t.Tensor:
-  """Renders triangles f32 [T, 3, 3] (scene_renderer.render_scene without textures) -> uint8 [H, W, 3] on their
-  device.  normals f32 [T, 3, 3] per vertex (normalised) or None (the geometric normal); material_ids int32 [T]
+                 return_rgb=True, *, tex_coords=None, diffuse_textures=None, diffuse_texture_indices=None) -> t.Tensor:
+  """Renders triangles f32 [T, 3, 3] (scene_renderer.render_scene) -> uint8 [H, W, 3] on their device.  normals f32 [T, 3, 3] per vertex (normalised) or None (the geometric normal); material_ids int32 [T]
   (default all 0) into diffuse_coefficients [M, 3] (default 0.8), ambient_coefficients [M, 3] (default 0.05) and
   specular_coefficient [M, 4] (rgb + shininess, default (0, 0, 0, 2048)).  view_projection_matrix defaults to
-  camera_util.get_default_camera_for_mesh; light_position to the camera."""
+  camera_util.get_default_camera_for_mesh; light_position to the camera.  tex_coords f32 [T, 3, 2] (default all 0),
+  diffuse_textures uint8 [L, Ht, Wt, 3] and diffuse_texture_indices int [M] (default all -1) as in the reference: the
+  indices are cut to the used materials and the textures to max(index) + 1 layers."""
   v = t.as_tensor(vertex_positions, dtype=t.float32)
   if v.dim() != 3 or v.shape[1:] != (3, 3):
     raise ValueError(f"render_scene: vertex_positions must be [T, 3, 3], got {tuple(v.shape)}")
@@ -277,11 +344,118 @@ def render_scene(vertex_positions, view_projection_matrix=None, image_size: Tupl
   ambient = coeffs(ambient_coefficients, 3, 0.05)
   spec = coeffs(specular_coefficient, 4, (0.0, 0.0, 0.0, 2048.0))
   mats = make_materials(diffuse, ambient, spec[:, :3], spec[:, 3])
+  tex_ids = None
+  if diffuse_textures is not None:
+    tex_ids = t.full((used,), -1, dtype=t.int32) if diffuse_texture_indices is None else t.as_tensor(
+        diffuse_texture_indices).detach().cpu()
+    if tex_ids.dim() != 1 or tex_ids.shape[0] < used:
+      raise ValueError(f"render_scene: diffuse_texture_indices must be [>= {used}], got {tuple(tex_ids.shape)}")
+    tex_ids = tex_ids[:used]
+    num_tex = max(int(tex_ids.max()) + 1, 1)
+    diffuse_textures = t.as_tensor(diffuse_textures)
+    if diffuse_textures.dim() != 4 or diffuse_textures.shape[0] < num_tex or diffuse_textures.shape[3] != 3:
+      raise ValueError(f"render_scene: diffuse_textures must be [>= {num_tex}, Ht, Wt, 3], got "
+                       f"{tuple(diffuse_textures.shape)}")
+    diffuse_textures = diffuse_textures[:num_tex]
+  elif diffuse_texture_indices is not None and int(t.as_tensor(diffuse_texture_indices)[:used].max()) >= 0:
+    raise ValueError("render_scene: diffuse_texture_indices name a texture, but diffuse_textures is None")
+  if tex_coords is not None:
+    tex_coords = t.as_tensor(tex_coords, dtype=t.float32)
   img = render_batch(v, material_ids, mats.to(dev), [[0, T]], vp[None], image_size, normals=normals,
                      light_positions=None if light_position is None else _host(light_position)[None],
                      light_colors=light_color, ambient_light_colors=ambient_light_color,
-                     clear_colors=_host(clear_color)[:3], cull_back_facing=bool(cull_back_facing))[0]
+                     clear_colors=_host(clear_color)[:3], cull_back_facing=bool(cull_back_facing),
+                     tex_coords=tex_coords, textures=diffuse_textures, texture_indices=tex_ids)[0]
   return _finish(img, output_type, return_rgb)
+
+
+def load_textures(encoded_images: Iterable[bytes], texture_size: Tuple[int, int]) -> Tuple[t.Tensor, t.Tensor]:
+  """A texture array from encoded images (scene_renderer.load_textures) -> (uint8 [N, H, W, 3], int32 [num_images]).
+
+  Every distinct non-empty entry of encoded_images (PNG, JPEG, ... bytes) is decoded once, converted to RGB, resized
+  bicubically to texture_size = (H, W) and flipped along its rows, so that the image's bottom row is texture row 0
+  (t = 0).  The second result maps entry j to its layer; an empty entry maps to -1.  With nothing to decode the array
+  is zeros [1, 1, 1, 3]."""
+  import PIL.Image
+  height, width = (int(v) for v in texture_size)
+  layer_of = {}
+  layers, indices = [], []
+  for enc in encoded_images:
+    enc = bytes(enc)
+    if not enc:
+      indices.append(-1)
+      continue
+    if enc not in layer_of:
+      layer_of[enc] = len(layers)
+      with PIL.Image.open(io.BytesIO(enc)) as im:
+        rgb = np.asarray(im.convert("RGB").resize((width, height), resample=PIL.Image.BICUBIC))
+      layers.append(np.ascontiguousarray(rgb[::-1]))
+    indices.append(layer_of[enc])
+  array = t.from_numpy(np.stack(layers)) if layers else t.zeros((1, 1, 1, 3), dtype=t.uint8)
+  return array, t.tensor(indices, dtype=t.int32)
+
+
+def render_scenes(scenes, view_projections=None, image_size: Tuple[int, int] = (256, 256),
+                  texture_size: Tuple[int, int] = (128, 128), device="cuda", shading_normals=True,
+                  **light_and_clear_kwargs) -> t.Tensor:
+  """Draws N data.scene.Scene objects, loaded with load_extra_fields=True, with their own materials and textures in
+  one render_batch call -> uint8 [N, H, W, 3] on device.
+
+  Every mesh goes through its o2w_transforms row (world space); with shading_normals its normals go through the
+  inverse transpose of that row's 3 x 3 part, else the geometric normal is shaded.  All meshes share one material
+  table (material_ids offset per mesh; diffuse from diffuse_colors, ambient and specular render_scene's defaults) and
+  one texture array, load_textures over every mesh's diffuse_texture_pngs at texture_size.  Scene n is one triangle
+  range; view_projections f32 [N, 4, 4] defaults to each scene's camera_transform @ view_transform.
+  light_and_clear_kwargs: render_batch's light_positions, light_colors, ambient_light_colors, clear_colors,
+  cull_back_facing."""
+  extra = set(light_and_clear_kwargs) - {"light_positions", "light_colors", "ambient_light_colors", "clear_colors",
+                                         "cull_back_facing"}
+  if extra:
+    raise TypeError(f"render_scenes: unexpected arguments {sorted(extra)}")
+  scenes = list(scenes)
+  if not scenes:
+    raise ValueError("render_scenes: need at least one scene")
+  tris, nrms, uvs, mids, diffuse, pngs, ranges = [], [], [], [], [], [], []
+  num_tri = num_mat = 0
+  for n, sc in enumerate(scenes):
+    K = len(sc.mesh_vertices)
+    fields = (sc.texcoords, sc.material_ids, sc.diffuse_colors, sc.diffuse_texture_pngs) + (
+        (sc.normals,) if shading_normals else ())
+    if any(len(f) != K for f in fields):
+      raise ValueError(f"render_scenes: scene {n} lacks its per-mesh extra fields; load it with "
+                       "load_from_npz(..., load_extra_fields=True)")
+    t0 = num_tri
+    for k in range(K):
+      v = _host(sc.mesh_vertices[k]).reshape(-1, 3, 3)
+      o2w = _host(sc.o2w_transforms[k])
+      colors = _host(sc.diffuse_colors[k]).reshape(-1, 3)
+      mesh_pngs = [bytes(p) for p in sc.diffuse_texture_pngs[k]]
+      uv = _host(sc.texcoords[k])
+      ids = _host(sc.material_ids[k], t.int64).reshape(-1)
+      if len(mesh_pngs) != colors.shape[0] or tuple(uv.shape) != (v.shape[0], 3, 2) or ids.shape[0] != v.shape[0]:
+        raise ValueError(f"render_scenes: scene {n}, mesh {k}: texcoords must be [T, 3, 2], material_ids [T], and "
+                         "diffuse_texture_pngs needs one entry per row of diffuse_colors")
+      tris.append(transformations.transform_mesh(v, o2w))
+      if shading_normals:
+        nm = _host(sc.normals[k]).reshape(-1, 3, 3)
+        if nm.shape != v.shape:
+          raise ValueError(f"render_scenes: scene {n}, mesh {k}: normals must have the vertices' shape")
+        nrms.append(t.matmul(nm, t.inverse(o2w[:3, :3])))                 # rows times inverse == inverse transpose
+      uvs.append(uv)
+      mids.append(ids + num_mat)
+      diffuse.append(colors)
+      pngs += mesh_pngs
+      num_mat += colors.shape[0]
+      num_tri += v.shape[0]
+    ranges.append([t0, num_tri])
+  if view_projections is None:
+    view_projections = t.stack([t.matmul(_host(sc.camera_transform), _host(sc.view_transform)) for sc in scenes])
+  textures, tex_ids = load_textures(pngs, texture_size)
+  dev = t.device(device)
+  return render_batch(t.cat(tris).to(dev), t.cat(mids).to(t.int32).to(dev), make_materials(t.cat(diffuse)).to(dev),
+                      ranges, view_projections, image_size, normals=t.cat(nrms).to(dev) if shading_normals else None,
+                      tex_coords=t.cat(uvs).to(dev), textures=textures.to(dev), texture_indices=tex_ids,
+                      **light_and_clear_kwargs)
 
 
 def voxel_materials(palette) -> t.Tensor:

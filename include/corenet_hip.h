@@ -732,6 +732,21 @@ int crn_render_raster(const float* triangles, const float* normals, const int32_
 /* Host twin (HOST memory): same contract, one image per task. */
 int crn_render_cpu(const float* triangles, const float* normals, const int32_t* material_ids, const float* materials,
                    int M, const crnRenderImage* images, int I, int H, int W, uint8_t* out, int num_threads);
+/* Diffuse textures: crn_render_raster / crn_render_cpu plus texcoords f32 [T][3][2] (NULL: all zero), texture_ids int32
+ * [M] (NULL: no material is textured) and textures uint8 [L][Ht][Wt][4] (RGBA8, 4-byte aligned, alpha ignored, row 0 is
+ * t = 0; NULL: none).  Material m is textured iff 0 <= texture_ids[m] < L; its diffuse colour is then multiplied by the
+ * bilinear, repeat-wrapped fetch at the perspective-correct (s, t) of the pixel (the rule: csrc/render_common.h, DESIGN
+ * section 14); only the winning fragment of a pixel samples.  With textures given, L, Ht, Wt must be in [1, 2^14]
+ * (CRN_EINVAL otherwise); without textures or texture_ids the calls are crn_render_raster / crn_render_cpu.          */
+int crn_render_raster_tex(const float* triangles, const float* normals, const int32_t* material_ids,
+                          const float* materials, int M, const crnRenderImage* images, int I, int H, int W, int max_len,
+                          const float* records, int32_t* bin_counts, const int64_t* bin_offsets, int32_t* bin_list,
+                          uint8_t* out, const float* texcoords, const int32_t* texture_ids, const uint8_t* textures,
+                          int L, int Ht, int Wt, crnStream s);
+int crn_render_cpu_tex(const float* triangles, const float* normals, const int32_t* material_ids, const float* materials,
+                       int M, const crnRenderImage* images, int I, int H, int W, uint8_t* out,
+                       const float* texcoords, const int32_t* texture_ids, const uint8_t* textures, int L, int Ht, int Wt,
+                       int num_threads);
 /* Exposed faces of N label grids labels[n][d][h][w] (int32, contiguous) as the voxel renderer draws them: voxel
  * (x, y, z) = (w, h, d) is a unit cube iff palette[label] (f32 [P][3]) exists and has no negative channel; of its faces
  * +x, -x, +y, -y, +z, -z only those whose neighbour is not drawn (or outside) are emitted, each as two triangles.
