@@ -599,6 +599,16 @@ class HipBackend:
     self.lib.crn_nearest(ptr(a), ptr(a_offsets), ptr(b), ptr(b_offsets), N, Na, int(max_na), int(max_nb), ptr(ws), n,
                          ptr(dist2), ptr(index), _lib.stream())
 
+  def point_triangle(self, p: t.Tensor, p_offsets: t.Tensor, triangles: t.Tensor, t_offsets: t.Tensor, max_np: int,
+                     max_nt: int, dist2: t.Tensor, index: t.Tensor):
+    """dist2 [Np], index [Np] <- per query of p the nearest eligible triangle of the same object of the soup; offsets:
+    device int64 [N + 1], max_np / max_nt: the largest object's queries / triangles (host ints)."""
+    N, Np, T = p_offsets.numel() - 1, p.shape[0], triangles.shape[0]
+    n = self.lib.crn_point_triangle_workspace_bytes(Np, T)
+    ws = self.workspace("pm_point_triangle", n, p.device)
+    self.lib.crn_point_triangle(ptr(p), ptr(p_offsets), ptr(triangles), ptr(t_offsets), N, Np, T, int(max_np), int(max_nt),
+                                ptr(ws), n, ptr(dist2), ptr(index), _lib.stream())
+
   def voxelize_mesh(self, tri, tri_mesh, view2voxel, M, D, H, W, sub_side, mult, conservative,
                     depth_mult, grid):
     self.lib.crn_voxelize_mesh(ptr(tri), ptr(tri_mesh), tri.shape[0], ptr(view2voxel), M, D, H, W,

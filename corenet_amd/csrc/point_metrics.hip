@@ -16,6 +16,11 @@
 //   When objects x query tiles cannot fill the chip the candidate range is cut into `splits` shares; every share merges
 //   its (d2, index) with a 64-bit atomicMin on (bits(d2) << 32) | index (d2 >= 0, so the bits order like the value; the
 //   minimum commutes, so the result does not depend on which workgroup finishes first).
+// point_triangle, two launches (four when the triangles of an object are split):
+//   records  one thread per triangle: pm_tri_record -> 20 floats in the workspace (NaNs for a triangle that is not eligible)
+//   pt       nn_kernel's layout with triangle records in place of points: 1024 queries of one object in registers, tiles
+//            of 256 records in LDS (20 KiB), five broadcast ds_read_b128 per record, then pm_tri_d2 for each of the lane's
+//            four queries: selects only, no bounds test (NaN padding), strict < in ascending order.  Split and merge as above.
 #include "crn_common.h"
 #include "point_metrics_common.h"
 
@@ -190,6 +195,121 @@ __global__ __launch_bounds__(NN_THREADS) void nn_kernel(const float* __restrict_
   }
 }
 
+// ---------------- point to triangle ----------------
+constexpr int PT_THREADS = 256;
+constexpr int PT_QPT = 4;                              // queries per lane
+constexpr int PT_QTILE = PT_THREADS * PT_QPT;          // queries per workgroup
+constexpr int PT_TB = 256;                             // triangle records per LDS tile (256 x 80 B = 20 KiB)
+constexpr int PT_REC4 = PM_TRI_REC / 4;                // 16-byte reads per record
+static_assert(PM_TRI_REC % 4 == 0 && (PT_TB * PT_REC4) % PT_THREADS == 0, "a tile is whole float4 rounds of the workgroup");
+static_assert(CRN_PT_QUERY_TILE == PT_QTILE && CRN_PT_TRIANGLE_TILE == PT_TB, "the header states the tiles");
+
+// one thread per triangle of the whole soup: its record, or NaNs when it is not eligible
+__global__ __launch_bounds__(256) void pt_records_kernel(const float* __restrict__ tri, int64_t T, float* __restrict__ rec) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= T) return;
+  float r[PM_TRI_REC];
+  pm_tri_record(tri + 9 * k, r);
+  f32x4* out = reinterpret_cast<f32x4*>(rec + PM_TRI_REC * k);
+#pragma unroll
+  for (int i = 0; i < PT_REC4; ++i) out[i] = f32x4{r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]};
+}
+
+// grid (query tiles, splits, objects of this launch), as nn_kernel.  rec: the records of the whole soup.
+template <bool SPLIT>
+__global__ __launch_bounds__(PT_THREADS) void pt_kernel(const float* __restrict__ p, const int64_t* __restrict__ p_off,
+                                                        const float* __restrict__ rec, const int64_t* __restrict__ t_off, int n0,
+                                                        float* __restrict__ dist2, int32_t* __restrict__ index,
+                                                        unsigned long long* __restrict__ keys) {
+  __shared__ f32x4 sr[PT_TB * PT_REC4];
+  const int n = n0 + blockIdx.z, tid = threadIdx.x;
+  const int64_t p0 = p_off[n], np = p_off[n + 1] - p0;
+  const int64_t q0 = (int64_t)blockIdx.x * PT_QTILE;
+  if (q0 >= np) return;                                                   // uniform
+  const int64_t t0 = t_off[n], nt = t_off[n + 1] - t0;
+  const int64_t tiles = (nt + PT_TB - 1) / PT_TB;
+  const int64_t per = ((tiles + gridDim.y - 1) / gridDim.y) * PT_TB;      // triangles per share, whole tiles
+  const int64_t c_begin = (int64_t)blockIdx.y * per;
+  const int64_t c_end = c_begin + per < nt ? c_begin + per : nt;
+  if (SPLIT && c_begin >= c_end) return;                                  // uniform; the keys are initialised
+
+  float ax[PT_QPT], ay[PT_QPT], az[PT_QPT], best[PT_QPT];
+  int32_t bi[PT_QPT];
+#pragma unroll
+  for (int k = 0; k < PT_QPT; ++k) {
+    const int64_t q = q0 + k * PT_THREADS + tid;
+    const bool in = q < np;
+    ax[k] = in ? p[3 * (p0 + q)] : NAN;                                   // a query past the end never finds anything
+    ay[k] = in ? p[3 * (p0 + q) + 1] : NAN;
+    az[k] = in ? p[3 * (p0 + q) + 2] : NAN;
+    best[k] = INFINITY;
+    bi[k] = -1;
+  }
+  const f32x4* ro = reinterpret_cast<const f32x4*>(rec + PM_TRI_REC * t0);
+  const f32x4 nan4 = {NAN, NAN, NAN, NAN};
+  for (int64_t c0 = c_begin; c0 < c_end; c0 += PT_TB) {
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < PT_TB * PT_REC4 / PT_THREADS; ++r) {              // the tile's records, coalesced 16-byte reads
+      const int f = r * PT_THREADS + tid;
+      sr[f] = c0 + f / PT_REC4 < c_end ? ro[c0 * PT_REC4 + f] : nan4;     // NaN padding: never chosen, no bounds test below
+    }
+    __syncthreads();
+    const int32_t cbase = (int32_t)c0;
+#pragma unroll 2
+    for (int j = 0; j < PT_TB; ++j) {
+      float r[PM_TRI_REC];
+#pragma unroll
+      for (int i = 0; i < PT_REC4; ++i) {                                 // every lane reads the same address: a broadcast
+        const f32x4 v = sr[j * PT_REC4 + i];
+        r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+      }
+#pragma unroll
+      for (int k = 0; k < PT_QPT; ++k) {
+        const float d2 = pm_tri_d2(ax[k], ay[k], az[k], r);
+        const bool less = d2 < best[k];                                   // strict, ascending j: ties keep the lowest index
+        best[k] = less ? d2 : best[k];
+        bi[k] = less ? cbase + j : bi[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < PT_QPT; ++k) {
+    const int64_t q = q0 + k * PT_THREADS + tid;
+    if (q >= np) continue;
+    if (SPLIT) {
+      atomicMin(&keys[p0 + q], ((unsigned long long)__float_as_uint(best[k]) << 32) | (unsigned)bi[k]);
+    } else {
+      dist2[p0 + q] = best[k];
+      index[p0 + q] = bi[k];
+    }
+  }
+}
+
+struct PtLayout {
+  size_t o_rec, o_keys, bytes;
+};
+
+PtLayout pt_layout(int64_t Np, int64_t T) {
+  PtLayout L;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  L.o_rec = 0;                                           // float [T][PM_TRI_REC]
+  L.o_keys = al((size_t)T * PM_TRI_REC * 4);             // uint64 [Np]
+  L.bytes = al(L.o_keys + (size_t)Np * 8);
+  return L;
+}
+
+// shares the triangles of an object are cut into: enough for NN_TARGET_WGS workgroups, at most one per tile
+int64_t pt_splits(int N, int64_t max_np, int64_t max_nt) {
+  const int64_t qtiles = (max_np + PT_QTILE - 1) / PT_QTILE;
+  const int64_t ctiles = (max_nt + PT_TB - 1) / PT_TB;
+  if (N < 1 || qtiles < 1) return 1;
+  int64_t splits = (NN_TARGET_WGS + N * qtiles - 1) / (N * qtiles);
+  if (splits > ctiles) splits = ctiles;
+  if (splits > 65535) splits = 65535;
+  return splits < 1 ? 1 : splits;
+}
+
 struct PmLayout {
   size_t o_cum, o_total, bytes;
 };
@@ -265,6 +385,62 @@ extern "C" int crn_nearest(const float* a, const int64_t* a_offsets, const float
   }
   if (splits > 1) {
     hipLaunchKernelGGL(nn_keys_final_kernel, dim3(kb), dim3(256), 0, st, (const unsigned long long*)keys, Na, dist2, index);
+    CRN_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+extern "C" size_t crn_point_triangle_workspace_bytes(int64_t Np, int64_t T) {
+  if (Np < 0 || T < 0) return 0;
+  return pt_layout(Np, T).bytes;
+}
+
+extern "C" size_t crn_point_triangle_tile(int which) { return which == 0 ? PT_QTILE : which == 1 ? PT_TB : 0; }
+
+extern "C" size_t crn_point_triangle_splits(int N, int64_t max_np, int64_t max_nt) {
+  if (N < 1 || max_np < 0 || max_nt < 0) return 0;
+  return (size_t)pt_splits(N, max_np, max_nt);
+}
+
+extern "C" int crn_point_triangle(const float* p, const int64_t* p_offsets, const float* triangles, const int64_t* t_offsets,
+                                  int N, int64_t Np, int64_t T, int64_t max_np, int64_t max_nt, void* workspace,
+                                  size_t workspace_bytes, float* dist2, int32_t* index, crnStream s) {
+  if (N < 1 || Np < 0 || T < 0 || max_np < 0 || max_np > Np || max_nt < 0 || max_nt > T || max_nt > CRN_PM_MAX_CANDIDATES ||
+      !p_offsets || !t_offsets)
+    return CRN_EINVAL;
+  if (Np == 0 || max_np == 0) return 0;
+  if (!p || !dist2 || !index || (T > 0 && !triangles)) return CRN_EINVAL;
+  const PtLayout L = pt_layout(Np, T);
+  if (!workspace || workspace_bytes < L.bytes) return CRN_EINVAL;
+  const int64_t qtiles = (max_np + PT_QTILE - 1) / PT_QTILE;
+  const int64_t splits = pt_splits(N, max_np, max_nt);
+  const int64_t rb = (T + 255) / 256, kb64 = (Np + 255) / 256;
+  if (qtiles >= ((int64_t)1 << 31) || rb >= ((int64_t)1 << 31) || kb64 >= ((int64_t)1 << 31)) return CRN_EINVAL;
+  hipStream_t st = (hipStream_t)s;
+  float* rec = (float*)((char*)workspace + L.o_rec);
+  unsigned long long* keys = (unsigned long long*)((char*)workspace + L.o_keys);
+  const unsigned kb = (unsigned)kb64;
+  if (T > 0) {
+    hipLaunchKernelGGL(pt_records_kernel, dim3((unsigned)rb), dim3(256), 0, st, triangles, T, rec);
+    CRN_CHECK_LAUNCH();
+  }
+  if (splits > 1) {
+    hipLaunchKernelGGL(nn_keys_init_kernel, dim3(kb), dim3(256), 0, st, keys, Np);
+    CRN_CHECK_LAUNCH();
+  }
+  for (int n0 = 0; n0 < N; n0 += 65535) {
+    const unsigned nz = (unsigned)(N - n0 < 65535 ? N - n0 : 65535);
+    const dim3 grid((unsigned)qtiles, (unsigned)splits, nz);
+    if (splits > 1)
+      hipLaunchKernelGGL(pt_kernel<true>, grid, dim3(PT_THREADS), 0, st, p, p_offsets, (const float*)rec, t_offsets, n0, dist2,
+                         index, keys);
+    else
+      hipLaunchKernelGGL(pt_kernel<false>, grid, dim3(PT_THREADS), 0, st, p, p_offsets, (const float*)rec, t_offsets, n0, dist2,
+                         index, keys);
+    CRN_CHECK_LAUNCH();
+  }
+  if (splits > 1) {
+    hipLaunchKernelGGL(nn_keys_final_kernel, dim3(kb), dim3(256), 0, st, (const unsigned long long*)keys, Np, dist2, index);
     CRN_CHECK_LAUNCH();
   }
   return 0;

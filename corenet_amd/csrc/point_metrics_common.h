@@ -95,3 +95,83 @@ CRN_PM_HD float pm_d2(float ax, float ay, float az, float bx, float by, float bz
   const float dx = ax - bx, dy = ay - by, dz = az - bz;
   return (dx * dx + dy * dy) + dz * dz;
 }
+
+// ---------------- point to triangle ----------------
+// A triangle is reduced once to a record of PM_TRI_REC floats: an orthonormal frame at A (u along AB, v in the plane
+// towards C, n = u x v) and the triangle in that frame, A = (0, 0), B = (l1, 0), C = l2 * (c2x, c2y), with the unit
+// direction and the length of every edge:
+//   [0..2] A   [3..5] u   [6..8] v   [9..11] n   [12] l1 = |AB|
+//   [13] c2x [14] c2y [15] l2 = |AC|       (unit direction of A -> C in the frame; c2y > 0)
+//   [16] c3x [17] c3y [18] l3 = |BC|       (unit direction of B -> C)         [19] 0
+// v is made orthogonal to u twice (Gram-Schmidt, then once more on the normalised vector) and n is their cross product,
+// so the frame is orthonormal to rounding however thin the triangle is; what a sliver loses is the direction of v about
+// its long axis, which moves no point of it by more than rounding.  A triangle that is not eligible
+// (pm_area_ok(pm_area) fails), or whose frame is not finite, gives a record of NaNs: every distance to it is NaN or +inf
+// and it is never chosen.
+#define PM_TRI_REC 20
+CRN_PM_HD void pm_tri_record(const float* p, float* r) {
+  const float e1x = p[3] - p[0], e1y = p[4] - p[1], e1z = p[5] - p[2];
+  const float e2x = p[6] - p[0], e2y = p[7] - p[1], e2z = p[8] - p[2];
+  const float l1 = sqrtf((e1x * e1x + e1y * e1y) + e1z * e1z);
+  const float ux = e1x / l1, uy = e1y / l1, uz = e1z / l1;
+  const float k = (e2x * ux + e2y * uy) + e2z * uz;
+  float wx = e2x - k * ux, wy = e2y - k * uy, wz = e2z - k * uz;
+  float lw = sqrtf((wx * wx + wy * wy) + wz * wz);
+  wx = wx / lw; wy = wy / lw; wz = wz / lw;
+  const float k2 = (wx * ux + wy * uy) + wz * uz;                  // what the first pass left of u in w: rounding / sin
+  wx = wx - k2 * ux; wy = wy - k2 * uy; wz = wz - k2 * uz;
+  lw = sqrtf((wx * wx + wy * wy) + wz * wz);
+  const float vx = wx / lw, vy = wy / lw, vz = wz / lw;
+  const float nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+  const float cx = (e2x * ux + e2y * uy) + e2z * uz, cy = (e2x * vx + e2y * vy) + e2z * vz;
+  const float l2 = sqrtf(cx * cx + cy * cy);
+  const float bx = cx - l1;
+  const float l3 = sqrtf(bx * bx + cy * cy);
+  r[0] = p[0]; r[1] = p[1]; r[2] = p[2];
+  r[3] = ux; r[4] = uy; r[5] = uz;
+  r[6] = vx; r[7] = vy; r[8] = vz;
+  r[9] = nx; r[10] = ny; r[11] = nz;
+  r[12] = l1;
+  r[13] = cx / l2; r[14] = cy / l2; r[15] = l2;
+  r[16] = bx / l3; r[17] = cy / l3; r[18] = l3;
+  r[19] = 0.f;
+  float sum = 0.f;                                                 // finite exactly when every term is finite
+  for (int i = 0; i < PM_TRI_REC; ++i) sum += r[i] * 0.f;
+  const bool ok = pm_area_ok(pm_area(p)) && sum == 0.f;
+  for (int i = 0; i < PM_TRI_REC; ++i) r[i] = ok ? r[i] : NAN;
+}
+
+// squared distance of one edge in the frame: (tx, ty) the query relative to the edge's start, (cx, cy) the edge's unit
+// direction, l its length.  s is the signed distance to the edge's line (positive on its left), a what the projection
+// lies outside [0, l] by.
+CRN_PM_HD float pm_edge_d2(float tx, float ty, float cx, float cy, float l, float* s) {
+  const float along = tx * cx + ty * cy;
+  *s = cx * ty - cy * tx;
+  float c = along < 0.f ? 0.f : along;
+  c = c > l ? l : c;
+  const float a = along - c;
+  return *s * *s + a * a;
+}
+
+// Squared distance from (px, py, pz) to the closed triangle of record r: the query in the frame is (x, y, z); the
+// distance is z * z plus the squared distance of (x, y) to the triangle in its plane, which is 0 inside (on the left
+// of A -> B and B -> C and on the right of A -> C) and the smallest of the three clamped edge distances elsewhere.
+// Selects only.  A NaN in the query or the record makes z, and with it the result, NaN.
+CRN_PM_HD float pm_tri_d2(float px, float py, float pz, const float* r) {
+  const float dx = px - r[0], dy = py - r[1], dz = pz - r[2];
+  const float x = (dx * r[3] + dy * r[4]) + dz * r[5];
+  const float y = (dx * r[6] + dy * r[7]) + dz * r[8];
+  const float z = (dx * r[9] + dy * r[10]) + dz * r[11];
+  float c = x < 0.f ? 0.f : x;
+  c = c > r[12] ? r[12] : c;
+  const float a1 = x - c;
+  const float q1 = y * y + a1 * a1;
+  float s2, s3;
+  const float q2 = pm_edge_d2(x, y, r[13], r[14], r[15], &s2);
+  const float q3 = pm_edge_d2(x - r[12], y, r[16], r[17], r[18], &s3);
+  float m = q2 < q1 ? q2 : q1;
+  m = q3 < m ? q3 : m;
+  const bool inside = (y >= 0.f) & (s2 <= 0.f) & (s3 >= 0.f);
+  const float in_plane = inside ? 0.f : m;
+  return z * z + in_plane;
+}

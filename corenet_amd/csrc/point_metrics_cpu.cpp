@@ -1,4 +1,4 @@
-// Surface sampling and nearest-neighbour distances on the host: the twin of point_metrics.hip, part of the product
+// Surface sampling, nearest-neighbour and point-to-triangle distances on the host: the twin of point_metrics.hip, part of the product
 // library.  Same contract, same per-element arithmetic (point_metrics_common.h): the GPU and this twin return identical
 // arrays.  One object per task (std::thread workers pulling object ids), as in marching_cubes_cpu.cpp.
 #include <atomic>
@@ -69,7 +69,37 @@ void nearest_object(const float* a, int64_t na, const float* b, int64_t nb, floa
   }
 }
 
+void point_triangle_object(const float* p, int64_t np, const float* tri, int64_t nt, float* dist2, int32_t* index) {
+  std::vector<float> rec((size_t)nt * PM_TRI_REC);
+  for (int64_t j = 0; j < nt; ++j) pm_tri_record(tri + 9 * j, rec.data() + PM_TRI_REC * j);
+  for (int64_t q = 0; q < np; ++q) {
+    const float px = p[3 * q], py = p[3 * q + 1], pz = p[3 * q + 2];
+    float best = INFINITY;
+    int32_t bi = -1;
+    for (int64_t j = 0; j < nt; ++j) {
+      const float d2 = pm_tri_d2(px, py, pz, rec.data() + PM_TRI_REC * j);
+      if (d2 < best) { best = d2; bi = (int32_t)j; }                             // strict, ascending: ties to the lowest index
+    }
+    dist2[q] = best;
+    index[q] = bi;
+  }
+}
+
 }  // namespace
+
+extern "C" int crn_point_triangle_cpu(const float* p, const int64_t* p_offsets, const float* triangles, const int64_t* t_offsets,
+                                      int N, float* dist2, int32_t* index, int num_threads) {
+  if (N < 1 || !offsets_ok(p_offsets, N) || !offsets_ok(t_offsets, N)) return CRN_EINVAL;
+  if (p_offsets[N] > 0 && (!p || !dist2 || !index)) return CRN_EINVAL;
+  if (t_offsets[N] > 0 && !triangles) return CRN_EINVAL;
+  for (int n = 0; n < N; ++n)
+    if (t_offsets[n + 1] - t_offsets[n] > CRN_PM_MAX_CANDIDATES) return CRN_EINVAL;
+  for_objects(N, num_threads, [&](int n) {
+    const int64_t p0 = p_offsets[n], t0 = t_offsets[n];
+    point_triangle_object(p + 3 * p0, p_offsets[n + 1] - p0, triangles + 9 * t0, t_offsets[n + 1] - t0, dist2 + p0, index + p0);
+  });
+  return 0;
+}
 
 extern "C" int crn_sample_surface_cpu(const float* triangles, const int64_t* tri_offsets, int N, int64_t S, uint32_t seed,
                                       float* points, int32_t* tri_index, uint8_t* valid, int num_threads) {

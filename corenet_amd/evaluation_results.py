@@ -10,7 +10,9 @@ both give identical images.  TensorBoard output is out of scope (DESIGN section 
 
 Quantitative surface results (no counterpart in the reference, which reports voxel IoU only): surface_metrics_for_batch
 measures the same marching-cubes surfaces against the ground truth with Chamfer distance and F-score
-(corenet_amd.mesh_metrics) and SurfaceResults accumulates them over an evaluation run.
+(corenet_amd.mesh_metrics) and SurfaceResults accumulates them over an evaluation run.  With
+distance="triangles" the distances run from the samples of one surface to the triangles of the other and normal
+consistency is reported beside them.
 
 Quantitative voxel results (evaluation_results.py:185-279): QuantitativeResults accumulates the confusion matrix over the
 dataset's classes on the device (`crn_eval_labels`: from a pmf, or streamed pass by pass at the resolution of the ground
@@ -202,6 +204,7 @@ class SurfaceRows(NamedTuple):
   scene_id: List[str]                      # [R]
   thresholds: Tuple[float, ...]            # [K]
   metrics: mesh_metrics.SurfaceMetrics     # [R] / [R, K] on pmf's device; NaN rows: class absent on both sides
+                                           # (a mesh_metrics.MeshSurfaceMetrics for distance="triangles")
 
 
 def _mc_soup(grids: t.Tensor, matrices: t.Tensor, level: float) -> Tuple[t.Tensor, t.Tensor]:
@@ -226,7 +229,7 @@ def _point_sets(triangles: t.Tensor, num_tri: t.Tensor, num_samples: int, seed: 
 
 def surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, num_samples: int = 16384,
                               thresholds: Sequence[float] = DEFAULT_SURFACE_THRESHOLDS, seed: int = 0, level: float = 0.5,
-                              gt_source: str = "mesh") -> SurfaceRows:
+                              gt_source: str = "mesh", distance: str = "points") -> SurfaceRows:
   """Chamfer distance and F-score of the predicted surfaces of a batch against its ground truth, per (scene, class).
 
   pmf f32 [B, C, D, H, W] class probabilities; ex the voxelized BatchedExample.  The predicted surface of (scene b,
@@ -244,12 +247,19 @@ def surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, num_samples: int = 1
             are bounded away from their ideal by those faces, against "grid" they measure the voxel surface alone.
   thresholds are distances in view-space units (the scene cube has side 1).  Both sides are sampled with the same seed,
   so identical surfaces give identical samples and a distance of exactly 0.
+  distance:
+    "points"     from the samples of one surface to the nearest SAMPLE of the other (chamfer_fscore).  The numbers carry
+                 the sampling floor of about 0.5 sqrt(area / num_samples).
+    "triangles"  from the samples of one surface to the TRIANGLES of the other (mesh_chamfer_fscore), the same two soups:
+                 no floor, and rows.metrics is a MeshSurfaceMetrics with normal consistency.
 
   Per call: one marching-cubes call for the prediction (one more for gt_source="grid"), two sampling calls, two
-  nearest-neighbour calls; no Python loop over kernels.  A class absent on both sides gives a NaN row."""
+  nearest-neighbour (or point-to-triangle) calls; no Python loop over kernels.  A class absent on both sides gives a NaN row."""
   task = _task(task_type)
   if gt_source not in ("mesh", "grid"):
     raise ValueError(f"surface_metrics_for_batch: gt_source must be 'mesh' or 'grid', got {gt_source!r}")
+  if distance not in ("points", "triangles"):
+    raise ValueError(f"surface_metrics_for_batch: distance must be 'points' or 'triangles', got {distance!r}")
   if pmf.dim() != 5 or pmf.shape[1] < 2:
     raise ValueError(f"surface_metrics_for_batch: pmf must be [B, C >= 2, D, H, W], got {tuple(pmf.shape)}")
   dev = pmf.device
@@ -282,9 +292,14 @@ def surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, num_samples: int = 1
         start += int(mesh_num_tri[b].sum())
       gather = t.cat(pieces) if pieces else t.zeros(0, dtype=t.int64)
       gt_tri, gt_cnt = ex.vertices.to(dev, t.float32)[gather.to(dev)], t.tensor(cnt, dtype=t.int64)
-  pred_pts, pred_off = _point_sets(pred_tri, pred_cnt, num_samples, seed)
-  gt_pts, gt_off = _point_sets(gt_tri, gt_cnt, num_samples, seed)
-  metrics = mesh_metrics.chamfer_fscore(pred_pts, pred_off, gt_pts, gt_off, thresholds)
+  if distance == "triangles":
+    def csr(cnt):
+      return t.cat([t.zeros(1, dtype=t.int64), t.cumsum(cnt.to(t.int64).cpu(), 0)])
+    metrics = mesh_metrics.mesh_chamfer_fscore(pred_tri, csr(pred_cnt), gt_tri, csr(gt_cnt), thresholds, num_samples, seed)
+  else:
+    pred_pts, pred_off = _point_sets(pred_tri, pred_cnt, num_samples, seed)
+    gt_pts, gt_off = _point_sets(gt_tri, gt_cnt, num_samples, seed)
+    metrics = mesh_metrics.chamfer_fscore(pred_pts, pred_off, gt_pts, gt_off, thresholds)
   rows = t.arange(B * K)
   return SurfaceRows(rows // K, rows % K + 1, [ex.scene_id[b] for b in range(B) for _ in range(K)],
                      tuple(float(x) for x in thresholds), metrics)
@@ -299,12 +314,19 @@ class SurfaceResults:
   """Accumulates surface_metrics_for_batch over an evaluation run, in the spirit of the reference's QuantitativeResults
   for IoU: add_batch(pmf, ex) takes what pipeline.evaluate_batch returns, summary() gives the mean Chamfer-L1 and F-score
   per threshold, per class and overall, over the rows that are not NaN (classes absent on both sides are skipped; a
-  class present on one side only counts with Chamfer +inf and F-score 0)."""
+  class present on one side only counts with Chamfer +inf and F-score 0).  With distance="triangles" it also accumulates
+  normal consistency and summary() carries it per class and overall."""
 
   def __init__(self, task_type="fg_bg", num_samples: int = 16384, thresholds: Sequence[float] = DEFAULT_SURFACE_THRESHOLDS,
-               seed: int = 0, level: float = 0.5, gt_source: str = "mesh"):
+               seed: int = 0, level: float = 0.5, gt_source: str = "mesh", distance: str = "points"):
+    if distance not in ("points", "triangles"):
+      raise ValueError(f"SurfaceResults: distance must be 'points' or 'triangles', got {distance!r}")
     self.task_type = task_type
+    self.distance = distance
     self.kwargs = dict(num_samples=num_samples, thresholds=tuple(thresholds), seed=seed, level=level, gt_source=gt_source)
+    if distance != "points":
+      self.kwargs["distance"] = distance
+    self.normal_consistency: List[t.Tensor] = []
     self.thresholds = tuple(float(x) for x in thresholds)
     self.scene_id: List[str] = []
     self.class_index: List[t.Tensor] = []
@@ -317,6 +339,8 @@ class SurfaceResults:
     self.class_index.append(rows.class_index)
     self.chamfer_l1.append(rows.metrics.chamfer_l1.cpu())
     self.fscore.append(rows.metrics.fscore.cpu())
+    if self.distance == "triangles":
+      self.normal_consistency.append(rows.metrics.normal_consistency.cpu())
     return rows
 
   def rows(self) -> Tuple[t.Tensor, t.Tensor, t.Tensor]:
@@ -327,10 +351,14 @@ class SurfaceResults:
 
   def summary(self) -> Dict:
     cls, cd, f = self.rows()
+    nc = t.cat(self.normal_consistency) if self.normal_consistency else t.zeros(0, dtype=t.float64)
 
     def entry(sel):
-      return {"chamfer_l1": float(_nanmean(cd[sel])), "fscore": [float(v) for v in _nanmean(f[sel])],
-              "num_rows": int((~t.isnan(cd[sel])).sum())}
+      e = {"chamfer_l1": float(_nanmean(cd[sel])), "fscore": [float(v) for v in _nanmean(f[sel])],
+           "num_rows": int((~t.isnan(cd[sel])).sum())}
+      if self.distance == "triangles":
+        e["normal_consistency"] = float(_nanmean(nc[sel]))
+      return e
     return {"thresholds": list(self.thresholds), "overall": entry(t.ones_like(cls, dtype=t.bool)),
             "per_class": {int(c): entry(cls == c) for c in sorted(set(cls.tolist()))}}
 

@@ -801,6 +801,37 @@ int crn_nearest(const float* a, const int64_t* a_offsets, const float* b, const 
 int crn_nearest_cpu(const float* a, const int64_t* a_offsets, const float* b, const int64_t* b_offsets, int N,
                     float* dist2, int32_t* index, int num_threads);
 
+/* crn_point_triangle: for query q of object n (p [Np][3], p_offsets) the triangle of object n
+ * (triangles [T][3][3], t_offsets) with the smallest (d2, index), d2 the squared Euclidean distance from the query to the
+ * closed triangle in float32.  dist2 f32 [Np], index int32 [Np] (local to the object).
+ *   eligible   a triangle is a candidate when pm_area_ok(pm_area(triangle)) holds (the sampler's rule: positive finite
+ *              area); zero-area, collinear, NaN and infinite triangles are never chosen.
+ *   no winner  a candidate is chosen only when its d2 is below +inf: a NaN d2 is never chosen, nor one that overflows
+ *              float32.  A query without such a candidate (an empty object, no eligible triangle, a NaN query) gets +inf
+ *              and -1.
+ *   ties       to the lowest index (ascending candidates, strict <).
+ *   arithmetic pm_tri_record / pm_tri_d2 of csrc/point_metrics_common.h, once, for the kernel and the host twin, without
+ *              contraction: both return the same dist2 and index bit for bit.  A triangle becomes a record of 20 floats
+ *              (an orthonormal frame at A, the edges' unit directions and lengths in it; a pre-pass on the GPU); the
+ *              pair routine is z^2 plus the squared in-plane distance (0 inside, else the smallest of three clamped edge
+ *              distances), selects only.
+ * max_np / max_nt: the largest number of queries / triangles of one object (max_nt <= CRN_PM_MAX_CANDIDATES); they size
+ * the launch, the offsets stay on the device.  workspace: crn_point_triangle_workspace_bytes(Np, T) (the records, and
+ * 64-bit keys for launches that split the triangles of an object over crn_point_triangle_splits(N, max_np, max_nt) > 1
+ * workgroups and merge with atomicMin, as crn_nearest).  A workgroup holds CRN_PT_QUERY_TILE queries and walks tiles of
+ * CRN_PT_TRIANGLE_TILE records; shares are whole tiles.  crn_point_triangle_tile(0 / 1) returns the query / triangle
+ * tile the library was built with (anything else: 0).  The call does not wait for the GPU.                           */
+#define CRN_PT_QUERY_TILE 1024
+#define CRN_PT_TRIANGLE_TILE 256
+size_t crn_point_triangle_tile(int which);
+size_t crn_point_triangle_workspace_bytes(int64_t Np, int64_t T);
+size_t crn_point_triangle_splits(int N, int64_t max_np, int64_t max_nt);
+int crn_point_triangle(const float* p, const int64_t* p_offsets, const float* triangles, const int64_t* t_offsets,
+                       int N, int64_t Np, int64_t T, int64_t max_np, int64_t max_nt,
+                       void* workspace, size_t workspace_bytes, float* dist2, int32_t* index, crnStream s);
+int crn_point_triangle_cpu(const float* p, const int64_t* p_offsets, const float* triangles, const int64_t* t_offsets,
+                           int N, float* dist2, int32_t* index, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
