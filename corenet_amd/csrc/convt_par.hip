@@ -932,7 +932,7 @@ namespace {
 constexpr int64_t kMaxTiles = 0x7fffffff;
 template <typename Geom>
 int64_t ct_grid(Geom& g, const float* x, int64_t x_sB, int B, int D, int H, int W, int td, const crnInTransform* tr) {
-  if (D % td || H % TH || W % TW) return -1;
+  if (D < 1 || H < 1 || W < 1 || D % td || H % TH || W % TW) return -1;      // (an extent of 0 is a whole number of tiles too: no launch)
   g.x = x; g.x_sB = x_sB; g.B = B; g.D = D; g.H = H; g.W = W;
   if (tr && tr->scale) { g.scale = tr->scale; g.shift = tr->shift; g.pre_relu = tr->pre_relu; g.post_relu = tr->post_relu; }
   g.tilesD = D / td; g.tilesH = H / TH; g.tilesW = W / TW;
@@ -1037,10 +1037,9 @@ extern "C" int crn_convt_s2k7_wgrad_bf3(const float* x, int64_t x_sB, int B, int
   if ((((uintptr_t)x) & 15) || (x_sB & 3) || (((uintptr_t)dy) & 15) || (dy_sB & 3) || (dy_sC & 3)) return CRN_EINVAL;
   CtWgGeom g{};
   const int64_t ntiles = ct_grid(g, x, x_sB, B, D, H, W, WTD, tr);
-  if (ntiles < 0) return CRN_EINVAL;
+  if (ntiles < 0 || ntiles > kMaxTiles) return CRN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)16 * 64 * Npad * sizeof(float), st));
-  if (ntiles > kMaxTiles) return CRN_EINVAL;
+  if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)16 * 64 * Npad * sizeof(float), st));      // (behind the last rejection)
   g.dy = dy; g.dy_sB = dy_sB; g.dy_sC = dy_sC; g.Cout = Cout; g.dw = dw; g.Npad = Npad;
   g.ximg = reinterpret_cast<const float*>(ximg); g.ximg_sB = (long long)16 * D * H * W;      // (floats per sample: 4 regions x 4 floats per entry)
   g.ntiles = (int)ntiles;

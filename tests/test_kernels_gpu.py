@@ -423,7 +423,8 @@ def test_convt_entries_accept_reject_contract(be):
   thing wrong, its literal status is asserted, and no output buffer may be touched (a rejected call launches nothing).  The entries
   differ on purpose: the generic ones take 1..16 classes, c2_fwd exactly 2, c2_dgrad 1 or 2 (that row is a GOOD call: checked against
   the contract emulator, 2e-5 of the range like test_convt_resident_weights_two_classes); only the generic data gradient wants
-  dy_sC >= 8 D H W; the weight gradient tiles D by 2 and steps aside in deterministic mode.  Every buffer has one sample + 64 bytes of
+  dy_sC >= 8 D H W; the weight gradient tiles D by 2 and steps aside in deterministic mode; an extent of 0 is rejected like one that is
+  no whole number of tiles (the host code once divided by the tile count of such a call).  Every buffer has one sample + 64 bytes of
   slack behind its real size (and dy / y 18 channels, dw the 17-class size) so that a call accepted by mistake stays inside it."""
   if _SELF:
     return
@@ -472,6 +473,9 @@ def test_convt_entries_accept_reject_contract(be):
   rows += [("wgrad", {"Cout": 0}, EINVAL), ("wgrad", {"Cout": 17, "Npad": 8 * 17}, EINVAL)]
   rows += [("c2_fwd", {"Cout": 3}, EINVAL), ("c2_dgrad", {"Cout": 3}, EINVAL), ("c2_fwd", {"Cout": 1}, EINVAL)]
   rows += [(e, bad, EINVAL) for e in ALL5 for bad in ({"D": 3}, {"H": 4}, {"W": 8})]
+  # an extent of 0 is "a whole number of tiles" too: rejected before the host code divides by the tile count (zero_first = 1 in the
+  # good weight-gradient call: its memset sits behind the last rejection, dw keeps its sentinel)
+  rows += [(e, bad, EINVAL) for e in ALL5 for bad in ({"D": 0}, {"H": 0}, {"W": 0})]
   for es, names in ((FWD, ("x", "y")), (DGR, ("dy", "dx")), (("wgrad",), ("x", "dy", "ximg")), (("ximage",), ("x", "img"))):
     rows += [(e, {n: good[e][n] + 4}, EINVAL) for e in es for n in names]         # a base pointer off by 4 bytes
   for es, names in ((FWD, ("x_sB", "y_sB", "y_sC")), (DGR, ("dx_sB", "dy_sB", "dy_sC")), (("wgrad",), ("x_sB", "dy_sB", "dy_sC")),
