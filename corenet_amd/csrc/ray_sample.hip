@@ -192,8 +192,8 @@ __global__ __launch_bounds__(256) void ray_project_kernel(const float* matrix, c
 // There is no floating-point projection in this kernel (rounds 1-4 projected every voxel again, three times over for the
 // three channel groups, and the loop-invariant products of that projection were what the MFMA-neighbour glitch of DESIGN
 // section 3e hit); index compares, float adds of run sums and integer atomics are all that is left.
-// DET (deterministic mode, crn_common.h): ALL sums are taken in 64-bit fixed point, in HBM -- scale_p[0] = 2^k chosen from
-// max |dout| of the whole tensor so that a pixel's sum cannot overflow; detmap = int64 image of dmap ([B][C][h][w], zeroed),
+// DET (deterministic mode, crn_common.h): ALL sums are taken in 64-bit fixed point, in HBM -- scale_p[0] * scale_p[1] = 2^k chosen
+// from max |dout| of the whole tensor so that a pixel's sum cannot overflow; detmap = int64 image of dmap ([B][C][h][w], zeroed),
 // converted by ray_det_finish_kernel.  The LDS window is not used.
 struct ScatterArgs {
   const float* dout; int64_t dout_sB; int C, D, H, W;
@@ -324,11 +324,17 @@ __global__ __launch_bounds__(256) void ray_scatter_kernel(const ScatterArgs a) {
           for (int k = 0; k < CN; ++k)
             if (cbase + k < C) atomicAdd(wp + k * wn, to_fixed(acc[k], fix_scale));          // ds_add_u64
         } else if (DET) {
-          const float sc = a.scale_p[0];
+          // the scale is the product of two floats (ray_det_scale_kernel); both products are exact.  A run sum that is not
+          // finite has no fixed-point image: it goes to dmap in float, where the finish kernel's add keeps it -- which of
+          // +-inf / NaN a pixel ends at does not depend on the order of the adds (index_put_ propagates them likewise)
+          const float sc0 = a.scale_p[0], sc1 = a.scale_p[1];
           unsigned long long* db = a.detmap + ((int64_t)b * C + cbase) * hw;
 #pragma unroll
           for (int k = 0; k < CN; ++k)
-            if (cbase + k < C) atomicAdd(db + k * hw + cur, (unsigned long long)(long long)__float2ll_rn(acc[k] * sc));
+            if (cbase + k < C) {
+              if ((__float_as_uint(acc[k]) & 0x7f800000u) == 0x7f800000u) atomicAdd(mb + k * hw + cur, acc[k]);
+              else atomicAdd(db + k * hw + cur, (unsigned long long)(long long)__float2ll_rn(acc[k] * sc0 * sc1));
+            }
         } else {
 #pragma unroll
           for (int k = 0; k < CN; ++k)
@@ -366,25 +372,32 @@ __global__ __launch_bounds__(256) void ray_scatter_kernel(const ScatterArgs a) {
   }
 }
 
-// deterministic mode: max |dout| (integer max of the float bit patterns), then the power-of-two scale
+// deterministic mode: max |dout| over the FINITE elements (integer max of the float bit patterns; inf / NaN take the float
+// path of the scatter), then the power-of-two scale
 __global__ void ray_det_maxabs_kernel(const float* dout, int64_t dout_sB, int64_t per_b, int B, unsigned* maxbits) {
   unsigned m = 0;
   for (int b = 0; b < B; ++b)
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per_b; i += (int64_t)gridDim.x * blockDim.x)
-      m = max(m, __float_as_uint(fabsf(dout[b * dout_sB + i])));
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per_b; i += (int64_t)gridDim.x * blockDim.x) {
+      const unsigned u = __float_as_uint(fabsf(dout[b * dout_sB + i]));
+      if (u < 0x7f800000u) m = max(m, u);
+    }
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0 && m) atomicMax(maxbits, m);
 }
 __global__ void ray_det_scale_kernel(const unsigned* maxbits, float* scale, int log2_terms) {
-  // |sum| <= 2^log2_terms * max: scale = 2^(61 - log2_terms - exponent(max) - 1) keeps it below 2^62
+  // |sum| <= 2^log2_terms * max: scale = 2^(61 - log2_terms - exponent(max) - 1) keeps it below 2^62.  A max below about
+  // 2^-(66 + log2_terms) needs more than 2^127: the scale is kept as scale[0] * scale[1], each a float (up to 2^254 in all,
+  // the smallest subnormal max needs 2^(61 + 148)); scale[1] = 1 for every max that needed one float, the product unchanged
   const float mx = __uint_as_float(maxbits[0]);
   int e = 0;
   if (mx > 0.f) frexpf(mx, &e);                                 // mx = f * 2^e, 0.5 <= f < 1
-  scale[0] = mx > 0.f ? ldexpf(1.f, 61 - log2_terms - e) : 1.f;
+  const int k = 61 - log2_terms - e;
+  scale[0] = mx > 0.f ? ldexpf(1.f, min(k, 127)) : 1.f;
+  scale[1] = mx > 0.f ? ldexpf(1.f, max(k - 127, 0)) : 1.f;
 }
 __global__ void ray_det_finish_kernel(const unsigned long long* detmap, const float* scale, float* dmap, int64_t dmap_sB,
                                       int64_t per_b, int B) {
-  const double inv = 1.0 / (double)scale[0];
+  const double inv = 1.0 / ((double)scale[0] * (double)scale[1]);
   for (int b = 0; b < B; ++b)
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per_b; i += (int64_t)gridDim.x * blockDim.x)
       dmap[b * dmap_sB + i] += (float)((double)(long long)detmap[b * per_b + i] * inv);
