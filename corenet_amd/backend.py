@@ -578,6 +578,25 @@ class HipBackend:
     st = (C.c_int64 * 4)(*grid.stride())
     self.lib.crn_box_filter(ptr(grid), st, ptr(out), N, D, H, W, int(k), ptr(ws), n, _lib.stream())
 
+  # -- voxel components (corenet_amd.voxel_components) ----------------------------------------------
+  def voxel_components(self, grid: t.Tensor, connectivity: int, by_value: bool, labels: t.Tensor, num: t.Tensor):
+    """labels (int32 [N, D, H, W]) / num (device int64 [N]) <- the connected components of grid (uint8 or int32, W
+    stride 1); queued on the current stream."""
+    N, D, H, W = grid.shape
+    n = self.lib.crn_voxel_components_workspace_bytes(N, D, H, W)
+    ws = self.workspace("vc", n, grid.device)
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_voxel_components(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, int(connectivity), int(bool(by_value)),
+                                  ptr(ws), n, ptr(labels), ptr(num), _lib.stream())
+
+  def component_stats(self, labels: t.Tensor, grid: Optional[t.Tensor], offsets: t.Tensor, K: int, size: t.Tensor,
+                      bbox: t.Tensor, first: t.Tensor, value: Optional[t.Tensor]):
+    """size / bbox / first (/ value when grid is given) of the K components of labels; offsets: device int64 [N + 1]."""
+    N, D, H, W = labels.shape
+    st = None if grid is None else (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_component_stats(ptr(labels), ptr(grid), st, 0 if grid is None else _DTYPE_CODE[grid.dtype], N, D, H, W,
+                                 ptr(offsets), int(K), ptr(size), ptr(bbox), ptr(first), ptr(value), _lib.stream())
+
   # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
   def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
                      tri_index: t.Tensor, valid: t.Tensor):

@@ -229,7 +229,8 @@ def _point_sets(triangles: t.Tensor, num_tri: t.Tensor, num_samples: int, seed: 
 
 def surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, num_samples: int = 16384,
                               thresholds: Sequence[float] = DEFAULT_SURFACE_THRESHOLDS, seed: int = 0, level: float = 0.5,
-                              gt_source: str = "mesh", distance: str = "points") -> SurfaceRows:
+                              gt_source: str = "mesh", distance: str = "points",
+                              min_component_voxels: int = 0) -> SurfaceRows:
   """Chamfer distance and F-score of the predicted surfaces of a batch against its ground truth, per (scene, class).
 
   pmf f32 [B, C, D, H, W] class probabilities; ex the voxelized BatchedExample.  The predicted surface of (scene b,
@@ -252,6 +253,9 @@ def surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, num_samples: int = 1
                  the sampling floor of about 0.5 sqrt(area / num_samples).
     "triangles"  from the samples of one surface to the TRIANGLES of the other (mesh_chamfer_fscore), the same two soups:
                  no floor, and rows.metrics is a MeshSurfaceMetrics with normal consistency.
+  min_component_voxels > 0 removes floaters from the prediction first: of every (scene, class) the 6-connected components
+  of pmf[b, k] > level with fewer voxels are set to 0 before marching cubes (corenet_amd.voxel_components); the ground
+  truth is untouched.  0 (the default) runs none of that.
 
   Per call: one marching-cubes call for the prediction (one more for gt_source="grid"), two sampling calls, two
   nearest-neighbour (or point-to-triangle) calls; no Python loop over kernels.  A class absent on both sides gives a NaN row."""
@@ -271,7 +275,12 @@ def surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, num_samples: int = 1
     raise ValueError(f"surface_metrics_for_batch: fg_bg expects 2 classes, pmf has {C}")
   v2x_inv = [ex.v2x_transform[b].detach().cpu().to(t.float32).inverse() for b in range(B)]
   mats = t.stack([v2x_inv[b] for b in range(B) for _ in range(K)]).to(dev)
-  pred_tri, pred_cnt = _mc_soup(pmf[:, 1:].reshape((B * K,) + tuple(pmf.shape[2:])), mats, level)
+  pred = pmf[:, 1:].reshape((B * K,) + tuple(pmf.shape[2:]))
+  if min_component_voxels > 0:
+    from corenet_amd.voxel_components import filter_components
+    kept = filter_components(pred > level, min_voxels=int(min_component_voxels), connectivity=6)
+    pred = t.where(kept, pred, t.zeros((), dtype=pred.dtype, device=dev))
+  pred_tri, pred_cnt = _mc_soup(pred, mats, level)
   if gt_source == "grid":
     classes = t.arange(1, C, device=dev, dtype=ex.grid.dtype)[None, :, None, None, None]
     onehot = (ex.grid.to(dev)[:, None] == classes).to(t.float32)
@@ -318,7 +327,8 @@ class SurfaceResults:
   normal consistency and summary() carries it per class and overall."""
 
   def __init__(self, task_type="fg_bg", num_samples: int = 16384, thresholds: Sequence[float] = DEFAULT_SURFACE_THRESHOLDS,
-               seed: int = 0, level: float = 0.5, gt_source: str = "mesh", distance: str = "points"):
+               seed: int = 0, level: float = 0.5, gt_source: str = "mesh", distance: str = "points",
+               min_component_voxels: int = 0):
     if distance not in ("points", "triangles"):
       raise ValueError(f"SurfaceResults: distance must be 'points' or 'triangles', got {distance!r}")
     self.task_type = task_type
@@ -326,6 +336,8 @@ class SurfaceResults:
     self.kwargs = dict(num_samples=num_samples, thresholds=tuple(thresholds), seed=seed, level=level, gt_source=gt_source)
     if distance != "points":
       self.kwargs["distance"] = distance
+    if min_component_voxels > 0:
+      self.kwargs["min_component_voxels"] = int(min_component_voxels)
     self.normal_consistency: List[t.Tensor] = []
     self.thresholds = tuple(float(x) for x in thresholds)
     self.scene_id: List[str] = []

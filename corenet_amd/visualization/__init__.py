@@ -2,9 +2,10 @@
 triangle / voxel-grid renderer (csrc/render.hip) and their host twins."""
 from corenet_amd.visualization.marching_cubes import (Meshes, box_filter, marching_cubes, marching_cubes_artifact_mesh,
                                                       to_marching_cubes, write_ply)
+from corenet_amd.visualization.instances import InstanceTable, instance_meshes
 from corenet_amd.visualization.render import (VoxelFaces, load_textures, make_materials, render_batch, render_scene,
                                               render_scenes, render_voxel_grid, voxel_faces, voxel_materials)
 
 __all__ = ["Meshes", "box_filter", "marching_cubes", "marching_cubes_artifact_mesh", "to_marching_cubes", "write_ply",
-           "VoxelFaces", "load_textures", "make_materials", "render_batch", "render_scene", "render_scenes",
+           "InstanceTable", "instance_meshes", "VoxelFaces", "load_textures", "make_materials", "render_batch", "render_scene", "render_scenes",
            "render_voxel_grid", "voxel_faces", "voxel_materials"]

@@ -832,6 +832,47 @@ int crn_point_triangle(const float* p, const int64_t* p_offsets, const float* tr
 int crn_point_triangle_cpu(const float* p, const int64_t* p_offsets, const float* triangles, const int64_t* t_offsets,
                            int N, float* dist2, int32_t* index, int num_threads);
 
+/* ---------------- voxel components (corenet_amd.voxel_components) -----------------
+ * Connected-component labelling of N independent grids grid[n][d][h][w] (element strides[0..2] arbitrary and >= 0,
+ * strides[3] must be 1; dtype 1 = uint8, 2 = int32, the codes of crn_fill_voxels).  Contract: DESIGN section 17.
+ *   foreground    value > 0.
+ *   connectivity  6 (faces), 18 (+ edges) or 26 (+ corners); by_value != 0: two neighbouring foreground voxels belong
+ *                 together only if their values are equal, by_value == 0: always.
+ *   labels        int32 [N][D][H][W] contiguous: 0 on background, the components of grid n numbered 1 .. K_n in ascending
+ *                 order of their lowest linear index d*H*W + h*W + w (for binary input scipy.ndimage.label's numbering).
+ *                 D*H*W <= 2^31 - 1 (labels and parents are 32-bit per grid).  num_components: int64 [N].
+ * The result is a function of the partition alone: identical from run to run and between the kernels and the host twin.
+ *
+ * GPU: crn_voxel_components queues six launches on stream s and does not wait for the GPU; no workgroup waits for
+ * another one (bricks of CRN_VC_BRICK_D x _H x _W voxels labelled in LDS, seams united with atomicMin on a global parent
+ * array, raster-order numbering by a chunked prefix sum).  workspace: crn_voxel_components_workspace_bytes(N, D, H, W)
+ * (the parents and the chunk counts).  N <= 65535.  crn_voxel_components_bricks writes the three brick extents.
+ *
+ * crn_component_stats: for component c = offsets[n] + label - 1 of grid n (offsets int64 [N + 1], the exclusive prefix
+ * sum of num_components; DEVICE memory for the GPU call; K = offsets[N]): size int64 [K] voxels, bbox int32 [K][6]
+ * (d0, h0, w0, d1, h1, w1) with exclusive upper bounds, first int64 [K] the lowest linear index, and, when grid is not
+ * NULL, value int32 [K] the grid's value at `first` (grid NULL: strides, dtype and value are not looked at).  Integer
+ * atomics: order-independent.  Labels outside 1 .. K_n are ignored.
+ *
+ * Host twins (HOST memory, same contract, identical results): a two-pass union-find over the whole grid, one grid per
+ * thread; num_threads <= 0: all.                                                                                    */
+#define CRN_VC_BRICK_D 8
+#define CRN_VC_BRICK_H 16
+#define CRN_VC_BRICK_W 64
+int crn_voxel_components_bricks(int32_t* out3);
+size_t crn_voxel_components_workspace_bytes(int N, int D, int H, int W);
+int crn_voxel_components(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int connectivity,
+                         int by_value, void* workspace, size_t workspace_bytes, int32_t* labels, int64_t* num_components,
+                         crnStream s);
+int crn_component_stats(const int32_t* labels, const void* grid, const int64_t* strides, int dtype, int N, int D, int H,
+                        int W, const int64_t* offsets, int64_t K, int64_t* size, int32_t* bbox, int64_t* first,
+                        int32_t* value, crnStream s);
+int crn_voxel_components_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W,
+                             int connectivity, int by_value, int32_t* labels, int64_t* num_components, int num_threads);
+int crn_component_stats_cpu(const int32_t* labels, const void* grid, const int64_t* strides, int dtype, int N, int D,
+                            int H, int W, const int64_t* offsets, int64_t K, int64_t* size, int32_t* bbox,
+                            int64_t* first, int32_t* value, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
