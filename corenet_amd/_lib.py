@@ -82,6 +82,7 @@ class HipError(RuntimeError):
 _SIGS = {
     "crn_conv_fwd": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32,
                      C.POINTER(CrnView), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "crn_conv1x1_fwd_pair": [C.POINTER(CrnView), vp, C.POINTER(CrnView), vp, i32, C.POINTER(CrnView), i32, i32, vp],
     "crn_conv_fwd_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), vp, i32, vp, i32,
                           C.POINTER(CrnView), i32, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(CrnConvPlan)],
     "crn_conv_wgrad_plan": [C.POINTER(CrnView), C.POINTER(CrnInTransform), C.POINTER(CrnView), vp, i32,

@@ -109,6 +109,16 @@ class HipBackend:
                           pad_lo[0], pad_lo[1], pad_lo[2], splits, int(accumulate), _ctapboxes(boxes),
                           _lib.stream())
 
+  def conv1x1_pair(self, x1: View, w1: t.Tensor, x2: View, w2: t.Tensor, npad: int, y: View, splits: int = 0,
+                   accumulate: bool = False) -> bool:
+    """y (+)= w1^T x1 + w2^T x2 in one launch of the fp32 pointwise kernel (crn_conv1x1_fwd_pair).  False: a shape the entry
+    does not cover (CRN_EINVAL), nothing was written or launched -- the caller issues the two convolutions."""
+    rc = self.lib._crn_conv1x1_fwd_pair(C.byref(_cview(x1)), ptr(w1), C.byref(_cview(x2)), ptr(w2), npad, C.byref(_cview(y)),
+                                        splits, int(accumulate), _lib.stream())
+    if rc not in (0, -1):
+      raise _lib.HipError(f"crn_conv1x1_fwd_pair failed with status {rc}")
+    return rc == 0
+
   @staticmethod
   def _plan_dict(p) -> dict:
     d = {n: int(getattr(p, n)) for n, _ in p._fields_}

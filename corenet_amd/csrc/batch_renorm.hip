@@ -34,6 +34,58 @@ __device__ __forceinline__ void for_slice(Slice sl, F4 f4, F1 f1) {
   }
 }
 
+// Sum over the `splits` partial results of a split-K convolution at one element (T = float) or float4 (T = f32x4): p = the
+// element in split 0, `slab` = Ts per split ([split][b][c][pos], dense).  Split 0 first, the order of the reduction kernel.
+// The loads of up to four splits are issued together, as in splitk_reduce_plain_kernel: walked one load latency after the other
+// (a loop over a run-time `splits`) the first pass of the two-pass backward took 113 us per step where it now takes 97.
+template <typename T>
+__device__ __forceinline__ T bn_splitk_sum_at(const T* p, int splits, int64_t slab) {
+  T sum = T{};
+  int sp = 0;
+  for (; sp + 4 <= splits; sp += 4) {       // the loads of four splits in flight, added in order (as the reduction kernel does)
+    const T a = p[sp * slab], b = p[(sp + 1) * slab], c = p[(sp + 2) * slab], d = p[(sp + 3) * slab];
+    sum += a; sum += b; sum += c; sum += d;
+  }
+  const int rest = splits - sp;             // 0..3 (uniform): loaded together as well
+  if (rest > 0) {
+    const T a = p[sp * slab], b = rest > 1 ? p[(sp + 1) * slab] : T{}, c = rest > 2 ? p[(sp + 2) * slab] : T{};
+    sum += a;
+    if (rest > 1) sum += b;
+    if (rest > 2) sum += c;
+  }
+  return sum;
+}
+
+// The first pass of a two-pass launch over a pending split-K sum (part != nullptr; t = the dense [B][C][S] tensor whose
+// values are still `splits` partial sums in the scratch): the workgroup that owns a slice adds it up, stores the sum to t for
+// the second pass and every later reader, and accumulates from it.  at() = the value of t at offset o of the channel row.
+// PEND is a template parameter of the kernels: the launches with nothing pending keep the plain loads' code.
+template <bool PEND>
+struct BnPendingRow {
+  const float* part; float* t; int64_t slab; int splits;     // part, t: the (b, c) row; slab = B * C * S
+  __device__ __forceinline__ f32x4 at4(int64_t o) const {
+    if (!PEND) return *reinterpret_cast<const f32x4*>(t + o);
+    const f32x4 v = bn_splitk_sum_at(reinterpret_cast<const f32x4*>(part + o), splits, slab / 4);
+    *reinterpret_cast<f32x4*>(t + o) = v;
+    return v;
+  }
+  __device__ __forceinline__ float at1(int64_t o) const {
+    if (!PEND) return t[o];
+    const float v = bn_splitk_sum_at(part + o, splits, slab);
+    t[o] = v;
+    return v;
+  }
+};
+template <bool PEND>
+__device__ __forceinline__ BnPendingRow<PEND> bn_pending_row(const float* t, int64_t sB, const float* part, int splits, int B,
+                                                             int C, int64_t S, int b, int c) {
+  BnPendingRow<PEND> r;
+  r.t = const_cast<float*>(t) + (int64_t)b * sB + (int64_t)c * S;
+  r.part = PEND ? part + ((int64_t)b * C + c) * S : nullptr;
+  r.slab = (int64_t)B * C * S; r.splits = splits;
+  return r;
+}
+
 // ---- statistics -------------------------------------------------------------
 // One element into the fp64 sums of a channel: sum(x'), sum(x'^2) with x' = relu(x) under pre_relu.
 __device__ __forceinline__ void bn_acc(float v, int pre_relu, double& s1, double& s2) {
@@ -42,18 +94,18 @@ __device__ __forceinline__ void bn_acc(float v, int pre_relu, double& s1, double
   s2 += (double)v * (double)v;
 }
 
-template <bool VEC>
+template <bool VEC, bool PEND>
 __global__ __launch_bounds__(kThreads) void bn_partial_kernel(const float* x, int64_t S, int64_t sB,
-                                                               int pre_relu, double* ws) {
+                                                               int pre_relu, double* ws, const float* part, int splits) {
   __shared__ double red[kThreads / 64];
   const int c = blockIdx.y, b = blockIdx.z;
-  const float* p = x + (int64_t)b * sB + (int64_t)c * S;
+  const BnPendingRow<PEND> p = bn_pending_row<PEND>(x, sB, part, splits, gridDim.z, gridDim.y, S, b, c);
   double s1 = 0.0, s2 = 0.0;
   auto one = [&](float v) { bn_acc(v, pre_relu, s1, s2); };
   for_slice<VEC>(block_slice(S),
-                 [&](int64_t s) { const f32x4 v = *reinterpret_cast<const f32x4*>(p + s);
+                 [&](int64_t s) { const f32x4 v = p.at4(s);
                                   one(v.x); one(v.y); one(v.z); one(v.w); },
-                 [&](int64_t s) { one(p[s]); });
+                 [&](int64_t s) { one(p.at1(s)); });
   const double t1 = crn_block_sum(s1, red);
   const double t2 = crn_block_sum(s2, red);
   if (threadIdx.x == 0) {
@@ -192,11 +244,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Sum of the `splits` partial results ([split][b][c][pos], dense) a split-K convolution left in the scratch, for float4 s4 of
 // (b, c): split 0 first, the order of the reduction kernel.
 __device__ __forceinline__ f32x4 bn_splitk_sum(const float* part, int splits, int B, int C, int S4, int b, int c, int s4) {
-  const f32x4* pp = reinterpret_cast<const f32x4*>(part) + ((int64_t)b * C + c) * S4 + s4;
-  const int64_t slab4 = (int64_t)B * C * S4;
-  f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int sp = 0; sp < splits; ++sp) sum += pp[sp * slab4];
-  return sum;
+  return bn_splitk_sum_at(reinterpret_cast<const f32x4*>(part) + ((int64_t)b * C + c) * S4 + s4, splits, (int64_t)B * C * S4);
 }
 
 // Where float4 s4 of channel c's full plane (rows of width W, a multiple of 4) lands in the stride-2 compaction [c][H2][W2] of
@@ -443,25 +491,26 @@ __global__ __launch_bounds__(kThreads) void bn_owner_bwd_reg_kernel(
 }
 
 // ---- backward ----------------------------------------------------------------
-template <bool VEC>
+template <bool VEC, bool PEND>
 __global__ __launch_bounds__(kThreads) void bn_bwd_partial_kernel(
     const float* x, int64_t sBx, const float* dy, int64_t sBdy, int64_t S, int C, int pre_relu,
     int post_relu, const float* scale, const float* shift, const float* saved, double* ws, float* dsum,
-    int ndsum) {
+    int ndsum, const float* part, int splits) {
   __shared__ double red[kThreads / 64];
   const int c = blockIdx.y, b = blockIdx.z;
   // the apply kernel (next launch on this stream) accumulates sum(dx) here with atomics
   if (dsum && c < ndsum && blockIdx.x == 0 && b == 0 && threadIdx.x == 0) dsum[c] = 0.f;
   const float* px = x + (int64_t)b * sBx + (int64_t)c * S;
-  const float* pg = dy + (int64_t)b * sBdy + (int64_t)c * S;
+  // (part != nullptr: dy is a pending split-K sum -- added up and stored here, the apply kernel reads it from dy)
+  const BnPendingRow<PEND> pg = bn_pending_row<PEND>(dy, sBdy, part, splits, gridDim.z, C, S, b, c);
   const BnBwdChannel ch = bn_bwd_channel(c, C, scale, shift, saved);
   double s1 = 0.0, s2 = 0.0;
   auto one = [&](float xv, float gv) { bn_bwd_acc(xv, gv, pre_relu, post_relu, ch, s1, s2); };
   for_slice<VEC>(block_slice(S),
                  [&](int64_t s) { const f32x4 a = *reinterpret_cast<const f32x4*>(px + s);
-                                  const f32x4 g = *reinterpret_cast<const f32x4*>(pg + s);
+                                  const f32x4 g = pg.at4(s);
                                   one(a.x, g.x); one(a.y, g.y); one(a.z, g.z); one(a.w, g.w); },
-                 [&](int64_t s) { one(px[s], pg[s]); });
+                 [&](int64_t s) { one(px[s], pg.at1(s)); });
   const double t1 = crn_block_sum(s1, red);
   const double t2 = crn_block_sum(s2, red);
   if (threadIdx.x == 0) {
@@ -715,17 +764,18 @@ inline void with_bool(bool on, F f) {
 }
 
 // A split-K convolution may have left the partial sums of its output pending (crn_splitk_defer).  If that output is `base`
-// and the launch about to be made is a register kernel on the same stream, the kernel adds them up itself: *part / *splits say
-// where they are.  The kernel stores the sum as [B][C][S] with nothing in between: only base, the extents and sB are compared
-// here, the rest is the producer's guarantee (a sum is left pending only for a crn_splitk_dense view, splitk.h).  A pending sum
-// meant for anything else is flushed first.
-int take_or_flush_pending(const float* base, int64_t sB, int B, int C, int64_t S, hipStream_t st, bool reg_form,
+// and the launch about to be made, on the same stream, is one that can add them up itself (`can_take`: a register kernel, or
+// the first pass of a two-pass launch, which stores the sum for the second), it does: *part / *splits say where they are.
+// The kernel stores the sum as [B][C][S] with nothing in between: only base, the extents and sB are compared here, the rest
+// is the producer's guarantee (a sum is left pending only for a crn_splitk_dense view, splitk.h).  A pending sum meant for
+// anything else is flushed first.
+int take_or_flush_pending(const float* base, int64_t sB, int B, int C, int64_t S, hipStream_t st, bool can_take,
                           const float** part, int* splits) {
   *part = nullptr; *splits = 0;
   CrnSplitPending& pend = crn_splitk_pending();
   if (!pend.active) return CRN_OK;
   const crnView& py = pend.y;
-  if (reg_form && pend.stream == st && py.base == base && py.B == B && py.C == C && (int64_t)py.D * py.H * py.W == S && sB == (int64_t)C * S) {
+  if (can_take && pend.stream == st && py.base == base && py.B == B && py.C == C && (int64_t)py.D * py.H * py.W == S && sB == (int64_t)C * S) {
     *part = pend.scratch; *splits = pend.splits; pend.active = false;
     return CRN_OK;
   }
@@ -766,10 +816,13 @@ static int bn_stats_impl(const float* x, int B, int C, int64_t S, int64_t sB, in
   if (training && (!nbt || !saved)) return CRN_EINVAL;
   int nparts = 1;
   const bool reg_form = training && owner_form(S, C, B) && vec_ok(S, {sB}, {x}) && (int64_t)B * S <= 16384;
-  // a split-K convolution left the partial sums of x pending (crn_splitk_defer): the register kernel adds them up
+  // a split-K convolution left the partial sums of x pending (crn_splitk_defer): the register kernel adds them up, or the
+  // first pass of the two-pass form (the owner kernel in between reads x twice: it gets the sum flushed)
+  // (a launch that is about to fail for want of workspace must not swallow the sum)
+  const bool two_pass = training && !owner_form(S, C, B) && ws_bytes >= (size_t)C * nsplit_for(S, C, B) * B * 2 * sizeof(double);
   const float* part;
   int psplits;
-  const int rcp = take_or_flush_pending(x, sB, B, C, S, st, reg_form, &part, &psplits);
+  const int rcp = take_or_flush_pending(x, sB, B, C, S, st, reg_form || two_pass, &part, &psplits);
   if (rcp != CRN_OK) return rcp;
   if (reg_form) {
     const bool with_tail = tail && vec_ok(S, {tail->r ? tail->sBr : 0, tail->y_pre ? tail->sBpre : 0, tail->y ? tail->sBy : 0},
@@ -799,7 +852,10 @@ static int bn_stats_impl(const float* x, int B, int C, int64_t S, int64_t sB, in
     if (ws_bytes < (size_t)C * nparts * 2 * sizeof(double)) return CRN_ENOMEM;
     dim3 grid(ns, C, B);
     with_bool(vec_ok(S, {sB}, {x}), [&](auto vec) {
-      hipLaunchKernelGGL(bn_partial_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, S, sB, pre_relu, ws);
+      with_bool(part != nullptr, [&](auto pend) {
+        hipLaunchKernelGGL((bn_partial_kernel<decltype(vec)::value, decltype(pend)::value>), grid, dim3(kThreads), 0, st, x, S, sB,
+                           pre_relu, ws, part, psplits);
+      });
     });
     CRN_CHECK_LAUNCH();
   }
@@ -928,10 +984,13 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
                                           const_cast<float*>(dy), sB_dy, stream);
     if (rch != CRN_OK) return rch;
   }
-  // a split-K convolution (a data gradient) left the partial sums of dy pending: the register kernel adds them up
+  // a split-K convolution (a data gradient) left the partial sums of dy pending: the register kernel adds them up, or the
+  // first pass of the two-pass form, which also stores the sum to dy for the apply pass
   const float* part;
   int psplits;
-  const int rcp = take_or_flush_pending(dy, sB_dy, B, C, S, st, reg_form, &part, &psplits);
+  // (a launch that is about to fail for want of workspace must not swallow the sum)
+  const bool two_pass = !owner_ok && ws_bytes >= (size_t)C * nsplit_for(S, C, B) * B * 2 * sizeof(double);
+  const int rcp = take_or_flush_pending(dy, sB_dy, B, C, S, st, reg_form || two_pass, &part, &psplits);
   if (rcp != CRN_OK) return rcp;
   if (reg_form) {
     with_nv((int64_t)B * S, [&](auto nv) {        // float4 per thread of x and of dy
@@ -959,8 +1018,10 @@ static int bn_bwd_impl(const float* x, int64_t sB_x, const float* dy, int64_t sB
   float* const dsum_det = (dsum && ndsum > 0 && crn_deterministic()) ? dsum : nullptr;
   if (dsum_det) dsum = nullptr;
   with_bool(v, [&](auto vec) {
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<decltype(vec)::value>, grid, dim3(kThreads), 0, st, x, sB_x, dy, sB_dy, S, C,
-                       pre_relu, post_relu, scale, shift, saved, ws, dsum, ndsum);
+    with_bool(part != nullptr, [&](auto pend) {
+      hipLaunchKernelGGL((bn_bwd_partial_kernel<decltype(vec)::value, decltype(pend)::value>), grid, dim3(kThreads), 0, st, x, sB_x,
+                         dy, sB_dy, S, C, pre_relu, post_relu, scale, shift, saved, ws, dsum, ndsum, part, psplits);
+    });
   });
   CRN_CHECK_LAUNCH();
   with_bool(v, [&](auto vec) {

@@ -48,12 +48,17 @@ struct PwGeom {
   int splits, cps;                 // split-K: blockIdx.z = split*B + b, cps input channels per split (multiple
                                    // of 32); partial sums go to the dense scratch y (mode 0), split*B + b as batch
   long long* stamps;               // tuning aid (CRN_PW_STAMPS=1): shader-clock stamps of workgroup 0
+  // PAIR launches (crn_conv1x1_fwd_pair): a second K source.  Channels [0, C1) of the reduction are rows of x / w, channels
+  // [C1, C) rows C - C1.. of x2 / w2 (same S and Npad); C1 % 64 == 0 and cps % 64 == 0, so a chunk never straddles the two
+  const float* x2; const float* w2;
+  int64_t x2sB;
+  int C1;
 };
 
 constexpr int kPwBN = 32;           // output columns of one workgroup (64 x 32 tiles)
 constexpr int kPwTab = 2048;        // channels of one workgroup (its split's range) whose scale / shift are staged in LDS
-// NS = 16-column blocks per workgroup (kPwBN / 16)
-template <int NS>
+// NS = 16-column blocks per workgroup (kPwBN / 16); PAIR: two K sources onto one output (PwGeom), no input transform
+template <int NS, bool PAIR = false>
 __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   constexpr int BM = 64, BN = NS * 16, KC = 64, SA = BM + 16, SB = BN + 16;   // KC 64: half the barriers of KC 32
   constexpr int NRA = KC / 16;
@@ -61,6 +66,7 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   __shared__ __attribute__((aligned(16))) float ldsB[KC * SB];
   crn_kernargs_now(g.x, g.y, g.w, g.bias, g.tr.scale, g.tr.shift, g.tr.pre_relu, g.tr.post_relu, g.B, g.C, g.N, g.Npad,
                    g.S, g.xsB, g.ysB, g.ysC, g.ysP, g.bias_sB, g.mode, g.splits, g.cps);
+  if (PAIR) crn_kernargs_now(g.x2, g.w2, g.x2sB, g.C1);
   const long long t_entry = (long long)__builtin_amdgcn_s_memtime();
   const long long r_entry = (long long)__builtin_amdgcn_s_memrealtime();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -93,19 +99,26 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
   constexpr int NL = NRA + NRB;                      // loads per thread and chunk
   const crn_rsrc xrs = crnk::make_rsrc(xb);
   const crn_rsrc wrs = crnk::make_rsrc(g.w);
+  // PAIR: the descriptors of the second source, built once; which pair a chunk reads is uniform (c0 and C1 are scalars)
+  const crn_rsrc x2rs = crnk::make_rsrc(PAIR ? g.x2 + (int64_t)b * g.x2sB : xb);
+  const crn_rsrc w2rs = crnk::make_rsrc(PAIR ? g.w2 : g.w);
   f32x4 ra[2][NRA], rb[2][NRB];
   auto issue = [&](int c0, f32x4 (&pa_)[NRA], f32x4 (&pb_)[NRB]) {
+    const bool second = PAIR && c0 >= g.C1;
+    const crn_rsrc ars = second ? x2rs : xrs;
+    const crn_rsrc brs = second ? w2rs : wrs;
+    const int cs = second ? g.C1 : 0;                  // first row of the chunk's source in the concatenated K
 #pragma unroll
     for (int q = 0; q < NRA; ++q) {
       const int c_a = c0 + ka + q * 16;
-      const unsigned off = (a_ok && c_a < cend) ? (unsigned)(c_a * g.S + m0 + ca) * 4u : kOOBo;
-      crnk::crn_bload4(pa_[q], xrs, off);
+      const unsigned off = (a_ok && c_a < cend) ? (unsigned)((c_a - cs) * g.S + m0 + ca) * 4u : kOOBo;
+      crnk::crn_bload4(pa_[q], ars, off);
     }
 #pragma unroll
     for (int q = 0; q < NRB; ++q) {
       const int c_b = c0 + kb + q * BROWS;
-      const unsigned off = (b_ok && c_b < cend) ? (unsigned)(c_b * g.Npad + n0 + cb) * 4u : kOOBo;
-      crnk::crn_bload4(pb_[q], wrs, off);
+      const unsigned off = (b_ok && c_b < cend) ? (unsigned)((c_b - cs) * g.Npad + n0 + cb) * 4u : kOOBo;
+      crnk::crn_bload4(pb_[q], brs, off);
     }
   };
   auto wait_slot = [&](f32x4 (&pa_)[NRA], f32x4 (&pb_)[NRB]) {   // the other slot's NL loads were issued later
@@ -449,6 +462,15 @@ bool fwd_vec_store(const crnView& y, int mw, int mode) {
          (y.sC & 3) == 0 && (((uintptr_t)y.base) & 15) == 0 && y.chan_off == nullptr && mode != 2;
 }
 
+// K splits a pointwise launch over C channels asks for when its output grid has `blocks` workgroups (1: none): long
+// reductions over few positions split their channels to fill the chip.  One copy for crn_conv_fwd's 1x1 path and
+// crn_conv1x1_fwd_pair; each rounds the channels per split to its own chunk.
+int pw_auto_splits(int C, int64_t blocks) {
+  constexpr int pw_blocks = 256, pw_fill = 512, pw_minc = 128;
+  if (blocks >= pw_blocks || C < 2 * pw_minc) return 1;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(C / pw_minc, 16), crn_cdiv(pw_fill, blocks)));
+}
+
 int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int Npad, const crnView* y,
                int kd, int kh, int kw, int pd, int ph, int pw, int splits, FwdSel* s) {
   *s = FwdSel{};
@@ -473,10 +495,9 @@ int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int N
     // split the channels over blocks, partial sums to the split-K scratch, one reduction launch
     // (64-column tiles were measured equal to 32-column ones on the whole step, 10.07 vs 10.04 ms: these launches are
     // latency bound, not operand-traffic bound)
-    constexpr int pw_blocks = 256, pw_fill = 512, pw_minc = 128;
     const int64_t blocks = crn_cdiv(Sx, 64) * crn_cdiv(y->C, kPwBN) * (int64_t)x->B;
-    if (splits < 1 && blocks < pw_blocks && x->C >= 2 * pw_minc) {
-      int sp = (int)std::min<int64_t>(std::min<int64_t>(x->C / pw_minc, 16), crn_cdiv(pw_fill, blocks));
+    if (splits < 1) {
+      int sp = pw_auto_splits(x->C, blocks);
       if (sp > 1) {
         const int cps = (crn_cdiv(x->C, sp) + 31) & ~31;
         sp = crn_cdiv(x->C, cps);
@@ -676,6 +697,48 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   // pointwise and the split-bf16 paths: the encoder's fp32 3x3 layers and decoder stage 2 lose their reduction launch
   if (rc == CRN_OK && g.mode == 3) rc = crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st);
   return rc;
+}
+
+// Two pointwise convolutions onto one output in one launch: y (+)= w1^T x1 + w2^T x2, the reduction running over the
+// channels of x1 followed by those of x2 (pointwise_fwd_kernel<., true>).  The data gradients of a down-sampling bottleneck
+// (op_a and the shortcut, resnet50.py:94-107) are such a pair.
+extern "C" int crn_conv1x1_fwd_pair(const crnView* x1, const float* w1, const crnView* x2, const float* w2, int Npad,
+                                    const crnView* y, int splits, int accumulate, crnStream stream) {
+  if (!x1 || !x2 || !w1 || !w2 || !y || Npad <= 0 || (Npad & 15) || y->C > Npad || y->C < 1) return CRN_EINVAL;
+  if (!plain_view(*x1) || !plain_view(*x2) || !plain_view(*y)) return CRN_EINVAL;
+  const int64_t S = (int64_t)x1->D * x1->H * x1->W;
+  if ((int64_t)x2->D * x2->H * x2->W != S || (int64_t)y->D * y->H * y->W != S || (S & 3)) return CRN_EINVAL;
+  if (x1->B < 1 || x2->B != x1->B || y->B != x1->B || x1->C < 1 || (x1->C & 63) || x2->C < 1) return CRN_EINVAL;
+  if ((((uintptr_t)w1) & 15) || (((uintptr_t)w2) & 15)) return CRN_EINVAL;
+  constexpr int64_t kRange = (int64_t)1 << 31;                   // buffer offsets of the hand-tracked loads
+  const int C1 = x1->C, C = C1 + x2->C;
+  if ((int64_t)std::max(C1, x2->C) * std::max<int64_t>(S, Npad) * 4 >= kRange || splits < 0) return CRN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  int rcf;
+  const bool armed = crn_splitk_begin(st, &rcf);
+  if (rcf != CRN_OK) return rcf;
+  // the split rule of the single launch (fwd_select) on the concatenated K; splits > 1: as asked.  cps a multiple of 64
+  int sp = splits;
+  if (sp == 0) sp = pw_auto_splits(C, crn_cdiv(S, 64) * crn_cdiv(y->C, kPwBN) * (int64_t)y->B);
+  sp = std::max(1, std::min(sp, C / 64));
+  int cps = (crn_cdiv(C, sp) + 63) & ~63;
+  sp = crn_cdiv(C, cps);
+  PwGeom p{};
+  p.x = x1->base; p.w = w1; p.x2 = x2->base; p.w2 = w2; p.y = y->base;
+  p.tr = crnInTransform{nullptr, nullptr, 0, 0};
+  p.B = y->B; p.C = C; p.C1 = C1; p.N = y->C; p.Npad = Npad; p.S = (int)S;
+  p.xsB = x1->sB; p.x2sB = x2->sB; p.ysB = y->sB; p.ysC = y->sC; p.ysP = 1; p.mode = accumulate ? 1 : 0;
+  p.splits = 1; p.cps = (C + 63) & ~63;
+  const int64_t ytot = (int64_t)y->B * y->C * S;
+  float* scratch = nullptr;
+  if (sp > 1 && (scratch = crn_splitk_scratch((size_t)sp * ytot, st)) != nullptr) {
+    p.splits = sp; p.cps = cps;
+    p.y = scratch; p.ysB = (int64_t)y->C * S; p.ysC = S; p.mode = 0;
+  }
+  dim3 grid((unsigned)crn_cdiv(S, 64), (unsigned)crn_cdiv(y->C, kPwBN), (unsigned)(y->B * p.splits));
+  hipLaunchKernelGGL((pointwise_fwd_kernel<kPwBN / 16, true>), grid, dim3(256), 0, st, p);
+  CRN_CHECK_LAUNCH();
+  return p.splits > 1 ? crn_splitk_finish(*y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
 }
 
 namespace {

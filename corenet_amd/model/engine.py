@@ -939,6 +939,17 @@ class Plan:
         dy, None, cv.wd, g.npad, None, 0, dx, g.window, g.pad_lo, 0, accumulate, boxes=(g.n_boxes, g.c_boxes),
         math=self._math(cv, "dgrad"), wslab=cv.wop_d if cv.wop_kind == "slab" else None))
 
+  def _dgrad_pair(self, c1: Conv, dy1: V.View, c2: Conv, dy2: V.View, dx: V.View) -> bool:
+    """dx = dgrad(c1)(dy1) + dgrad(c2)(dy2) of two 1x1 layers with the same input in one launch.  False: nothing was launched
+    (a backend without the entry, a layer that is not on the fp32 pointwise kernel, a shape the entry rejects)."""
+    be = self.be
+    g1, g2 = c1.dgrad, c2.dgrad
+    if (getattr(be, "conv1x1_pair", None) is None or self._math(c1, "dgrad") != "fp32" or self._math(c2, "dgrad") != "fp32"
+        or any(tuple(g.window) != (1, 1, 1) or any(g.pad_lo) for g in (g1, g2)) or g1.npad != g2.npad):
+      return False
+    return self._timed("dgrad " + c1.name + " + " + c2.name,
+                       lambda: be.conv1x1_pair(dy1, c1.wd, dy2, c2.wd, g1.npad, dx))
+
   def _dgrad_bn_bwd(self, cv: Conv, dy: V.View, g: t.Tensor, x: t.Tensor, Cn: int, S: int, b, dx: t.Tensor, cprev: Conv) -> bool:
     """Data gradient g of decoder conv `cv` + backward of the BatchRenorm `b` in front of it (input x, output gradient g,
     input gradient dx; dsum = the bias gradient of the conv `cprev` that produced x).  True: the norm's backward is done
@@ -1497,8 +1508,11 @@ class Plan:
       self._wgrad(csn, xin, None, self.vw(blk.gys))
       gin = blk.gin
       gv = self.vw(blk.gxs) if blk.stride == 2 else self.vw(gin)
-      self._dgrad(ca, self.vw(blk.gya), gv)
-      self._dgrad(csn, self.vw(blk.gys), gv, accumulate=True)
+      # gv = Wa^T gya + Ws^T gys: one GEMM over the concatenated channels, one launch (crn_conv1x1_fwd_pair) where both
+      # layers are on the fp32 pointwise kernel and the entry covers the shape; two launches otherwise
+      if not self._dgrad_pair(ca, self.vw(blk.gya), csn, self.vw(blk.gys), gv):
+        self._dgrad(ca, self.vw(blk.gya), gv)
+        self._dgrad(csn, self.vw(blk.gys), gv, accumulate=True)
       if blk.stride == 2:
         if hasattr(be, "bn_bwd_head"):
           self._g_compact = blk.gxs                   # expanded by its reader: the norm backward at the head of the block in front

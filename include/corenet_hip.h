@@ -76,6 +76,20 @@ int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const float* w, int
                  int splits, int accumulate /* y += result instead of y = result */,
                  const crnTapBoxes* boxes /* may be NULL */, crnStream stream);
 
+/* Two 1x1x1 convolutions onto one output in ONE launch of the pointwise kernel:
+ *   y[b,n,o] (+)= sum_{c < C1} x1[b,c,o] * w1[c*Npad + n] + sum_{c < C2} x2[b,c,o] * w2[c*Npad + n]
+ * (the data gradients of op_a and of the shortcut of a down-sampling bottleneck, resnet50.py:94-107, are such a pair).
+ * The reduction runs over the channels of x1, then those of x2, so the result differs from two crn_conv_fwd calls (the
+ * second accumulating) by fp32 summation order only.  No input transform, no bias.
+ * Covered: x1, x2 and y plain views (every sample a dense [C][D][H][W] block, 16-byte aligned base, batch stride a
+ * multiple of 4) of the same B and the same S = D*H*W, S % 4 == 0, x1->C % 64 == 0, one Npad (multiple of 16, >= y->C)
+ * for both weight matrices, 16-byte aligned weights; CRN_EINVAL otherwise, before anything is written or launched and
+ * without consuming the arming of crn_splitk_defer.
+ * splits: 0 = the rule of crn_conv_fwd's 1x1 path on C1 + C2 channels, 1 = none, n = at most n.  A split launch follows
+ * the split-K protocol of crn_conv_fwd (crn_splitk_defer below): one pending sum or one reduction launch.          */
+int crn_conv1x1_fwd_pair(const crnView* x1, const float* w1, const crnView* x2, const float* w2, int Npad,
+                         const crnView* y, int splits, int accumulate /* y += result */, crnStream stream);
+
 /* Which kernel a crn_conv_fwd / crn_conv_wgrad call with these arguments gets: the selection the launch itself runs,
  * as host arithmetic on extents, strides and alignment.  No HIP call is made and no pointer is followed except the view,
  * transform and box structs themselves (base, chan_off, w, dw, scale are only tested for NULL and alignment), so a
@@ -169,10 +183,12 @@ int crn_conv_fwd_bf3_slabs_stats(const crnView* x, const crnInTransform* tr, con
  * the 1x1 path of crn_conv_fwd), the following shortcut: if that call splits and does not accumulate, the sum is
  * left pending (recorded per host thread, together with the stream and device the convolution ran on) and a
  * crn_batch_renorm_stats (x = the conv's output) or crn_batch_renorm_bwd (dy = the conv's output) that follows ON THE
- * SAME STREAM adds the partial sums up while it loads them (stats also stores the sum to x; bwd does not write dy: it
- * is its only reader).  EVERY other entry point of this library that takes a stream -- and a BatchRenorm call on
- * another tensor or another stream -- first completes a pending sum with an ordinary reduction launch on the
- * convolution's own stream, so arming is always safe for callers that reach the tensor through this library on that
+ * SAME STREAM adds the partial sums up while it loads them (stats also stores the sum to x; bwd is dy's only reader: its
+ * register-resident form does not write dy, its two-pass form stores the sum to dy in the first pass for the second; the
+ * one-workgroup-per-channel forms that read their input twice get the sum from a reduction launch first).  Results are
+ * bit-identical to reduction + call: the splits are added in the reduction's order.  EVERY other entry point of this
+ * library that takes a stream -- and a BatchRenorm call on another tensor or another stream -- first completes a
+ * pending sum with an ordinary reduction launch on the convolution's own stream, so arming is always safe for callers that reach the tensor through this library on that
  * host thread; it only pays when the BatchRenorm call follows directly (resnet50.py:62-69: every conv of the encoder is
  * followed by its norm; in backward every data gradient feeds the norm's backward).  A caller that hands y to code
  * OUTSIDE the library (a torch op, a memcpy) or to another host thread while a sum may be pending must not arm.   */
