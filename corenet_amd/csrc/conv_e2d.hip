@@ -47,9 +47,8 @@ struct E2dGeom {
   int nchunks, chunks_per_split;
   int tab;                // entries of the scale / shift tables in LDS (channels of one split)
   int mode;               // 0 store, 1 accumulate (read-modify-write), 3 split-K partial sums [split][b][n][pos]
-  int dbg;                // tools build only (CRN_E2D_DBG=16): shader-clock stamps of workgroup 0 / wave 0 into stamps[]
-                          // (crn_e2d_debug_stamps); zero in the product library
-  long long* stamps;
+  long long* stamps;      // tools build only (CRN_E2D_DBG=16): shader-clock stamps of workgroup 0 / wave 0
+                          // (crn_e2d_debug_stamps); null in the product library
 };
 
 // crn_bf3_operands: one row of the layer table = (first float of the packed [Cin][T][Npad] weights, first 32-byte
@@ -68,43 +67,34 @@ __global__ __launch_bounds__(256) void bf3_operands_kernel(const float* packed, 
   }
   const long long* d = desc + lo * kOpFields;
   const int Cin = (int)d[2], T = (int)d[3], Npad = (int)d[4];
+  const long long e = ((long long)blockIdx.x - d[5]) * 256 + threadIdx.x;     // entry of the layer
+  float v[8];
   if (d[6] > 0) {                                     // slab order: entry ((chunk*kd + zd)*TP + tp)*Npad + n
     const int KHW = (int)d[6], kd = T / KHW, TP = (KHW + 3) & ~3;
-    const long long entries = (long long)((Cin + 7) >> 3) * kd * TP * Npad;
-    const long long e = ((long long)blockIdx.x - d[5]) * 256 + threadIdx.x;
-    if (e >= entries) return;
+    if (e >= (long long)((Cin + 7) >> 3) * kd * TP * Npad) return;
     const int n = (int)(e % Npad);
     long long r = e / Npad;
     const int tp = (int)(r % TP); r /= TP;
     const int zd = (int)(r % kd);
     const int chunk = (int)(r / kd);
-    float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = chunk * 8 + j;
       v[j] = (c < Cin && tp < KHW) ? packed[d[0] + ((long long)c * T + zd * KHW + tp) * Npad + n] : 0.f;
     }
-    bf16x8 h, l;
-    split8(v, h, l);
-    bf16x8* dst = reinterpret_cast<bf16x8*>(out + (d[1] + e) * 32);
-    dst[0] = h;
-    dst[1] = l;
-    return;
-  }
-  const int ntn = Npad >> 4;
-  const long long entries = (long long)(Cin >> 5) * T * ntn * 64;
-  const long long e = ((long long)blockIdx.x - d[5]) * 256 + threadIdx.x;
-  if (e >= entries) return;
-  const int lane = (int)(e & 63);
-  const long long rest = e >> 6;
-  const int ntile = (int)(rest % ntn);
-  const int kg = (int)(rest / ntn);
-  const int cbg = kg / T, t = kg - cbg * T;
-  const int kk = lane >> 4, i16 = lane & 15;
-  const float* src = packed + d[0] + ((long long)(cbg * 32 + kk * 8) * T + t) * Npad + ntile * 16 + i16;
-  float v[8];
+  } else {                                            // operand blocks of the encoder engine
+    const int ntn = Npad >> 4;
+    if (e >= (long long)(Cin >> 5) * T * ntn * 64) return;
+    const int lane = (int)(e & 63);
+    const long long rest = e >> 6;
+    const int ntile = (int)(rest % ntn);
+    const int kg = (int)(rest / ntn);
+    const int cbg = kg / T, t = kg - cbg * T;
+    const int kk = lane >> 4, i16 = lane & 15;
+    const float* src = packed + d[0] + ((long long)(cbg * 32 + kk * 8) * T + t) * Npad + ntile * 16 + i16;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = src[(long long)j * T * Npad];
+    for (int j = 0; j < 8; ++j) v[j] = src[(long long)j * T * Npad];
+  }
   bf16x8 h, l;
   split8(v, h, l);
   bf16x8* dst = reinterpret_cast<bf16x8*>(out + (d[1] + e) * 32);
@@ -114,9 +104,43 @@ __global__ __launch_bounds__(256) void bf3_operands_kernel(const float* packed, 
 
 constexpr unsigned kOOB = 0x80000000u;     // buffer offset outside the 2 GiB range of make_rsrc: the load returns 0
 
-template <int N>
-__device__ __forceinline__ void wait_vm(f32x4& a, f32x4& b) {
+// The waits for the hand-issued loads (crn_bload*, invisible to the compiler's waitcnt pass): s_waitcnt vmcnt(N) -- at most N
+// loads still in flight -- with the destination registers as in-out operands.  The operands are what keeps the compiler from
+// reading a register above the wait, and from giving it to another value while its load is in flight.
+template <int N, typename R>
+__device__ __forceinline__ void wait_vm(R& a, R& b) {
   asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
+}
+// ... for the patch registers of conv_e2d_kernel, of which each instance has one set: pf (3x3) or pv (1x1)
+template <int N, int NF, int NV>
+__device__ __forceinline__ void wait_patch(float (&pf)[NF], f32x4 (&pv)[NV]) {
+  if constexpr (NF > 1) {
+#pragma unroll
+    for (int i = 0; i < NF; i += 8)
+      asm volatile("s_waitcnt vmcnt(%8)"
+                   : "+v"(pf[i]), "+v"(pf[i + 1]), "+v"(pf[i + 2]), "+v"(pf[i + 3]), "+v"(pf[i + 4]), "+v"(pf[i + 5]),
+                     "+v"(pf[i + 6]), "+v"(pf[i + 7])
+                   : "n"(N));
+  } else {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(pv[i]) : "n"(N));
+  }
+}
+
+// Keeps two MFMA operands live past the MFMAs that read them.  An operand that dies AT an MFMA may hand its registers to that
+// MFMA's result; the accumulator then moves from register to register, and an MFMA that reads its SrcC from other registers than
+// it writes wants nine wait states behind the one before (tools/check_mfma_hazards.py, which tests/test_host_cpu.py runs on
+// this file's object) where accumulating in place wants none.
+template <typename R>
+__device__ __forceinline__ void keep_live(const R& a, const R& b) { asm volatile("" ::"v"(a), "v"(b)); }
+
+// The fused in-transform of one element (BatchRenorm-apply and the ReLUs around it): max, *, +, max in this order, never
+// contracted.  Padding and channels past C are not x: the callers keep them zero.
+__device__ __forceinline__ float in_transform(float a, int pre_relu, float scale, float shift, int post_relu) {
+  if (pre_relu) a = fmaxf(a, 0.f);
+  a = a * scale + shift;
+  if (post_relu) a = fmaxf(a, 0.f);
+  return a;
 }
 
 // T = window taps (9: 3x3, 1: 1x1); CB = 32-channel blocks per chunk; TW = tile width (3x3: 16 or 8, tile = 64/TW
@@ -142,9 +166,8 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
   const long long t_entry = (long long)__builtin_amdgcn_s_memtime();
   crn_kernargs_now(g.x.base, g.x.B, g.x.C, g.x.H, g.x.W, g.x.sB, g.x.sC, g.x.sH, g.y.base, g.y.C, g.y.sB, g.y.sC, g.y.sH,
                g.tr.scale, g.tr.shift, g.tr.pre_relu, g.tr.post_relu, g.wop, g.bias, g.bias_sB, g.ntn, g.nblk, g.ph,
-               g.pw, g.tilesH, g.tilesW, g.nchunks, g.chunks_per_split, g.tab, g.mode, g.dbg, g.stamps, gridDim.x);
-  if (g.dbg & 1) return;
-  const bool stamp = (g.dbg & 16) && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0;
+               g.pw, g.tilesH, g.tilesW, g.nchunks, g.chunks_per_split, g.tab, g.mode, g.stamps, gridDim.x);
+  const bool stamp = g.stamps && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0;
   auto mark = [&](int i) { if (stamp) g.stamps[i] = (long long)__builtin_amdgcn_s_memtime() - t_entry; };
   mark(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -207,13 +230,7 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
   };
   auto transform8 = [&](float (&v)[8], int ctab) {     // ctab = table index of the first of the 8 channels
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float a = v[j];
-      if (g.tr.pre_relu) a = fmaxf(a, 0.f);
-      a = a * tscale[ctab + j] + tshift[ctab + j];
-      if (g.tr.post_relu) a = fmaxf(a, 0.f);
-      v[j] = a;
-    }
+    for (int j = 0; j < 8; ++j) v[j] = in_transform(v[j], g.tr.pre_relu, tscale[ctab + j], tshift[ctab + j], g.tr.post_relu);
   };
   auto patch_commit = [&](int chunk, bf16x8* Ahi, bf16x8* Alo) {
     if constexpr (T == 9) {
@@ -247,19 +264,6 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
         Ahi[(wave * 4 + kk8) * PS + row] = h;
         Alo[(wave * 4 + kk8) * PS + row] = l;
       }
-    }
-  };
-  auto patch_wait = [&]() {                            // the B loads of the next chunk (2 per K step) were issued later
-    if constexpr (T == 9) {
-#pragma unroll
-      for (int i = 0; i < 16; i += 8)
-        asm volatile("s_waitcnt vmcnt(%8)"
-                     : "+v"(pf[i]), "+v"(pf[i + 1]), "+v"(pf[i + 2]), "+v"(pf[i + 3]), "+v"(pf[i + 4]), "+v"(pf[i + 5]),
-                       "+v"(pf[i + 6]), "+v"(pf[i + 7])
-                     : "n"(2 * KS));
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(pv[i]) : "n"(2 * KS));
     }
   };
 
@@ -305,23 +309,14 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
         tscale[c] = g.tr.scale[cc];
         tshift[c] = g.tr.shift[cc];
       }
-    if constexpr (T == 9) {
-#pragma unroll
-      for (int i = 0; i < 16; i += 8)
-        asm volatile("s_waitcnt vmcnt(0)"
-                     : "+v"(pf[i]), "+v"(pf[i + 1]), "+v"(pf[i + 2]), "+v"(pf[i + 3]), "+v"(pf[i + 4]), "+v"(pf[i + 5]),
-                       "+v"(pf[i + 6]), "+v"(pf[i + 7]));
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pv[i]));
-    }
+    wait_patch<0>(pf, pv);
     mark(2);
     __syncthreads();                                   // the tables
     patch_commit(cbeg, Abuf, Abuf + PLANE);
     __syncthreads();
     mark(3);
 
-    for (int chunk = cbeg; chunk < ((g.dbg & 2) ? cbeg : cend); ++chunk) {
+    for (int chunk = cbeg; chunk < cend; ++chunk) {
       const int buf = (chunk - cbeg) & 1;
       const bf16x8* Ahi = Abuf + buf * 2 * PLANE;
       const bf16x8* Alo = Ahi + PLANE;
@@ -338,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
         const bf16x8 wh = __builtin_bit_cast(bf16x8, bh[s]);
         const bf16x8 wl = __builtin_bit_cast(bf16x8, bl[s]);
         bf16x8 nh[4], nl[4];
-        if (s + 1 < KS && !(g.dbg & 32)) {
+        if (s + 1 < KS) {
           const int cbl = (s + 1) / T, t = (s + 1) % T;
           const int toff = cbl * 4 * PS + (t / KW) * PW + (t % KW);
 #pragma unroll
@@ -346,22 +341,23 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
         }
         __builtin_amdgcn_sched_barrier(0);             // (the scheduler would sink the reads below the MFMAs)
         // (1x1: channel blocks past Cin are zeros on both sides -- out-of-range loads -- and are multiplied anyway)
-        if (!(g.dbg & 4)) {
-#pragma unroll
-        for (int ms = 0; ms < 4; ++ms) acc[ms] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ms], wh, acc[ms], 0, 0, 0);
+        // hi*lo first (the order the scheduler gave these twelve before, too): the two products of an acx accumulator are
+        // then eight MFMAs apart, those of acc a whole K step
 #pragma unroll
         for (int ms = 0; ms < 4; ++ms) acx[ms] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ms], wl, acx[ms], 0, 0, 0);
 #pragma unroll
+        for (int ms = 0; ms < 4; ++ms) acc[ms] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ms], wh, acc[ms], 0, 0, 0);
+#pragma unroll
         for (int ms = 0; ms < 4; ++ms) acx[ms] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[ms], wh, acx[ms], 0, 0, 0);
-        }
-        b_issue(chunk + 1, s, (g.dbg & 64) ? kOOB : step_oob(chunk + 1, s), bh[s], bl[s]);
-        if (s + 1 < KS && !(g.dbg & 32)) {
+        keep_live(bh[s], bl[s]);
+        b_issue(chunk + 1, s, step_oob(chunk + 1, s), bh[s], bl[s]);
+        if (s + 1 < KS) {
 #pragma unroll
           for (int ms = 0; ms < 4; ++ms) { ah[ms] = nh[ms]; al[ms] = nl[ms]; }
         }
       }
       mark(4 + 2 * (chunk - cbeg));
-      patch_wait();
+      wait_patch<2 * KS>(pf, pv);                      // the B loads of the next chunk (2 per K step) were issued later
       mark(5 + 2 * (chunk - cbeg));
       if (chunk + 1 < cend) {
         bf16x8* Nhi = Abuf + (buf ^ 1) * 2 * PLANE;
@@ -374,24 +370,15 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
   // the loads issued for "the chunk after the last" (out of range: zeros) still target these registers: keep them
   // allocated until the loads have landed
 #pragma unroll
-  for (int s = 0; s < KS; ++s) asm volatile("s_waitcnt vmcnt(0)" : "+v"(bh[s]), "+v"(bl[s]));
-  if constexpr (T == 9) {
-#pragma unroll
-    for (int i = 0; i < 16; i += 8)
-      asm volatile("s_waitcnt vmcnt(0)"
-                   : "+v"(pf[i]), "+v"(pf[i + 1]), "+v"(pf[i + 2]), "+v"(pf[i + 3]), "+v"(pf[i + 4]), "+v"(pf[i + 5]),
-                     "+v"(pf[i + 6]), "+v"(pf[i + 7]));
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pv[i]));
-  }
+  for (int s = 0; s < KS; ++s) wait_vm<0>(bh[s], bl[s]);
+  wait_patch<0>(pf, pv);
 
   mark(30);
 #pragma unroll
   for (int ms = 0; ms < 4; ++ms) acc[ms] += acx[ms];
   // ---- epilogue: D row = 4*kk + r (position of the M tile), col = i16 (output column) ----
   const int n = ntile * 16 + i16;
-  if (n >= g.y.C || (g.dbg & 8)) return;
+  if (n >= g.y.C) return;
   const float bsv = (g.bias && split == 0) ? g.bias[(int64_t)b * g.bias_sB + n] : 0.f;
   float* yb = g.y.base + (int64_t)(g.mode == 3 ? split * g.x.B + b : b) * g.y.sB + (int64_t)n * g.y.sC;
   if constexpr (T == 9) {
@@ -424,16 +411,80 @@ __global__ __launch_bounds__(256, 2) void conv_e2d_kernel(E2dGeom g) {
 // Workgroup = 4 waves on one 64 (c) x 32 (n) tile, each wave every fourth K step of the workgroup's K range (the 36
 // launches per step have K = 256 ... 16384 positions); the four partial tiles meet in LDS and go to dw with
 // fire-and-forget atomics (dw is zeroed by the caller or by zero_first, like crn_conv_wgrad).
-struct Wg1Geom {
+// Both kernels below are this GEMM and differ in how the A rows are produced; the steps they share come first.
+struct WgGeom {
   const float* x; const float* dy; float* dw;
   const float* scale; const float* shift;
   int pre_relu, post_relu;
   long long xsB, dsB;      // sample strides
   int C, N, Npad, S;       // S = positions per sample (multiple of 32)
+  int H, W;                // 3x3 only
   int ksteps, ksteps_per_block;   // K steps of 32 positions: B * S / 32 in total
 };
 
-__global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(Wg1Geom g) {
+// byte offset of row r (a channel of x, a column of dy) in its sample; rows past the tensor are loaded as zeros
+__device__ __forceinline__ unsigned wg_row(int r, int rows, int S) { return r < rows ? (unsigned)r * (unsigned)S * 4u : kOOB; }
+
+// the lane's 8 consecutive K of two dy rows (column tiles n0, n0 + 16), raw: two 16-byte loads per row
+__device__ __forceinline__ void wg_dy_issue(f32x4 (&rb)[2][2], const crn_rsrc& drs, const unsigned (&brow)[2], unsigned koff,
+                                            unsigned oob) {
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) {
+    crn_bload4(rb[nt][0], drs, (brow[nt] + koff) | oob);
+    crn_bload4(rb[nt][1], drs, (brow[nt] + koff + 16u) | oob);
+  }
+}
+
+// two raw 16-byte loads = 8 consecutive K of one row -> its MFMA operand registers
+__device__ __forceinline__ void wg_split(const f32x4 (&r)[2], bf16x8& hi, bf16x8& lo) {
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = r[j >> 2][j & 3];
+  split8(v, hi, lo);
+}
+
+// one K step on MT row tiles x 2 column tiles.  Per accumulator hi*hi, then hi*lo, then lo*hi; MT independent MFMAs in a row
+template <int MT>
+__device__ __forceinline__ void wg_mfma(f32x4 (&acc)[MT][2], const bf16x8 (&ah)[MT], const bf16x8 (&al)[MT], const bf16x8 (&bh)[2],
+                                        const bf16x8 (&bl)[2]) {
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
+  }
+}
+
+// The four waves' partial tiles -> LDS -> one sum per element (waves 0, 1, 2, 3 in this order) -> dw, fire-and-forget atomics.
+// Wave w sums tiles w*MT/2 .. +MT/2-1 of the 2*MT.  D row = 4*kk + r, col = i16 (output column); dw_row(mt, row) = the row of dw
+// that row `row` of row tile mt is, or -1 past the tensor.
+template <int MT, typename F>
+__device__ __forceinline__ void wg_flush(f32x4 (&red)[4][2 * MT][64], const f32x4 (&acc)[MT][2], int wave, int lane, int n0,
+                                         const WgGeom& g, F dw_row) {
+  const int i16 = lane & 15, kk = lane >> 4;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) red[wave][mt * 2 + nt][lane] = acc[mt][nt];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < MT / 2; ++q) {
+    const int tile = wave * (MT / 2) + q;
+    const f32x4 v = red[0][tile][lane] + red[1][tile][lane] + red[2][tile][lane] + red[3][tile][lane];
+    const int mt = tile >> 1, nt = tile & 1;
+    const int n = n0 + 16 * nt + i16;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = dw_row(mt, 4 * kk + r);
+      if (row >= 0 && n < g.N) atomicAdd(g.dw + (long long)row * g.Npad + n, v[r]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(WgGeom g) {
   crn_kernargs_now(g.x, g.dy, g.dw, g.scale, g.shift, g.pre_relu, g.post_relu, g.xsB, g.dsB, g.C, g.N, g.Npad, g.S,
                    g.ksteps, g.ksteps_per_block);
   __shared__ __attribute__((aligned(16))) f32x4 red[4][8][64];          // [wave][tile][lane]: 32 KiB
@@ -442,27 +493,19 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(Wg1Geom g) {
   const int i16 = lane & 15, kk = lane >> 4;
   const int c0 = blockIdx.x * 64, n0 = blockIdx.y * 32;
   const int kbeg = blockIdx.z * g.ksteps_per_block, kend = min(kbeg + g.ksteps_per_block, g.ksteps);
-  // rows of this lane: 4 x channels (A), 2 x output columns (B); rows past the tensors are loaded as zeros
-  unsigned arow[4], brow[2];
+  // rows of this lane: 4 x channels (A), 2 x output columns (B)
+  unsigned arow[4];
+  const unsigned brow[2] = {wg_row(n0 + i16, g.N, g.S), wg_row(n0 + 16 + i16, g.N, g.S)};
   float sc[4], sh[4];
   const bool has_tr = g.scale != nullptr;
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
     const int c = c0 + 16 * mt + i16;
-    arow[mt] = c < g.C ? (unsigned)c * (unsigned)g.S * 4u : kOOB;
+    arow[mt] = wg_row(c, g.C, g.S);
     sc[mt] = (has_tr && c < g.C) ? g.scale[c] : 1.f;
     sh[mt] = (has_tr && c < g.C) ? g.shift[c] : 0.f;
   }
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int n = n0 + 16 * nt + i16;
-    brow[nt] = n < g.N ? (unsigned)n * (unsigned)g.S * 4u : kOOB;
-  }
-  f32x4 acc[4][2];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[4][2] = {};
 
   f32x4 ra[4][2], rb[2][2];                             // raw fp32 operands of one K step
   auto issue = [&](int step) {
@@ -476,17 +519,13 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(Wg1Geom g) {
       crn_bload4(ra[mt][0], xrs, (arow[mt] + koff) | oob);
       crn_bload4(ra[mt][1], xrs, (arow[mt] + koff + 16u) | oob);
     }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      crn_bload4(rb[nt][0], drs, (brow[nt] + koff) | oob);
-      crn_bload4(rb[nt][1], drs, (brow[nt] + koff + 16u) | oob);
-    }
+    wg_dy_issue(rb, drs, brow, koff, oob);
   };
   auto wait_all = [&]() {
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[mt][0]), "+v"(ra[mt][1]));
+    for (int mt = 0; mt < 4; ++mt) wait_vm<0>(ra[mt][0], ra[mt][1]);
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) asm volatile("s_waitcnt vmcnt(0)" : "+v"(rb[nt][0]), "+v"(rb[nt][1]));
+    for (int nt = 0; nt < 2; ++nt) wait_vm<0>(rb[nt][0], rb[nt][1]);
   };
   int step = kbeg + wave;
   issue(step);
@@ -498,13 +537,8 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(Wg1Geom g) {
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float a = ra[mt][j >> 2][j & 3];
-        if (has_tr) {
-          if (g.pre_relu) a = fmaxf(a, 0.f);
-          a = a * sc[mt] + sh[mt];
-          if (g.post_relu) a = fmaxf(a, 0.f);
-        }
-        v[j] = a;
+        const float a = ra[mt][j >> 2][j & 3];
+        v[j] = has_tr ? in_transform(a, g.pre_relu, sc[mt], sh[mt], g.post_relu) : a;
       }
       if (has_tr && arow[mt] == kOOB) {
 #pragma unroll
@@ -513,42 +547,15 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(Wg1Geom g) {
       split8(v, ah[mt], al[mt]);
     }
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = rb[nt][j >> 2][j & 3];
-      split8(v, bh[nt], bl[nt]);
-    }
+    for (int nt = 0; nt < 2; ++nt) wg_split(rb[nt], bh[nt], bl[nt]);
     issue(step + 4);                                    // the raw registers are free again: next K step of this wave
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-    }
+    wg_mfma<4>(acc, ah, al, bh, bl);
   }
   wait_all();                                           // the loads issued for "the step after the last" (zeros)
-  // the four partial tiles -> LDS -> one sum per element -> dw.  D row = 4*kk + r (channel), col = i16 (column)
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) red[wave][mt * 2 + nt][lane] = acc[mt][nt];
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int tile = wave * 2 + q;                      // wave w sums tiles 2w, 2w + 1
-    const f32x4 v = red[0][tile][lane] + red[1][tile][lane] + red[2][tile][lane] + red[3][tile][lane];
-    const int mt = tile >> 1, nt = tile & 1;
-    const int n = n0 + 16 * nt + i16;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int c = c0 + 16 * mt + 4 * kk + r;
-      if (c < g.C && n < g.N) atomicAdd(g.dw + (long long)c * g.Npad + n, v[r]);
-    }
-  }
+  wg_flush<4>(red, acc, wave, lane, n0, g, [&](int mt, int row) {
+    const int c = c0 + 16 * mt + row;
+    return c < g.C ? c : -1;
+  });
 }
 
 // ---- weight gradient of the 3x3 layers: the same idea -----------------------------------------------------------
@@ -558,16 +565,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_bf3_kernel(Wg1Geom g) {
 // edge elements (two dword loads, out of range at the image border), and builds three operand vectors from the same
 // registers -- rows 3*q + 0, 1, 2, i.e. lane i16 of three M tiles.  Nothing is loaded unaligned, nothing outside
 // the sample is touched, zero padding is a load that is not issued.
-struct Wg3Geom {
-  const float* x; const float* dy; float* dw;
-  const float* scale; const float* shift;
-  int pre_relu, post_relu;
-  long long xsB, dsB;
-  int C, N, Npad, S, H, W;
-  int ksteps, ksteps_per_block;
-};
-
-__global__ __launch_bounds__(256, 2) void wgrad3x3_bf3_kernel(Wg3Geom g) {
+__global__ __launch_bounds__(256, 2) void wgrad3x3_bf3_kernel(WgGeom g) {
   crn_kernargs_now(g.x, g.dy, g.dw, g.scale, g.shift, g.pre_relu, g.post_relu, g.xsB, g.dsB, g.C, g.N, g.Npad, g.S, g.H,
                    g.W, g.ksteps, g.ksteps_per_block);
   __shared__ __attribute__((aligned(16))) f32x4 red[4][12][64];         // [wave][tile][lane]: 48 KiB
@@ -578,27 +576,19 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_bf3_kernel(Wg3Geom g) {
   const int kbeg = blockIdx.z * g.ksteps_per_block, kend = min(kbeg + g.ksteps_per_block, g.ksteps);
   const bool has_tr = g.scale != nullptr;
   // the lane's two (c, zh) pairs and two output columns
-  unsigned arow[2], brow[2];
+  unsigned arow[2];
+  const unsigned brow[2] = {wg_row(n0 + i16, g.N, g.S), wg_row(n0 + 16 + i16, g.N, g.S)};
   int dzh[2];
   float sc[2], sh[2];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + 16 * qt + i16, c = q / 3;
     dzh[qt] = q - 3 * c - 1;                            // zh - 1
-    arow[qt] = c < g.C ? (unsigned)c * (unsigned)g.S * 4u : kOOB;
+    arow[qt] = wg_row(c, g.C, g.S);
     sc[qt] = (has_tr && c < g.C) ? g.scale[c] : 1.f;
     sh[qt] = (has_tr && c < g.C) ? g.shift[c] : 0.f;
   }
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int n = n0 + 16 * nt + i16;
-    brow[nt] = n < g.N ? (unsigned)n * (unsigned)g.S * 4u : kOOB;
-  }
-  f32x4 acc[6][2];
-#pragma unroll
-  for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[6][2] = {};
 
   f32x4 ra[2][2], rb[2][2];
   float el[2], er[2];                                   // edge elements left / right of the aligned group
@@ -622,24 +612,17 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_bf3_kernel(Wg3Geom g) {
       crn_bload(el[qt], xrs, okl ? off - 4u : kOOB);
       crn_bload(er[qt], xrs, okr ? off + 32u : kOOB);
     }
-    const unsigned koff = (unsigned)s * 4u, oob = live ? 0u : kOOB;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      crn_bload4(rb[nt][0], drs, (brow[nt] + koff) | oob);
-      crn_bload4(rb[nt][1], drs, (brow[nt] + koff + 16u) | oob);
-    }
+    wg_dy_issue(rb, drs, brow, (unsigned)s * 4u, live ? 0u : kOOB);
   };
   auto wait_all = [&]() {
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[qt][0]), "+v"(ra[qt][1]), "+v"(el[qt]), "+v"(er[qt]));
+    for (int qt = 0; qt < 2; ++qt) { wait_vm<0>(ra[qt][0], ra[qt][1]); wait_vm<0>(el[qt], er[qt]); }
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) asm volatile("s_waitcnt vmcnt(0)" : "+v"(rb[nt][0]), "+v"(rb[nt][1]));
+    for (int nt = 0; nt < 2; ++nt) wait_vm<0>(rb[nt][0], rb[nt][1]);
   };
   auto tf = [&](float a, int qt, bool valid) -> float {  // transform of a loaded element; padding stays zero
     if (!has_tr) return a;
-    if (g.pre_relu) a = fmaxf(a, 0.f);
-    a = a * sc[qt] + sh[qt];
-    if (g.post_relu) a = fmaxf(a, 0.f);
+    a = in_transform(a, g.pre_relu, sc[qt], sh[qt], g.post_relu);
     return valid ? a : 0.f;
   };
   int step = kbeg + wave;
@@ -663,42 +646,16 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_bf3_kernel(Wg3Geom g) {
       }
     }
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = rb[nt][j >> 2][j & 3];
-      split8(v, bh[nt], bl[nt]);
-    }
+    for (int nt = 0; nt < 2; ++nt) wg_split(rb[nt], bh[nt], bl[nt]);
     issue(step + 4);
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-      for (int mt = 0; mt < 6; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-#pragma unroll
-      for (int mt = 0; mt < 6; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-#pragma unroll
-      for (int mt = 0; mt < 6; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-    }
+    wg_mfma<6>(acc, ah, al, bh, bl);
   }
   wait_all();
-#pragma unroll
-  for (int mt = 0; mt < 6; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) red[wave][mt * 2 + nt][lane] = acc[mt][nt];
-  __syncthreads();
-  // D row = 4*kk + r = lane-row index iq of the M tile (qt, zw): q = q0 + 16*qt + iq, dw row 3*q + zw
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int tile = wave * 3 + j;                      // wave w sums tiles 3w .. 3w+2
-    const f32x4 v = red[0][tile][lane] + red[1][tile][lane] + red[2][tile][lane] + red[3][tile][lane];
-    const int mt = tile >> 1, nt = tile & 1, qt = mt / 3, zw = mt - 3 * qt;
-    const int n = n0 + 16 * nt + i16;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + 16 * qt + 4 * kk + r;
-      if (q < 3 * g.C && n < g.N) atomicAdd(g.dw + (long long)(3 * q + zw) * g.Npad + n, v[r]);
-    }
-  }
+  // row iq of the M tile mt = (qt, zw) is the lane row of q = q0 + 16*qt + iq: dw row 3*q + zw
+  wg_flush<6>(red, acc, wave, lane, n0, g, [&](int mt, int iq) {
+    const int qt = mt / 3, zw = mt - 3 * qt, q = q0 + 16 * qt + iq;
+    return q < 3 * g.C ? 3 * q + zw : -1;
+  });
 }
 
 bool dense_2d(const crnView& v) {   // unit W stride, rows back to back, 16-byte aligned channel planes
@@ -719,11 +676,9 @@ extern "C" int crn_bf3_operands(const float* packed, const int64_t* desc, int nl
 }
 
 namespace {
+#ifdef CRN_TOOLS
 long long* g_stamps = nullptr;
-template <int T, int CB, int TW>
-int launch_e2d(const E2dGeom& g, dim3 grid, size_t lds, hipStream_t st) {
-  return crn_launch(conv_e2d_kernel<T, CB, TW>, grid, dim3(256), lds, st, g);
-}
+#endif
 
 // Everything crn_conv2d_bf3 decides -- every rejection, the LDS bound included, the kernel, the split and the grid -- as host
 // arithmetic (no HIP call), shared by the launch and crn_conv2d_bf3_plan so that there is one copy of the selection.
@@ -809,7 +764,6 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
   if (want_stamps) {
     if (!g_stamps) CRN_HIP(hipMalloc(&g_stamps, 32 * sizeof(long long)));
     g.stamps = g_stamps;
-    g.dbg = 16;
   }
 #endif
   const int splits = s.splits;
@@ -821,10 +775,13 @@ extern "C" int crn_conv2d_bf3(const crnView* x, const crnInTransform* tr, const 
     g.y = crn_splitk_scratch_view(yreal, scratch);
   }
   const dim3 grid(s.grid[0], s.grid[1], s.grid[2]);
-  int rc;
-  if (s.kernel == CRN_E2D_K1) rc = launch_e2d<1, 4, 16>(g, grid, s.lds, st);
-  else if (s.kernel == CRN_E2D_K3W16) rc = launch_e2d<9, 1, 16>(g, grid, s.lds, st);
-  else rc = launch_e2d<9, 1, 8>(g, grid, s.lds, st);
+  void (*kernel)(E2dGeom) = nullptr;
+  switch (s.kernel) {
+    case CRN_E2D_K1: kernel = conv_e2d_kernel<1, 4, 16>; break;
+    case CRN_E2D_K3W16: kernel = conv_e2d_kernel<9, 1, 16>; break;
+    case CRN_E2D_K3W8: kernel = conv_e2d_kernel<9, 1, 8>; break;
+  }
+  int rc = crn_launch(kernel, grid, dim3(256), s.lds, st, g);
   if (rc == CRN_OK && splits > 1) rc = crn_splitk_finish(yreal, scratch, splits, accumulate, armed, st);
   return rc;
 }
@@ -868,8 +825,7 @@ namespace {
 // As e2d_fwd_select, for crn_conv_wgrad_2d_bf3 and crn_conv_wgrad_2d_bf3_plan: every rejection and every choice, no HIP call.
 struct E2dWgSel {
   int kernel;              // CRN_E2D_WG1 / WG3
-  Wg1Geom g1;
-  Wg3Geom g3;
+  WgGeom g;
   int row_tiles, col_tiles, splits, ksteps, per_block;
   size_t dw_bytes;         // what zero_first clears
 };
@@ -901,23 +857,13 @@ int e2d_wg_select(const crnView* x, const crnInTransform* tr, const crnView* dy,
   s->kernel = k3 ? CRN_E2D_WG3 : CRN_E2D_WG1;
   s->row_tiles = row_tiles; s->col_tiles = col_tiles; s->splits = splits; s->ksteps = ksteps; s->per_block = per_block;
   s->dw_bytes = (size_t)x->C * (k3 ? 9 : 1) * Npad * 4;
-  if (k3) {
-    Wg3Geom& g = s->g3;
-    g = Wg3Geom{};
-    g.x = x->base; g.dy = dy->base; g.dw = dw;
-    g.scale = tr ? tr->scale : nullptr; g.shift = tr ? tr->shift : nullptr;
-    g.pre_relu = tr ? tr->pre_relu : 0; g.post_relu = tr ? tr->post_relu : 0;
-    g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S; g.H = x->H; g.W = x->W;
-    g.ksteps = ksteps; g.ksteps_per_block = per_block;
-  } else {
-    Wg1Geom& g = s->g1;
-    g = Wg1Geom{};
-    g.x = x->base; g.dy = dy->base; g.dw = dw;
-    g.scale = tr ? tr->scale : nullptr; g.shift = tr ? tr->shift : nullptr;
-    g.pre_relu = tr ? tr->pre_relu : 0; g.post_relu = tr ? tr->post_relu : 0;
-    g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S;
-    g.ksteps = ksteps; g.ksteps_per_block = per_block;
-  }
+  WgGeom& g = s->g;
+  g = WgGeom{};
+  g.x = x->base; g.dy = dy->base; g.dw = dw;
+  g.scale = tr ? tr->scale : nullptr; g.shift = tr ? tr->shift : nullptr;
+  g.pre_relu = tr ? tr->pre_relu : 0; g.post_relu = tr ? tr->post_relu : 0;
+  g.xsB = x->sB; g.dsB = dy->sB; g.C = x->C; g.N = dy->C; g.Npad = Npad; g.S = (int)S; g.H = x->H; g.W = x->W;
+  g.ksteps = ksteps; g.ksteps_per_block = per_block;
   return CRN_OK;
 }
 }  // namespace
@@ -932,10 +878,7 @@ extern "C" int crn_conv_wgrad_2d_bf3(const crnView* x, const crnInTransform* tr,
   // behind the last rejection: a rejected call writes nothing
   if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, s.dw_bytes, st));
   const dim3 grid((unsigned)s.row_tiles, (unsigned)s.col_tiles, (unsigned)s.splits);
-  if (s.kernel == CRN_E2D_WG3) hipLaunchKernelGGL(wgrad3x3_bf3_kernel, grid, dim3(256), 0, st, s.g3);
-  else hipLaunchKernelGGL(wgrad1x1_bf3_kernel, grid, dim3(256), 0, st, s.g1);
-  CRN_CHECK_LAUNCH();
-  return CRN_OK;
+  return crn_launch(s.kernel == CRN_E2D_WG3 ? wgrad3x3_bf3_kernel : wgrad1x1_bf3_kernel, grid, dim3(256), 0, st, s.g);
 }
 
 extern "C" int crn_conv_wgrad_2d_bf3_plan(const crnView* x, const crnInTransform* tr, const crnView* dy, float* dw, int Npad,
