@@ -607,6 +607,17 @@ class HipBackend:
     self.lib.crn_component_stats(ptr(labels), ptr(grid), st, 0 if grid is None else _DTYPE_CODE[grid.dtype], N, D, H, W,
                                  ptr(offsets), int(K), ptr(size), ptr(bbox), ptr(first), ptr(value), _lib.stream())
 
+  # -- voxel distances (corenet_amd.voxel_distance) --------------------------------------------------
+  def voxel_distance(self, grid: t.Tensor, mode: int, d2: t.Tensor, index: Optional[t.Tensor]):
+    """d2 (/ index) (int32 [N, D, H, W]) <- the exact squared distance of every voxel to the target set `mode` of grid
+    (uint8 or int32, W stride 1) (/ the linear index of that target); queued on the current stream."""
+    N, D, H, W = grid.shape
+    n = self.lib.crn_voxel_distance_workspace_bytes(N, D, H, W, int(index is not None))
+    ws = self.workspace("vd", n, grid.device) if n else None
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_voxel_distance(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, int(mode), ptr(ws), n, ptr(d2), ptr(index),
+                                _lib.stream())
+
   # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
   def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
                      tri_index: t.Tensor, valid: t.Tensor):

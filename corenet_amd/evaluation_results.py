@@ -375,6 +375,71 @@ class SurfaceResults:
             "per_class": {int(c): entry(cls == c) for c in sorted(set(cls.tolist()))}}
 
 
+def _voxel_sizes(v2x_transform: t.Tensor) -> t.Tensor:
+  """f32 [B] on the host: the edge of a voxel in view space, from inverse(v2x_transform[b]).  The three column norms of
+  its 3x3 block must agree to 1e-4 relative: the voxel measure assumes cubic voxels."""
+  sizes = []
+  for b in range(v2x_transform.shape[0]):
+    inv = v2x_transform[b].detach().cpu().to(t.float64).inverse()
+    norms = inv[:3, :3].norm(dim=0)
+    if float(norms.max() - norms.min()) > 1e-4 * float(norms.max()):
+      raise ValueError(f"voxel_surface_metrics_for_batch: the voxels of scene {b} are not cubic (edges {norms.tolist()})")
+    sizes.append(float(norms.mean()))
+  return t.tensor(sizes, dtype=t.float32)
+
+
+def voxel_surface_metrics_for_batch(pmf: t.Tensor, ex, task_type, thresholds: Sequence[float] = DEFAULT_SURFACE_THRESHOLDS,
+                                    level: float = 0.5, min_component_voxels: int = 0) -> SurfaceRows:
+  """Chamfer distance and F-score per (scene, class) at voxel resolution (corenet_amd.voxel_distance): the predicted set
+  of (scene b, class k) is pmf[b, k] > level, the ground truth ex.grid[b] == k, a side's points are its surface voxels
+  and a point's distance is the exact distance to the nearest surface voxel of the other side, in view-space units
+  (voxel edge from inverse(ex.v2x_transform[b]); ValueError unless the voxels are cubic).  Deterministic, no seed, no
+  marching cubes: two distance transforms per call.  Rows, thresholds and NaN conventions are those of
+  surface_metrics_for_batch; min_component_voxels > 0 removes the prediction's floaters first, as there."""
+  from corenet_amd.voxel_distance import voxel_surface_metrics
+  task = _task(task_type)
+  if pmf.dim() != 5 or pmf.shape[1] < 2:
+    raise ValueError(f"voxel_surface_metrics_for_batch: pmf must be [B, C >= 2, D, H, W], got {tuple(pmf.shape)}")
+  dev = pmf.device
+  B, C = pmf.shape[:2]
+  K = C - 1
+  if len(ex.scene_id) != B:
+    raise ValueError(f"voxel_surface_metrics_for_batch: pmf has {B} elements, the batch {len(ex.scene_id)}")
+  if task == "fg_bg" and K != 1:
+    raise ValueError(f"voxel_surface_metrics_for_batch: fg_bg expects 2 classes, pmf has {C}")
+  if tuple(ex.grid.shape) != (B,) + tuple(pmf.shape[2:]):
+    raise ValueError(f"voxel_surface_metrics_for_batch: ex.grid is {tuple(ex.grid.shape)}, pmf {tuple(pmf.shape)}")
+  sizes = _voxel_sizes(ex.v2x_transform)
+  pred = (pmf[:, 1:] > level).reshape((B * K,) + tuple(pmf.shape[2:]))
+  if min_component_voxels > 0:
+    from corenet_amd.voxel_components import filter_components
+    pred = filter_components(pred, min_voxels=int(min_component_voxels), connectivity=6)
+  classes = t.arange(1, C, device=dev, dtype=ex.grid.dtype)[None, :, None, None, None]
+  gt = (ex.grid.to(dev)[:, None] == classes).reshape(pred.shape)
+  metrics = voxel_surface_metrics(pred, gt, thresholds, voxel_size=sizes.repeat_interleave(K))
+  rows = t.arange(B * K)
+  return SurfaceRows(rows // K, rows % K + 1, [ex.scene_id[b] for b in range(B) for _ in range(K)],
+                     tuple(float(x) for x in thresholds), metrics)
+
+
+class VoxelSurfaceResults(SurfaceResults):
+  """SurfaceResults over voxel_surface_metrics_for_batch: add_batch measures at voxel resolution; rows() and summary()
+  are those of SurfaceResults."""
+
+  def __init__(self, task_type="fg_bg", thresholds: Sequence[float] = DEFAULT_SURFACE_THRESHOLDS, level: float = 0.5,
+               min_component_voxels: int = 0):
+    super().__init__(task_type, thresholds=thresholds, level=level)
+    self.kwargs = dict(thresholds=tuple(thresholds), level=level, min_component_voxels=int(min_component_voxels))
+
+  def add_batch(self, pmf: t.Tensor, ex) -> SurfaceRows:
+    rows = voxel_surface_metrics_for_batch(pmf, ex, self.task_type, **self.kwargs)
+    self.scene_id += rows.scene_id
+    self.class_index.append(rows.class_index)
+    self.chamfer_l1.append(rows.metrics.chamfer_l1.cpu())
+    self.fscore.append(rows.metrics.fscore.cpu())
+    return rows
+
+
 GLOBAL_CLASS_NAME = "__global__"
 METRIC_NAMES = ("iou", "precision", "recall")
 

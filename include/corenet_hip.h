@@ -889,6 +889,44 @@ int crn_component_stats_cpu(const int32_t* labels, const void* grid, const int64
                             int H, int W, const int64_t* offsets, int64_t K, int64_t* size, int32_t* bbox,
                             int64_t* first, int32_t* value, int num_threads);
 
+/* ---------------- voxel distances (corenet_amd.voxel_distance) -----------------
+ * Exact squared Euclidean distance transform of N independent grids grid[n][d][h][w] (strides and dtype as for
+ * crn_voxel_components).  Contract: DESIGN section 18.
+ *   mode    the target set T of a grid: CRN_VD_FOREGROUND the voxels with value > 0, CRN_VD_BACKGROUND all others,
+ *           CRN_VD_SURFACE the foreground voxels with one of their 6 neighbours not foreground or outside the grid.
+ *   d2      int32 [N][D][H][W] contiguous: min over u in T of |v - u|^2 in voxel units, an exact integer.
+ *   index   NULL, or int32 [N][D][H][W] contiguous: the per-grid linear index d*H*W + h*W + w of the u that attains it,
+ *           DEFINED by the separable recurrence: (1) the nearest target of the same row, ties to the lower w;
+ *           (2) argmin_j g1[j] + (i - j)^2 over the column along h, ties to the lower j, the winner keeps row j's w;
+ *           (3) the same along d.  The value is the true 3-D minimum; the index does not depend on scheduling.
+ *   A grid with empty T: d2 = CRN_VD_NO_TARGET, index = -1 everywhere.
+ * CRN_EINVAL: an empty extent (N == 0 is valid and does nothing), D*H*W > 2^31 - 1, or
+ * (D-1)^2 + (H-1)^2 + (W-1)^2 >= 2^31 - 1.  Nothing depends on crn_set_deterministic.
+ *
+ * GPU: crn_voxel_distance queues a row pass and one line pass per axis h, d longer than 1 on stream s and does not wait
+ * for the GPU; no workgroup waits for another one.  A line pass stages whole lines of up to CRN_VD_LINE_CAP elements x
+ * 64 columns in LDS and keeps CRN_VD_LINE_R outputs per lane in registers; with the index it packs (value << bits) | j
+ * into one word where (bound + 1) << bits <= 2^CRN_VD_PACK_BITS (bound: the largest value the pass can produce, the sum
+ * of the squared extents - 1 up to its axis; bits = ceil(log2(line length))), else it compares and selects; longer lines
+ * are read from a copy in global memory.  crn_voxel_distance_tiles writes those three constants.  workspace:
+ * crn_voxel_distance_workspace_bytes(N, D, H, W, want_index) -- the second index buffer, and the copy for lines beyond
+ * the capacity; it may be 0, and workspace NULL then.
+ *
+ * Host twin (HOST memory, same contract, identical results): one grid per thread; num_threads <= 0: all.          */
+#define CRN_VD_FOREGROUND 0
+#define CRN_VD_BACKGROUND 1
+#define CRN_VD_SURFACE 2
+#define CRN_VD_NO_TARGET 2147483647
+#define CRN_VD_LINE_R 16
+#define CRN_VD_LINE_CAP 512
+#define CRN_VD_PACK_BITS 31
+int crn_voxel_distance_tiles(int32_t* out3);
+size_t crn_voxel_distance_workspace_bytes(int N, int D, int H, int W, int want_index);
+int crn_voxel_distance(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int mode,
+                       void* workspace, size_t workspace_bytes, int32_t* d2, int32_t* index, crnStream s);
+int crn_voxel_distance_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int mode,
+                           int32_t* d2, int32_t* index, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
