@@ -208,6 +208,9 @@ _SIGS = {
     "crn_voxel_distance_tiles": [vp],
     "crn_voxel_distance": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp],
     "crn_voxel_distance_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp, i32],
+    "crn_voxel_visibility_tiles": [vp],
+    "crn_voxel_visibility": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp],
+    "crn_voxel_visibility_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, i32, vp, vp, i32],
     "crn_voxelize_mesh": [vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "crn_batch_renorm_eval_affine": [vp, vp, vp, i32, f32, vp, vp, vp],
     "crn_transform_meshes": [vp, vp, i32, vp, i32, vp, vp],
@@ -228,6 +231,7 @@ _SIZE_FNS = {
     "crn_point_triangle_tile": [i32],
     "crn_voxel_components_workspace_bytes": [i32, i32, i32, i32],
     "crn_voxel_distance_workspace_bytes": [i32, i32, i32, i32, i32],
+    "crn_voxel_visibility_workspace_bytes": [i32, i32, i32, i32],
     "crn_convt_s2k7_ximage_bytes": [i32, i32, i32, i32],
     "crn_stem_conv_parts": [i32, i32, i32],
 }

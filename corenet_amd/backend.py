@@ -618,6 +618,18 @@ class HipBackend:
     self.lib.crn_voxel_distance(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, int(mode), ptr(ws), n, ptr(d2), ptr(index),
                                 _lib.stream())
 
+  # -- voxel visibility (corenet_amd.voxel_visibility) ------------------------------------------------
+  def voxel_visibility(self, grid: t.Tensor, eye_q: t.Tensor, flags: int, occluded: t.Tensor, first: Optional[t.Tensor]):
+    """occluded (bool [N, D, H, W]) (/ first, int32) <- whether an occupied voxel of grid (uint8 or int32, W stride 1)
+    lies between every voxel and the eye eye_q (int32 [N, 3] on the HOST, 1/256 voxel) (/ the one nearest the eye);
+    queued on the current stream."""
+    N, D, H, W = grid.shape
+    n = self.lib.crn_voxel_visibility_workspace_bytes(N, D, H, W)
+    ws = self.workspace("vv", n, grid.device)
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_voxel_visibility(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, eye_q.data_ptr(), int(flags), ptr(ws), n,
+                                  ptr(occluded), ptr(first), _lib.stream())
+
   # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
   def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
                      tri_index: t.Tensor, valid: t.Tensor):

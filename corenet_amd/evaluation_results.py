@@ -440,6 +440,95 @@ class VoxelSurfaceResults(SurfaceResults):
     return rows
 
 
+class VisibilityRows(NamedTuple):
+  """One row per (scene, foreground class), scene-major, like SurfaceRows."""
+  scene_index: t.Tensor                    # i64 [R], host
+  class_index: t.Tensor                    # i64 [R], host: 1 .. C - 1
+  scene_id: List[str]                      # [R]
+  eye: t.Tensor                            # f64 [B, 3], host: the camera of every scene in voxel coordinates
+  metrics: "VisibilityIoU"                 # [R, 2] on pmf's device: column 0 what the camera sees, column 1 what is hidden
+
+
+def visibility_metrics_for_batch(pmf: t.Tensor, ex, task_type, level: float = 0.5) -> VisibilityRows:
+  """IoU per (scene, class) split into the part of the grid the camera sees and the part hidden behind the scene
+  (corenet_amd.voxel_visibility): the predicted set of (scene b, class k) is pmf[b, k] > level, the ground truth
+  ex.grid[b] == k, and a voxel is hidden iff an occupied voxel of the WHOLE scene, ex.grid[b] > 0, lies between its
+  centre and the camera -- other objects hide too.  The camera of scene b is the centre of projection of
+  ex.camera_transform[b] in the voxel space of view2voxel_matrices(ex.grid_sampling_offset, resolution), where the voxel
+  centres are the grid's sample points (ValueError for a camera without one, e.g. an orthographic one).  One occlusion
+  call per batch; reading the camera from the device synchronises once.  Rows are those of surface_metrics_for_batch; a
+  class absent on both sides of a region gives iou NaN there."""
+  from corenet_amd import voxel_visibility as VV
+  from corenet_amd.data.batched_example import view2voxel_matrices
+  task = _task(task_type)
+  if pmf.dim() != 5 or pmf.shape[1] < 2:
+    raise ValueError(f"visibility_metrics_for_batch: pmf must be [B, C >= 2, D, H, W], got {tuple(pmf.shape)}")
+  dev = pmf.device
+  B, C = pmf.shape[:2]
+  K = C - 1
+  if len(ex.scene_id) != B:
+    raise ValueError(f"visibility_metrics_for_batch: pmf has {B} elements, the batch {len(ex.scene_id)}")
+  if task == "fg_bg" and K != 1:
+    raise ValueError(f"visibility_metrics_for_batch: fg_bg expects 2 classes, pmf has {C}")
+  if tuple(ex.grid.shape) != (B,) + tuple(pmf.shape[2:]):
+    raise ValueError(f"visibility_metrics_for_batch: ex.grid is {tuple(ex.grid.shape)}, pmf {tuple(pmf.shape)}")
+  eye = VV.eye_in_voxel_space(ex.camera_transform, view2voxel_matrices(ex.grid_sampling_offset, tuple(pmf.shape[2:])))
+  grid = ex.grid.to(dev)
+  hidden = VV.occlusion(grid, eye).occluded                                  # [B, D, H, W]: the whole scene occludes
+  shape = (B * K,) + tuple(pmf.shape[2:])
+  pred = (pmf[:, 1:] > level).reshape(shape)
+  classes = t.arange(1, C, device=dev, dtype=grid.dtype)[None, :, None, None, None]
+  gt = (grid[:, None] == classes).reshape(shape)
+  metrics = VV._split_iou(pred, gt, hidden[:, None].expand((B, K) + tuple(pmf.shape[2:])).reshape(shape))
+  rows = t.arange(B * K)
+  return VisibilityRows(rows // K, rows % K + 1, [ex.scene_id[b] for b in range(B) for _ in range(K)], eye, metrics)
+
+
+class VisibilityResults:
+  """Accumulates visibility_metrics_for_batch over an evaluation run, in the manner of VoxelSurfaceResults:
+  add_batch(pmf, ex) takes what pipeline.evaluate_batch returns; summary() gives, for the seen and the hidden region,
+  the mean IoU over the rows that are not NaN and the IoU of the summed counts, per class and overall."""
+
+  REGIONS = ("visible", "hidden")
+
+  def __init__(self, task_type="fg_bg", level: float = 0.5):
+    self.task_type = task_type
+    self.level = level
+    self.scene_id: List[str] = []
+    self.class_index: List[t.Tensor] = []
+    self.intersection: List[t.Tensor] = []
+    self.union: List[t.Tensor] = []
+    self.iou: List[t.Tensor] = []
+
+  def add_batch(self, pmf: t.Tensor, ex) -> VisibilityRows:
+    rows = visibility_metrics_for_batch(pmf, ex, self.task_type, level=self.level)
+    self.scene_id += rows.scene_id
+    self.class_index.append(rows.class_index)
+    self.intersection.append(rows.metrics.intersection.cpu())
+    self.union.append(rows.metrics.union.cpu())
+    self.iou.append(rows.metrics.iou.cpu())
+    return rows
+
+  def rows(self) -> Tuple[t.Tensor, t.Tensor, t.Tensor, t.Tensor]:
+    """(class_index i64 [R], intersection i64 [R, 2], union i64 [R, 2], iou f64 [R, 2]) of every row added so far."""
+    if not self.class_index:
+      z = t.zeros((0, 2), dtype=t.int64)
+      return t.zeros(0, dtype=t.int64), z, z.clone(), t.zeros((0, 2), dtype=t.float64)
+    return t.cat(self.class_index), t.cat(self.intersection), t.cat(self.union), t.cat(self.iou)
+
+  def summary(self) -> Dict:
+    cls, inter, union, iou = self.rows()
+
+    def entry(sel):
+      i, u = inter[sel].sum(0), union[sel].sum(0)
+      pooled = t.where(u > 0, i.to(t.float64) / u.to(t.float64), t.full((), float("nan"), dtype=t.float64))
+      mean = _nanmean(iou[sel])
+      return {r: {"mean_iou": float(mean[c]), "pooled_iou": float(pooled[c]), "num_rows": int((~t.isnan(iou[sel][:, c])).sum())}
+              for c, r in enumerate(self.REGIONS)}
+    return {"overall": entry(t.ones_like(cls, dtype=t.bool)),
+            "per_class": {int(c): entry(cls == c) for c in sorted(set(cls.tolist()))}}
+
+
 GLOBAL_CLASS_NAME = "__global__"
 METRIC_NAMES = ("iou", "precision", "recall")
 

@@ -927,6 +927,50 @@ int crn_voxel_distance(const void* grid, const int64_t* strides, int dtype, int 
 int crn_voxel_distance_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int mode,
                            int32_t* d2, int32_t* index, int num_threads);
 
+/* ---------------- voxel visibility (corenet_amd.voxel_visibility) -----------------
+ * Which voxels of N independent grids grid[n][d][h][w] (strides and dtype as for crn_voxel_components; occupied iff
+ * value > 0) an eye can see.  Contract: DESIGN section 19.  Space is measured in 1 / CRN_VV_SUBDIVISIONS of a voxel:
+ * voxel (x, y, z) = index [z][y][x] is the cube [256x, 256x + 256] x [256y, ..] x [256z, ..] with centre
+ * (256x + 128, 256y + 128, 256z + 128).
+ *   eye_q       int32 [N][3] in HOST memory (both entries): the eye (x, y, z) of every grid in those units.
+ *   occluded    uint8 [N][D][H][W] contiguous: 1 iff an occupied voxel u != v has its open interior met by the open
+ *               segment from the centre of v to the eye (the traversed voxels of v); v's own value does not matter.
+ *   first       NULL, or int32 [N][D][H][W] contiguous: the per-grid linear index z*H*W + y*W + x of the occupied
+ *               traversed voxel nearest the eye, -1 where there is none.
+ * The traversed voxels are DEFINED by the integer walk of DESIGN section 19 (three 64-bit face-crossing terms; all
+ * axes whose term equals the minimum step together), which both entries run, so results are identical bit for bit.
+ * CRN_EINVAL: an empty extent (N == 0 is valid and does nothing), an extent above CRN_VV_MAX_EXTENT, an eye
+ * coordinate beyond +-CRN_VV_MAX_EYE, a flag the entry does not know.  Then every term of the walk stays below 2^61.
+ *   flags       CRN_VV_FLAT (GPU): read the fine occupancy bits only (below).  CRN_VV_COUNT_STEPS (host twin only, needs
+ *               first): first receives the trip count of every voxel's walk to the grid boundary or the eye instead.
+ *
+ * GPU: crn_voxel_visibility queues a memset, a pack pass and one walk launch per 64 grids on stream s and does not
+ * wait for the GPU (the eyes travel as kernel arguments); no workgroup waits for another one.  The pack pass writes one
+ * occupancy bit per voxel (a 64-bit word per 64 voxels of a row) and ORs one bit per brick of CRN_VV_BRICK^3 voxels
+ * into a coarse map; the walk pass stages a grid's coarse map in LDS and reads a fine word only inside an occupied
+ * brick.  A coarse map beyond CRN_VV_COARSE_CAP_BYTES, or CRN_VV_FLAT, selects the flat form, which reads fine words
+ * only.  crn_voxel_visibility_tiles writes (CRN_VV_BRICK, CRN_VV_COARSE_CAP_BYTES, CRN_VV_WG_WORDS: the 64-voxel
+ * words a workgroup of the walk pass owns).  workspace: crn_voxel_visibility_workspace_bytes(N, D, H, W), never 0
+ * for N >= 1.
+ *
+ * Host twin (HOST memory, same contract, identical results): the planes of all grids are spread over num_threads
+ * (<= 0: all).                                                                                                    */
+#define CRN_VV_SUBDIVISIONS 256
+#define CRN_VV_MAX_EXTENT 2048
+#define CRN_VV_MAX_EYE (1 << 19)
+#define CRN_VV_FLAT 1
+#define CRN_VV_COUNT_STEPS 2
+#define CRN_VV_BRICK 4
+#define CRN_VV_COARSE_CAP_BYTES 65536
+#define CRN_VV_WG_WORDS 256
+int crn_voxel_visibility_tiles(int32_t* out3);
+size_t crn_voxel_visibility_workspace_bytes(int N, int D, int H, int W);
+int crn_voxel_visibility(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W,
+                         const int32_t* eye_q, int flags, void* workspace, size_t workspace_bytes, uint8_t* occluded,
+                         int32_t* first, crnStream s);
+int crn_voxel_visibility_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W,
+                             const int32_t* eye_q, int flags, uint8_t* occluded, int32_t* first, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
