@@ -211,6 +211,9 @@ _SIGS = {
     "crn_voxel_visibility_tiles": [vp],
     "crn_voxel_visibility": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp],
     "crn_voxel_visibility_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, i32, vp, vp, i32],
+    "crn_voxel_overlap_tiles": [vp],
+    "crn_voxel_overlap": [vp, C.POINTER(i64), i32, vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp],
+    "crn_voxel_overlap_cpu": [vp, C.POINTER(i64), i32, vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32],
     "crn_voxelize_mesh": [vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "crn_batch_renorm_eval_affine": [vp, vp, vp, i32, f32, vp, vp, vp],
     "crn_transform_meshes": [vp, vp, i32, vp, i32, vp, vp],
@@ -232,6 +235,7 @@ _SIZE_FNS = {
     "crn_voxel_components_workspace_bytes": [i32, i32, i32, i32],
     "crn_voxel_distance_workspace_bytes": [i32, i32, i32, i32, i32],
     "crn_voxel_visibility_workspace_bytes": [i32, i32, i32, i32],
+    "crn_voxel_overlap_workspace_bytes": [i32, vp],
     "crn_convt_s2k7_ximage_bytes": [i32, i32, i32, i32],
     "crn_stem_conv_parts": [i32, i32, i32],
 }

@@ -630,6 +630,17 @@ class HipBackend:
     self.lib.crn_voxel_visibility(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, eye_q.data_ptr(), int(flags), ptr(ws), n,
                                   ptr(occluded), ptr(first), _lib.stream())
 
+  # -- label overlaps (corenet_amd.voxel_overlap) ------------------------------------------------------
+  def voxel_overlap(self, a: t.Tensor, b: t.Tensor, num_a: t.Tensor, num_b: t.Tensor, table_offsets: t.Tensor,
+                    table: t.Tensor, bad: t.Tensor):
+    """table (int64, flat) / bad (int64 [N]) <- the overlap counts of the label grids a, b (uint8 or int32, W stride 1)
+    with the highest labels num_a, num_b (device int64 [N]); table_offsets: int64 [N + 1] on the HOST; queued on the
+    current stream."""
+    N, D, H, W = a.shape
+    sa, sb = (C.c_int64 * 4)(*a.stride()), (C.c_int64 * 4)(*b.stride())
+    self.lib.crn_voxel_overlap(ptr(a), sa, _DTYPE_CODE[a.dtype], ptr(b), sb, _DTYPE_CODE[b.dtype], N, D, H, W, ptr(num_a),
+                               ptr(num_b), table_offsets.data_ptr(), ptr(table), 8 * table.numel(), ptr(bad), _lib.stream())
+
   # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
   def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
                      tri_index: t.Tensor, valid: t.Tensor):

@@ -529,6 +529,131 @@ class VisibilityResults:
             "per_class": {int(c): entry(cls == c) for c in sorted(set(cls.tolist()))}}
 
 
+class InstanceRows(NamedTuple):
+  """Per (scene, class) the panoptic counts, and one row per ground-truth object, scene-major in mesh order."""
+  scene_id: List[str]                      # [B]
+  counts: "PanopticCounts"                 # tp / fp / fn i64, sum_iou f64 [B, num_classes] on pmf's device
+  scene_index: t.Tensor                    # i64 [M], host
+  mesh_index: t.Tensor                     # i64 [M], host: the object is mesh mesh_index of its scene
+  class_index: t.Tensor                    # i64 [M], host: ex.mesh_labels of the object
+  gt_voxels: t.Tensor                      # i64 [M], host: 0 for a mesh that leaves no voxel (still a false negative)
+  matched: t.Tensor                        # bool [M], host
+  matched_iou: t.Tensor                    # f64 [M], host: the IoU with the matched predicted component, 0 if none
+  best_iou: t.Tensor                       # f64 [M], host: the best IoU with a predicted component of the object's class
+
+
+def instance_metrics_for_batch(pmf: t.Tensor, ex, task_type, connectivity: int = 6, min_component_voxels: int = 0,
+                               iou_threshold: float = 0.5, gt_instances: Optional[t.Tensor] = None,
+                               **voxelization) -> InstanceRows:
+  """Per-object evaluation of a batch (corenet_amd.voxel_overlap): per-object IoU and the counts of
+  panoptic / segmentation / recognition quality.
+
+  The predicted instances are the connected components (`connectivity`, per value) of the predicted label grid
+  extract_labels(pmf, ex, task_type)[0]; the class of a component is the label it carries.  Components below
+  min_component_voxels voxels are folded into the background.  The ground-truth instances are gt_instances (int32
+  [B, D, H, W], mesh index + 1, 0 where no mesh is) if given, otherwise batched_example.voxelize(ex, resolution,
+  voxel_content_mesh_index, **voxelization) with the keywords of batched_example.voxelize (where meshes overlap, the
+  voxel belongs to the one with the highest index); the class of instance i of scene b is ex.mesh_labels[b][i - 1].  A
+  predicted component matches an object iff their classes are equal and their IoU exceeds iou_threshold (>= 0.5, so
+  matches are unique: match_segments).  A mesh that leaves no voxel counts as a false negative.  Touching objects of one
+  class come out as one predicted component, which then matches at most one of them: that is the measurement, not an
+  error.  A ground-truth label above the scene's number of meshes raises ValueError.
+
+  Per call: one connected-components call with its statistics, one label_overlaps call, torch on the sparse table."""
+  from corenet_amd import voxel_overlap as VO
+  from corenet_amd.voxel_components import component_stats, connected_components
+  task = _task(task_type)
+  if pmf.dim() != 5 or pmf.shape[1] < 2:
+    raise ValueError(f"instance_metrics_for_batch: pmf must be [B, C >= 2, D, H, W], got {tuple(pmf.shape)}")
+  dev = pmf.device
+  B, C = pmf.shape[:2]
+  if len(ex.scene_id) != B or len(ex.mesh_labels) != B:
+    raise ValueError(f"instance_metrics_for_batch: pmf has {B} elements, the batch {len(ex.scene_id)}")
+  mesh_labels = [t.as_tensor(v).to(t.int64).cpu().reshape(-1) for v in ex.mesh_labels]
+  if gt_instances is None:
+    from corenet_amd.data import batched_example
+    gt_instances = batched_example.voxelize(ex, tuple(pmf.shape[2:]), batched_example.voxel_content_mesh_index, **voxelization).grid
+  gt_instances = t.as_tensor(gt_instances).to(dev)
+  if tuple(gt_instances.shape) != (B,) + tuple(pmf.shape[2:]):
+    raise ValueError(f"instance_metrics_for_batch: gt_instances is {tuple(gt_instances.shape)}, pmf {tuple(pmf.shape)}")
+  pred = extract_labels(pmf, ex, task)[0]
+  comps = connected_components(pred, connectivity, by_value=True)
+  stats = component_stats(comps, pred)
+  num_meshes = t.tensor([v.numel() for v in mesh_labels], dtype=t.int64)
+  ov = VO.label_overlaps(comps.labels, gt_instances, comps.num_components, num_meshes.to(dev))
+  if bool(ov.bad.any()):
+    raise ValueError(f"instance_metrics_for_batch: gt_instances has labels outside 0 .. number of meshes ({ov.bad.tolist()} voxels)")
+  K = stats.size.numel()
+  comp_scene = t.repeat_interleave(t.arange(B), stats.offsets[1:] - stats.offsets[:-1], output_size=K).to(dev)
+  class_a = t.zeros(K + B, dtype=t.int32, device=dev)                        # a background row in front of every scene
+  class_a[t.arange(K, device=dev) + comp_scene + 1] = stats.value
+  class_b = t.cat([t.cat([t.zeros(1, dtype=t.int64), v]) for v in mesh_labels]).to(dev, t.int32)
+  matches = VO.match_segments(ov, class_a, class_b, iou_threshold=iou_threshold, min_voxels_a=int(min_component_voxels))
+  num_classes = max([C] + [int(v.max()) + 1 for v in mesh_labels if v.numel()])
+  counts = VO.panoptic_quality(matches, num_classes)
+  objects = matches.valid_b.nonzero()[:, 0]                                   # scene-major, mesh order
+  return InstanceRows(list(ex.scene_id), counts,
+                      t.repeat_interleave(t.arange(B), num_meshes), t.cat([t.arange(int(n)) for n in num_meshes] + [t.zeros(0, dtype=t.int64)]),
+                      t.cat(mesh_labels + [t.zeros(0, dtype=t.int64)]), matches.size_b[objects].cpu(),
+                      (matches.partner_b[objects] > 0).cpu(), matches.iou_b[objects].cpu(), matches.best_iou_b[objects].cpu())
+
+
+class InstanceResults:
+  """Accumulates instance_metrics_for_batch over an evaluation run, in the manner of VisibilityResults: add_batch(pmf,
+  ex) takes what pipeline.evaluate_batch returns (keyword arguments go on to instance_metrics_for_batch, e.g.
+  gt_instances); summary() pools the counts over all scenes and gives, per class and overall (the classes summed): PQ,
+  SQ, RQ, tp / fp / fn, the mean best_iou per ground-truth object and the number of predicted components per
+  ground-truth object, (tp + fp) / (tp + fn)."""
+
+  def __init__(self, task_type="fg_bg", connectivity: int = 6, min_component_voxels: int = 0, iou_threshold: float = 0.5,
+               **voxelization):
+    self.task_type = task_type
+    self.connectivity = connectivity
+    self.min_component_voxels = min_component_voxels
+    self.iou_threshold = iou_threshold
+    self.voxelization = voxelization
+    self.scene_id: List[str] = []
+    self.counts: List[Tuple[t.Tensor, t.Tensor, t.Tensor, t.Tensor]] = []
+    self.class_index: List[t.Tensor] = []
+    self.best_iou: List[t.Tensor] = []
+
+  def add_batch(self, pmf: t.Tensor, ex, gt_instances: Optional[t.Tensor] = None) -> InstanceRows:
+    rows = instance_metrics_for_batch(pmf, ex, self.task_type, connectivity=self.connectivity,
+                                      min_component_voxels=self.min_component_voxels, iou_threshold=self.iou_threshold,
+                                      gt_instances=gt_instances, **self.voxelization)
+    self.scene_id += rows.scene_id
+    self.counts.append(tuple(x.cpu() for x in rows.counts))
+    self.class_index.append(rows.class_index)
+    self.best_iou.append(rows.best_iou)
+    return rows
+
+  def pooled(self) -> Tuple[t.Tensor, t.Tensor, t.Tensor, t.Tensor]:
+    """(tp, fp, fn i64 [num_classes], sum_iou f64 [num_classes]) summed over every scene added so far; batches with
+    fewer classes are padded."""
+    nc = max([c[0].shape[1] for c in self.counts] + [1])
+    out = [t.zeros(nc, dtype=t.int64), t.zeros(nc, dtype=t.int64), t.zeros(nc, dtype=t.int64), t.zeros(nc, dtype=t.float64)]
+    for c in self.counts:
+      for acc, x in zip(out, c):
+        acc[:x.shape[1]] += x.sum(0)
+    return tuple(out)
+
+  def summary(self) -> Dict:
+    from corenet_amd.voxel_overlap import panoptic_scores
+    tp, fp, fn, sum_iou = self.pooled()
+    cls = t.cat(self.class_index) if self.class_index else t.zeros(0, dtype=t.int64)
+    best = t.cat(self.best_iou) if self.best_iou else t.zeros(0, dtype=t.float64)
+
+    def entry(tp, fp, fn, sum_iou, sel):
+      pq, sq, rq = panoptic_scores(tp, fp, fn, sum_iou)
+      objects = int(tp + fn)
+      return {"pq": float(pq), "sq": float(sq), "rq": float(rq), "tp": int(tp), "fp": int(fp), "fn": int(fn),
+              "num_objects": objects, "mean_best_iou": float(best[sel].mean()) if objects else float("nan"),
+              "components_per_object": float(tp + fp) / objects if objects else float("nan")}
+    present = [c for c in range(tp.numel()) if int(tp[c] + fp[c] + fn[c])]
+    return {"overall": entry(tp.sum(), fp.sum(), fn.sum(), sum_iou.sum(), t.ones_like(cls, dtype=t.bool)),
+            "per_class": {c: entry(tp[c], fp[c], fn[c], sum_iou[c], cls == c) for c in present}}
+
+
 GLOBAL_CLASS_NAME = "__global__"
 METRIC_NAMES = ("iou", "precision", "recall")
 

@@ -971,6 +971,51 @@ int crn_voxel_visibility(const void* grid, const int64_t* strides, int dtype, in
 int crn_voxel_visibility_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W,
                              const int32_t* eye_q, int flags, uint8_t* occluded, int32_t* first, int num_threads);
 
+/* ---------------- label overlaps of two voxel grids (corenet_amd.voxel_overlap) -----------------
+ * How many voxels carry label i in grid a[n][d][h][w] and label j in grid b[n][d][h][w], for N independent pairs of
+ * grids.  Contract: DESIGN section 20.  a and b have their own dtype (1 = uint8, 2 = int32: the codes of
+ * crn_voxel_components) and their own strides [4] in elements: W stride 1, N / D / H strides arbitrary (>= 0).
+ * D*H*W <= 2^31 - 1.
+ *   num_a, num_b   int64 [N]: the highest valid label of every grid (e.g. crn_voxel_components' num).
+ *   table_offsets  int64 [N + 1] in HOST memory (both entries), ascending from 0: the table of grid n is the
+ *                  (num_a[n] + 1) x (num_b[n] + 1) int64 counts, row-major (a the row), at table + table_offsets[n].
+ *                  Background (label 0) is an ordinary row and column.  The call zeroes the whole buffer first.
+ *   bad            int64 [N]: voxels with a < 0, a > num_a[n], b < 0 or b > num_b[n]; they are counted nowhere else
+ *                  (crn_eval_labels' rule).  A grid whose num_a / num_b is negative, or whose (num_a + 1) * (num_b + 1)
+ *                  is not the length table_offsets gives it, has all its voxels in bad and its table left at zero: the
+ *                  kernels never write outside a grid's own table.
+ * CRN_EINVAL: an empty extent (N == 0 is valid and does nothing), an unknown dtype, a W stride other than 1,
+ * table_offsets that descend, a grid with more than 2^31 - 1 entries (keys are 32-bit), a GPU call whose tables
+ * together exceed CRN_VO_MAX_TABLE_ENTRIES; CRN_ENOMEM: table_bytes below crn_voxel_overlap_workspace_bytes.
+ * crn_voxel_overlap_workspace_bytes(N, table_offsets) is the size of the table buffer in bytes (never 0 for N >= 1; 0
+ * for offsets the call would refuse): the call needs no other device memory.
+ *
+ * GPU: crn_voxel_overlap queues two memsets and one launch per 64 grids on stream s and does not wait for the GPU (the
+ * offsets travel as kernel arguments); no workgroup waits for another one.  A workgroup owns CRN_VO_CHUNK consecutive
+ * voxels of one grid, each of its waves an equal share of them.  Rows are read with 16-byte loads (4 int32 or 16 uint8
+ * voxels per lane per load) between a scalar head, up to the first voxel at which both rows are 16-byte aligned, and a
+ * scalar tail; rows of a and b whose alignments never agree are read with scalar loads throughout.  A lane merges equal
+ * neighbouring pairs before it counts and keeps the (0, 0) and bad counts in registers, reduced once per wave.  A grid
+ * with at most CRN_VO_LDS_ENTRIES entries is counted in LDS (u32 atomics) and the non-zero entries are added to the
+ * table at the end (64-bit atomics); a larger table receives the merged runs directly.  Integer adds only: the result is
+ * the same from run to run and equal to the host twin's; nothing depends on crn_set_deterministic.
+ * crn_voxel_overlap_tiles writes (CRN_VO_CHUNK, CRN_VO_LDS_ENTRIES, CRN_VO_MAX_TABLE_ENTRIES).
+ *
+ * Host twin (HOST memory, same contract without the cap on the tables together, identical results): chunks of
+ * CRN_VO_CHUNK voxels are spread over num_threads (<= 0: all), every thread counts into tables of its own, summed at
+ * the end; tables above 2^20 entries are added to directly.                                                       */
+#define CRN_VO_CHUNK 65536
+#define CRN_VO_LDS_ENTRIES 16384
+#define CRN_VO_MAX_TABLE_ENTRIES (1 << 26)
+int crn_voxel_overlap_tiles(int32_t* out3);
+size_t crn_voxel_overlap_workspace_bytes(int N, const int64_t* table_offsets);
+int crn_voxel_overlap(const void* a, const int64_t* strides_a, int dtype_a, const void* b, const int64_t* strides_b,
+                      int dtype_b, int N, int D, int H, int W, const int64_t* num_a, const int64_t* num_b,
+                      const int64_t* table_offsets, int64_t* table, size_t table_bytes, int64_t* bad, crnStream s);
+int crn_voxel_overlap_cpu(const void* a, const int64_t* strides_a, int dtype_a, const void* b, const int64_t* strides_b,
+                          int dtype_b, int N, int D, int H, int W, const int64_t* num_a, const int64_t* num_b,
+                          const int64_t* table_offsets, int64_t* table, int64_t* bad, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
