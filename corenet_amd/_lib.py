@@ -191,6 +191,8 @@ _SIGS = {
     "crn_render_cpu": [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i32],
     "crn_render_raster_tex": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "crn_render_cpu_tex": [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32],
+    "crn_render_raster_geometry": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "crn_render_cpu_geometry": [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32],
     "crn_voxel_faces_count": [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp, vp],
     "crn_voxel_faces_emit": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, sz, vp, vp, vp, vp],
     "crn_voxel_faces_cpu": [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32],

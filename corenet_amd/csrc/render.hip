@@ -199,6 +199,79 @@ __global__ __launch_bounds__(RD_THREADS) void rd_raster_tex_kernel(
   rd_raster_pixel<true>(tri, nrm, mids, mats, M, imgs, H, W, recs, offs, list, out, tex);
 }
 
+// ---------------- geometry buffers ----------------
+// The raster pass again, without shading: same winner rule, then the winner's triangle index, barycentrics, clip w and
+// z_ndc instead of a colour.  The tile's list is walked in chunks staged in LDS: the workgroup copies RD_CHUNK records
+// at a time, one 16-byte load per thread (thread = record * 4 + quarter), and every lane tests the chunk from there (all
+// lanes read one address: a broadcast).  The colour kernels' walk, every lane loading each listed record itself, was
+// measured beside it and was slower; the winner is decided by the key (z, record id) alone, so the
+// outputs do not depend on the walk.
+constexpr int RD_CHUNK = RD_THREADS / 4;
+
+struct crnRdGeomOut {
+  int32_t* tri;     // [I][H][W] or NULL
+  float* bary;      // [I][H][W][3] or NULL
+  float* depth;     // [I][H][W] or NULL
+  float* z;         // [I][H][W] or NULL
+};
+
+__global__ __launch_bounds__(RD_THREADS) void rd_raster_geometry_kernel(
+    const float* __restrict__ tri, const crnRenderImage* __restrict__ imgs, int H, int W, const float* __restrict__ recs,
+    const int64_t* __restrict__ offs, const int32_t* __restrict__ list, crnRdGeomOut out) {
+  __shared__ float4 s_rec[RD_CHUNK * 4];
+  __shared__ int32_t s_id[RD_CHUNK];
+  const int i = blockIdx.y;
+  const crnRenderImage& im = imgs[i];
+  const int tx = (W + RD_T - 1) / RD_T, ntiles = tx * ((H + RD_T - 1) / RD_T);
+  const int tile = blockIdx.x, ty = tile / tx;
+  const int col = (tile - ty * tx) * RD_T + (threadIdx.x & (RD_T - 1)), row = ty * RD_T + threadIdx.x / RD_T;
+  const int64_t b = (int64_t)i * ntiles + tile;
+  const int64_t beg = offs[b], end = offs[b + 1];
+  const int j = threadIdx.x >> 2, quarter = threadIdx.x & 3;
+  float bz = 0.f;
+  int32_t bid = -1;
+  for (int64_t base = beg; base < end; base += RD_CHUNK) {          // uniform bounds: every thread meets every barrier
+    const int n = (int)(end - base < RD_CHUNK ? end - base : RD_CHUNK);
+    if (base != beg) __syncthreads();                               // the previous chunk has been tested by every lane
+    if (j < n) {
+      const int32_t id = list[base + j];
+      s_rec[threadIdx.x] = reinterpret_cast<const float4*>(recs + 16 * (int64_t)id)[quarter];
+      if (quarter == 0) s_id[j] = id;
+    }
+    __syncthreads();
+    for (int k = 0; k < n; ++k) {
+      const int32_t id = s_id[k];
+      crnRdRec r;
+      load_rec(reinterpret_cast<const float*>(s_rec), k, r);
+      float E[3], z;
+      if (rd_fragment(r, col, row, E, z) && rd_wins(z, id, bz, bid)) {
+        bz = z;
+        bid = id;
+      }
+    }
+  }
+  if (col >= W || row >= H) return;
+  const int64_t px = ((int64_t)i * H + row) * W + col;
+  int32_t t = -1;
+  float bary[3] = {0.f, 0.f, 0.f}, depth = INFINITY, z = INFINITY;
+  if (bid >= 0) {
+    crnRdRec r;
+    load_rec(recs, bid, r);
+    float E[3];
+    rd_fragment(r, col, row, E, z);
+    t = im.t0 + (bid - im.inst0);
+    float p[9];
+    for (int q = 0; q < 9; ++q) p[q] = tri[9 * (int64_t)t + q];
+    rd_geometry(im, p, E, bary, depth);
+  }
+  if (out.tri) out.tri[px] = t;
+  if (out.bary) {
+    out.bary[3 * px] = bary[0]; out.bary[3 * px + 1] = bary[1]; out.bary[3 * px + 2] = bary[2];
+  }
+  if (out.depth) out.depth[px] = depth;
+  if (out.z) out.z[px] = z;
+}
+
 // ---------------- voxel faces ----------------
 struct VxLayout {
   int64_t vox;        // per grid
@@ -382,6 +455,27 @@ extern "C" int crn_render_raster_tex(const float* triangles, const float* normal
     hipLaunchKernelGGL(rd_raster_kernel, dim3((unsigned)ntiles, (unsigned)I), dim3(RD_THREADS), 0, st, triangles, normals,
                        material_ids, materials, M, images, H, W, records, bin_offsets, bin_list, out);
   }
+  CRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int crn_render_raster_geometry(const float* triangles, const crnRenderImage* images, int I, int H, int W,
+                                          int max_len, const float* records, int32_t* bin_counts,
+                                          const int64_t* bin_offsets, int32_t* bin_list, int32_t* triangle_index,
+                                          float* barycentrics, float* depth, float* z_ndc, crnStream s) {
+  if (!rd_args_ok(images, I, H, W, max_len) || !bin_counts || !bin_offsets) return CRN_EINVAL;
+  if (!triangle_index && !barycentrics && !depth && !z_ndc) return CRN_EINVAL;
+  if (max_len > 0 && (!triangles || !records || !bin_list)) return CRN_EINVAL;
+  hipStream_t st = (hipStream_t)s;
+  const int ntiles = ((W + RD_T - 1) / RD_T) * ((H + RD_T - 1) / RD_T);
+  if (max_len > 0) {
+    hipLaunchKernelGGL(rd_fill_kernel, dim3((unsigned)crn_cdiv(max_len, 256), (unsigned)I), dim3(256), 0, st, images, H, W,
+                       records, bin_counts, bin_offsets, bin_list);
+    CRN_CHECK_LAUNCH();
+  }
+  const crnRdGeomOut out = {triangle_index, barycentrics, depth, z_ndc};
+  hipLaunchKernelGGL(rd_raster_geometry_kernel, dim3((unsigned)ntiles, (unsigned)I), dim3(RD_THREADS), 0, st, triangles,
+                     images, H, W, records, bin_offsets, bin_list, out);
   CRN_CHECK_LAUNCH();
   return 0;
 }

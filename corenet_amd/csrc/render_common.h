@@ -110,6 +110,21 @@ CRN_RD_HD bool rd_wins(float z, int32_t id, float bz, int32_t bid) {
   return bid < 0 || z < bz || (z == bz && id > bid);
 }
 
+// Geometry of the winning fragment (crn_render_raster_geometry): the perspective-correct weights b_i = E_i / s with
+// s = (E0 + E1) + E2, the ones rd_shade and rd_tex_diffuse interpolate with, and the fragment's clip-space w,
+// sum E_k w_k / s with w_k the fourth component of vp . (p_k, 1).  p: the triangle's 9 world coordinates.
+CRN_RD_HD void rd_geometry(const crnRenderImage& im, const float* p, const float E[3], float b[3], float& depth) {
+  const float s = (E[0] + E[1]) + E[2];
+  float w[3];
+  for (int k = 0; k < 3; ++k) {
+    float c[4];
+    rd_xform4(im.vp, p[3 * k], p[3 * k + 1], p[3 * k + 2], c);
+    w[k] = c[3];
+  }
+  for (int i = 0; i < 3; ++i) b[i] = E[i] / s;
+  depth = ((E[0] * w[0] + E[1] * w[1]) + E[2] * w[2]) / s;
+}
+
 CRN_RD_HD float rd_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 CRN_RD_HD void rd_normalize(float* v) {

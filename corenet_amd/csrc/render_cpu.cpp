@@ -32,13 +32,14 @@ void for_tasks(int n, int num_threads, F fn) {
   for (auto& x : th) x.join();
 }
 
-void render_image(const float* tri, const float* nrm, const int32_t* mids, const float* mats, int M,
-                  const crnRenderImage& im, int H, int W, uint8_t* out, const crnRdTex& tex) {
+// The setup records of an image's range and, per pixel, the winning record id (-1: none) and its z_ndc.
+void winners(const float* tri, const crnRenderImage& im, int H, int W, std::vector<crnRdRec>& recs,
+             std::vector<float>& bz, std::vector<int32_t>& bid) {
   const int64_t np = (int64_t)H * W;
-  std::vector<float> bz(np, 0.f);
-  std::vector<int32_t> bid(np, -1);
+  bz.assign(np, 0.f);
+  bid.assign(np, -1);
   const int len = im.t1 - im.t0;
-  std::vector<crnRdRec> recs(len > 0 ? len : 0);
+  recs.resize(len > 0 ? len : 0);
   for (int k = 0; k < len; ++k) {
     crnRdRec& r = recs[k];
     if (!rd_setup(im, H, W, tri + 9 * (int64_t)(im.t0 + k), r)) continue;
@@ -53,6 +54,14 @@ void render_image(const float* tri, const float* nrm, const int32_t* mids, const
         }
       }
   }
+}
+
+void render_image(const float* tri, const float* nrm, const int32_t* mids, const float* mats, int M,
+                  const crnRenderImage& im, int H, int W, uint8_t* out, const crnRdTex& tex) {
+  std::vector<crnRdRec> recs;
+  std::vector<float> bz;
+  std::vector<int32_t> bid;
+  winners(tri, im, H, W, recs, bz, bid);
   for (int row = 0; row < H; ++row)
     for (int col = 0; col < W; ++col) {
       const int64_t p = (int64_t)row * W + col;
@@ -79,7 +88,53 @@ void render_image(const float* tri, const float* nrm, const int32_t* mids, const
     }
 }
 
+// The requested geometry outputs of one image (each pointer at the image's first pixel, or NULL).
+void geometry_image(const float* tri, const crnRenderImage& im, int H, int W, int32_t* out_tri, float* out_bary,
+                    float* out_depth, float* out_z) {
+  std::vector<crnRdRec> recs;
+  std::vector<float> bz;
+  std::vector<int32_t> bid;
+  winners(tri, im, H, W, recs, bz, bid);
+  for (int row = 0; row < H; ++row)
+    for (int col = 0; col < W; ++col) {
+      const int64_t p = (int64_t)row * W + col;
+      int32_t t = -1;
+      float bary[3] = {0.f, 0.f, 0.f}, depth = INFINITY, z = INFINITY;
+      if (bid[p] >= 0) {
+        const int k = bid[p] - im.inst0;
+        float E[3];
+        rd_fragment(recs[k], col, row, E, z);
+        t = im.t0 + k;
+        rd_geometry(im, tri + 9 * (int64_t)t, E, bary, depth);
+      }
+      if (out_tri) out_tri[p] = t;
+      if (out_bary) {
+        out_bary[3 * p] = bary[0]; out_bary[3 * p + 1] = bary[1]; out_bary[3 * p + 2] = bary[2];
+      }
+      if (out_depth) out_depth[p] = depth;
+      if (out_z) out_z[p] = z;
+    }
+}
+
 }  // namespace
+
+extern "C" int crn_render_cpu_geometry(const float* triangles, const crnRenderImage* images, int I, int H, int W,
+                                       int32_t* triangle_index, float* barycentrics, float* depth, float* z_ndc,
+                                       int num_threads) {
+  if (!images || I < 1 || H < 1 || W < 1) return CRN_EINVAL;
+  if (!triangle_index && !barycentrics && !depth && !z_ndc) return CRN_EINVAL;
+  for (int i = 0; i < I; ++i) {
+    if (images[i].t1 < images[i].t0) return CRN_EINVAL;
+    if (images[i].t1 > images[i].t0 && !triangles) return CRN_EINVAL;
+  }
+  const int64_t np = (int64_t)H * W;
+  for_tasks(I, num_threads, [&](int i) {
+    geometry_image(triangles, images[i], H, W, triangle_index ? triangle_index + i * np : nullptr,
+                   barycentrics ? barycentrics + 3 * i * np : nullptr, depth ? depth + i * np : nullptr,
+                   z_ndc ? z_ndc + i * np : nullptr);
+  });
+  return 0;
+}
 
 extern "C" int crn_render_cpu(const float* triangles, const float* normals, const int32_t* material_ids,
                               const float* materials, int M, const crnRenderImage* images, int I, int H, int W,

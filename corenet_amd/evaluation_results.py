@@ -529,6 +529,158 @@ class VisibilityResults:
             "per_class": {int(c): entry(cls == c) for c in sorted(set(cls.tolist()))}}
 
 
+class ReprojectionRows(NamedTuple):
+  """Per scene the silhouette and depth rows; per (scene, foreground class), scene-major like SurfaceRows, the label
+  rows.  Tensors are on pmf's device unless noted."""
+  scene_id: List[str]                      # [B]
+  silhouette: "SilhouetteCounts"           # [B]: covered pixels of prediction and ground truth
+  depth: "DepthErrors"                     # [B]: sums over the pixels both cover
+  scene_index: t.Tensor                    # i64 [R], host
+  class_index: t.Tensor                    # i64 [R], host: 1 .. C - 1
+  class_scene_id: List[str]                # [R]
+  class_intersection: t.Tensor             # i64 [R]: pixels with the class's label in both label images
+  class_union: t.Tensor                    # i64 [R]
+  class_iou: t.Tensor                      # f64 [R], NaN where the union is 0
+
+
+def reprojection_metrics_for_batch(pmf: t.Tensor, ex, task_type, image_size: Optional[Tuple[int, int]] = None,
+                                   level: float = 0.5, gt: str = "grid") -> ReprojectionRows:
+  """Image-space agreement of prediction and ground truth seen from the input camera (corenet_amd.image_metrics on
+  render.render_geometry).
+
+  The prediction is the label grid of extract_labels, emptied where the winning probability is not above level (for
+  level >= 0.5 a voxel carries class k iff pmf[b, k] > level, the set the other metrics use), drawn as the exposed faces
+  of its voxels (render.voxel_faces through inverse(ex.v2x_transform[b]): view space, as in visualize_output).  The
+  ground truth is ex.grid's faces built the same way (gt="grid") or the scene's view-space triangles ex.vertices, a
+  pixel's label being the mesh label of its triangle (gt="mesh").  Both are drawn from ex.camera_transform[b] without
+  culling in ONE render_geometry call of 2 B images of image_size (default: the input image's (H, W)).  Per scene: the
+  silhouette intersection, union and IoU; the depth-error sums over the pixels both sides cover (depth is the distance
+  along the view axis); per (scene, foreground class) the intersection, union and IoU of the two label images -- for
+  fg_bg the one class is the scene's label as extract_labels defines it, i.e. the silhouette again.  With gt="grid" a
+  prediction equal to the ground truth draws the same triangles twice: IoU exactly 1 and every depth sum exactly 0."""
+  from corenet_amd import image_metrics as IM
+  task = _task(task_type)
+  if gt not in ("grid", "mesh"):
+    raise ValueError(f"reprojection_metrics_for_batch: gt must be 'grid' or 'mesh', got {gt!r}")
+  if pmf.dim() != 5 or pmf.shape[1] < 2:
+    raise ValueError(f"reprojection_metrics_for_batch: pmf must be [B, C >= 2, D, H, W], got {tuple(pmf.shape)}")
+  dev = pmf.device
+  B, C = pmf.shape[:2]
+  K = C - 1
+  if len(ex.scene_id) != B:
+    raise ValueError(f"reprojection_metrics_for_batch: pmf has {B} elements, the batch {len(ex.scene_id)}")
+  if task == "fg_bg" and K != 1:
+    raise ValueError(f"reprojection_metrics_for_batch: fg_bg expects 2 classes, pmf has {C}")
+  if tuple(ex.grid.shape) != (B,) + tuple(pmf.shape[2:]):
+    raise ValueError(f"reprojection_metrics_for_batch: ex.grid is {tuple(ex.grid.shape)}, pmf {tuple(pmf.shape)}")
+  if image_size is None:
+    image_size = tuple(ex.input_image.shape[-2:])
+  mesh_labels = [t.as_tensor(v).to(t.int64).cpu().reshape(-1) for v in ex.mesh_labels]
+  if task == "fg_bg":
+    if any(v.shape != (1,) for v in mesh_labels):
+      raise ValueError("reprojection_metrics_for_batch: fg_bg expects one mesh label per scene")
+    scene_label = t.cat(mesh_labels)
+    num_labels = int(scene_label.max()) + 1
+    if int(scene_label.min()) < 1:
+      raise ValueError(f"reprojection_metrics_for_batch: mesh labels must be positive, got {scene_label.tolist()}")
+  else:
+    num_labels = C
+  pred_lbl, gt_lbl = extract_labels(pmf, ex, task)
+  pred_lbl = pred_lbl * (pmf.amax(dim=1) > level)
+  # label 0 is not drawn; what the other labels look like does not matter
+  palette = t.zeros((num_labels, 3), dtype=t.float32)
+  palette[0] = -1.0
+  v2x_inv = [ex.v2x_transform[b].detach().cpu().to(t.float32).inverse() for b in range(B)]
+  cams = t.stack([ex.camera_transform[b].detach().cpu().to(t.float32) for b in range(B)])
+  if gt == "grid":
+    grids = t.cat([pred_lbl, gt_lbl.to(dev, t.int32)], 0)
+    faces = render.voxel_faces(grids, palette, t.stack(v2x_inv + v2x_inv))
+    tri, tri_label = faces.triangles, faces.material_ids
+    counts = faces.num_triangles.cpu()
+  else:
+    faces = render.voxel_faces(pred_lbl, palette, t.stack(v2x_inv))
+    mesh_num_tri = [t.as_tensor(v).to(t.int64).cpu().reshape(-1) for v in ex.mesh_num_tri]
+    if any(n.shape != l.shape for n, l in zip(mesh_num_tri, mesh_labels)) or \
+        sum(int(n.sum()) for n in mesh_num_tri) != ex.vertices.shape[0]:
+      raise ValueError("reprojection_metrics_for_batch: ex.mesh_num_tri, ex.mesh_labels and ex.vertices disagree")
+    tri = t.cat([faces.triangles, ex.vertices.to(dev, t.float32)], 0)
+    gt_label = t.cat([t.repeat_interleave(l, n) for l, n in zip(mesh_labels, mesh_num_tri)]).to(dev, t.int32)
+    tri_label = t.cat([faces.material_ids, gt_label], 0)
+    counts = t.cat([faces.num_triangles.cpu(), t.stack([n.sum() for n in mesh_num_tri])])
+  start = t.cumsum(counts, 0) - counts
+  ranges = t.stack([start, start + counts], 1)
+  buffers = render.render_geometry(tri, ranges, t.cat([cams, cams], 0), image_size, cull_back_facing=False,
+                                   outputs=("triangle_index", "depth"))
+  labels = render.gather_triangle_attribute(buffers, tri_label, 0)
+  mask = buffers.mask
+  silhouette = IM.silhouette_counts(mask[:B], mask[B:])
+  depth = IM.depth_errors(buffers.depth[:B], buffers.depth[B:], mask[:B] & mask[B:])
+  table = IM.label_image_overlaps(labels[:B], labels[B:], num_labels)       # [B, pred, gt]
+  diag = t.diagonal(table, dim1=1, dim2=2)
+  union = table.sum(2) + table.sum(1) - diag                                 # [B, num_labels]
+  rows = t.arange(B * K)
+  scene_index, class_index = rows // K, rows % K + 1
+  label_of_row = (scene_label if task == "fg_bg" else class_index).to(dev)
+  inter, union = diag[scene_index.to(dev), label_of_row], union[scene_index.to(dev), label_of_row]
+  return ReprojectionRows(list(ex.scene_id), silhouette, depth, scene_index, class_index,
+                          [ex.scene_id[b] for b in range(B) for _ in range(K)], inter, union, IM._iou(inter, union))
+
+
+class ReprojectionResults:
+  """Accumulates reprojection_metrics_for_batch over an evaluation run, in the manner of VisibilityResults:
+  add_batch(pmf, ex) takes what pipeline.evaluate_batch returns.  summary() gives, for the silhouette and per class,
+  the mean IoU over the rows that are not NaN and the IoU of the summed counts, and the depth errors pooled from the
+  summed sums: mean_abs, rmse, abs_rel and delta1 (NaN when no pixel is covered on both sides)."""
+
+  def __init__(self, task_type="fg_bg", image_size: Optional[Tuple[int, int]] = None, level: float = 0.5,
+               gt: str = "grid"):
+    self.task_type, self.image_size, self.level, self.gt = task_type, image_size, level, gt
+    self.scene_id: List[str] = []
+    self._scene: List[Tuple[t.Tensor, ...]] = []      # silhouette (intersection, union, iou) + the five depth fields
+    self._class: List[Tuple[t.Tensor, ...]] = []      # class_index, intersection, union, iou
+
+  def add_batch(self, pmf: t.Tensor, ex) -> ReprojectionRows:
+    rows = reprojection_metrics_for_batch(pmf, ex, self.task_type, image_size=self.image_size, level=self.level,
+                                          gt=self.gt)
+    self.scene_id += rows.scene_id
+    self._scene.append(tuple(x.cpu() for x in tuple(rows.silhouette) + tuple(rows.depth)))
+    self._class.append((rows.class_index, rows.class_intersection.cpu(), rows.class_union.cpu(), rows.class_iou.cpu()))
+    return rows
+
+  def rows(self) -> Dict[str, t.Tensor]:
+    """Every row added so far, on the host.  Per scene [S]: intersection, union (i64), iou (f64), depth_count (i64),
+    depth_abs_sum, depth_sq_sum, depth_abs_rel_sum (f64), depth_delta1_count (i64); per (scene, class) [R]: class_index,
+    class_intersection, class_union (i64), class_iou (f64)."""
+    i64, f64 = t.int64, t.float64
+    scene = (("intersection", i64), ("union", i64), ("iou", f64), ("depth_count", i64), ("depth_abs_sum", f64),
+             ("depth_sq_sum", f64), ("depth_abs_rel_sum", f64), ("depth_delta1_count", i64))
+    cls = (("class_index", i64), ("class_intersection", i64), ("class_union", i64), ("class_iou", f64))
+    out = {}
+    for names, parts in ((scene, self._scene), (cls, self._class)):
+      for c, (name, dtype) in enumerate(names):
+        out[name] = t.cat([p[c] for p in parts]) if parts else t.zeros(0, dtype=dtype)
+    return out
+
+  def summary(self) -> Dict:
+    r = self.rows()
+    nan = t.full((), float("nan"), dtype=t.float64)
+
+    def entry(inter, union, iou):
+      i, u = inter.sum(), union.sum()
+      pooled = i.to(t.float64) / u.to(t.float64) if int(u) > 0 else nan
+      return {"mean_iou": float(_nanmean(iou)), "pooled_iou": float(pooled),
+              "num_rows": int((~t.isnan(iou)).sum())}
+    n = r["depth_count"].sum().to(t.float64)
+    div = lambda x: float(x.sum().to(t.float64) / n) if float(n) > 0 else float("nan")
+    cls = r["class_index"]
+    return {"silhouette": entry(r["intersection"], r["union"], r["iou"]),
+            "per_class": {int(c): entry(r["class_intersection"][cls == c], r["class_union"][cls == c],
+                                        r["class_iou"][cls == c]) for c in sorted(set(cls.tolist()))},
+            "depth": {"num_pixels": int(n), "mean_abs": div(r["depth_abs_sum"]),
+                      "rmse": div(r["depth_sq_sum"]) ** 0.5, "abs_rel": div(r["depth_abs_rel_sum"]),
+                      "delta1": div(r["depth_delta1_count"])}}
+
+
 class InstanceRows(NamedTuple):
   """Per (scene, class) the panoptic counts, and one row per ground-truth object, scene-major in mesh order."""
   scene_id: List[str]                      # [B]

@@ -121,6 +121,61 @@ def _texture_args(tex_coords, textures, texture_indices, T: int, M: int, dev) ->
                    texels)
 
 
+def _triangles(triangles) -> t.Tensor:
+  triangles = t.as_tensor(triangles, dtype=t.float32).contiguous()
+  if triangles.dim() != 3 or triangles.shape[1:] != (3, 3):
+    raise ValueError(f"render: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+  return triangles
+
+
+def _ranges_and_cameras(ranges, view_projections, H: int, W: int, T: int) -> Tuple[t.Tensor, t.Tensor]:
+  """The checked triangle ranges int64 [I, 2] and view-projections f32 [I, 4, 4] of a render call, on the host."""
+  ranges = _host(ranges, t.int64).reshape(-1, 2)
+  I = ranges.shape[0]
+  if I < 1 or H < 1 or W < 1:
+    raise ValueError("render: need at least one image of positive size")
+  if (ranges[:, 0] < 0).any() or (ranges[:, 1] < ranges[:, 0]).any() or (ranges[:, 1] > T).any() or T >= 1 << 31:
+    raise ValueError("render: every range must satisfy 0 <= t0 <= t1 <= T < 2^31")
+  return ranges, _host(view_projections).reshape(I, 4, 4)
+
+
+def _image_records(ranges: t.Tensor, vps: t.Tensor, cull_back_facing) -> Tuple[np.ndarray, int, int]:
+  """crnRenderImage[I] as float32 words with the fields every raster call reads (vp, cull, t0, t1, inst0) filled in and
+  the rest zero, the number of (image, triangle) pairs and the longest range."""
+  I = ranges.shape[0]
+  cull = _host(cull_back_facing, t.int64).reshape(-1).expand(I)
+  lens = ranges[:, 1] - ranges[:, 0]
+  inst0 = t.cumsum(lens, 0) - lens
+  num_inst = int(lens.sum())
+  if num_inst >= 1 << 31:
+    raise ValueError("render: at most 2^31 - 1 (image, triangle) pairs per call")
+  rec = np.zeros((I, _IMAGE_WORDS), np.float32)
+  rec[:, :16] = vps.reshape(I, 16).numpy()
+  ints = rec.view(np.int32)
+  ints[:, 31] = cull.numpy()
+  ints[:, 33] = ranges[:, 0].numpy()
+  ints[:, 34] = ranges[:, 1].numpy()
+  ints[:, 35] = inst0.numpy()
+  return rec, num_inst, int(lens.max())
+
+
+def _bin(lib, triangles: t.Tensor, images: t.Tensor, I: int, H: int, W: int, max_len: int, num_inst: int):
+  """crn_render_bin on the triangles' device -> (images there, records, counts, offsets, the sized tile lists, stream)."""
+  from corenet_amd import _lib as L
+  dev = triangles.device
+  images = images.to(dev)
+  ntiles = ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
+  records = t.empty((max(num_inst, 1), 16), dtype=t.float32, device=dev)
+  counts = t.empty(I * ntiles, dtype=t.int32, device=dev)
+  offsets = t.empty(I * ntiles + 1, dtype=t.int64, device=dev)
+  s = L.stream()
+  lib.crn_render_bin(triangles.data_ptr(), images.data_ptr(), I, H, W, max_len, num_inst, records.data_ptr(),
+                     counts.data_ptr(), offsets.data_ptr(), s)
+  total = int(offsets[-1].item())                                       # the call's one synchronisation
+  bins = t.empty(max(total, 1), dtype=t.int32, device=dev)
+  return images, records, counts, offsets, bins, s
+
+
 def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tensor, ranges, view_projections,
                  image_size: Tuple[int, int], normals: Optional[t.Tensor] = None, normal_modes=None,
                  light_positions=None, light_colors=(1.0, 1.0, 1.0), ambient_light_colors=(0.2, 0.2, 0.2),
@@ -141,9 +196,7 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
   (tile, triangle) pairs."""
   H, W = (int(v) for v in image_size)
   dev = triangles.device
-  triangles = t.as_tensor(triangles, dtype=t.float32).contiguous()
-  if triangles.dim() != 3 or triangles.shape[1:] != (3, 3):
-    raise ValueError(f"render: triangles must be [T, 3, 3], got {tuple(triangles.shape)}")
+  triangles = _triangles(triangles)
   T = triangles.shape[0]
   material_ids = t.as_tensor(material_ids).to(dev, t.int32).contiguous()
   materials = t.as_tensor(materials, dtype=t.float32).to(dev).contiguous()
@@ -154,13 +207,8 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
     if normals.shape != triangles.shape:
       raise ValueError("render: normals must have the triangles' shape")
   tex = _texture_args(tex_coords, textures, texture_indices, T, materials.shape[0], dev)
-  ranges = _host(ranges, t.int64).reshape(-1, 2)
+  ranges, vps = _ranges_and_cameras(ranges, view_projections, H, W, T)
   I = ranges.shape[0]
-  if I < 1 or H < 1 or W < 1:
-    raise ValueError("render: need at least one image of positive size")
-  if (ranges[:, 0] < 0).any() or (ranges[:, 1] < ranges[:, 0]).any() or (ranges[:, 1] > T).any() or T >= 1 << 31:
-    raise ValueError("render: every range must satisfy 0 <= t0 <= t1 <= T < 2^31")
-  vps = _host(view_projections).reshape(I, 4, 4)
   if normal_modes is None:
     normal_modes = t.full((I,), 1 if normals is not None else 0, dtype=t.int64)
   normal_modes = _host(normal_modes, t.int64).reshape(-1).expand(I)
@@ -168,41 +216,18 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
     raise ValueError("render: normal modes 1 and 2 need normals")
   cams = t.stack([camera_position(vps[i]) for i in range(I)])
   lights = cams if light_positions is None else _rows(light_positions, I, 3, "light_positions")
-  cull = _host(cull_back_facing, t.int64).reshape(-1).expand(I)
-  lens = ranges[:, 1] - ranges[:, 0]
-  inst0 = t.cumsum(lens, 0) - lens
-  num_inst = int(lens.sum())
-  if num_inst >= 1 << 31:
-    raise ValueError("render: at most 2^31 - 1 (image, triangle) pairs per call")
-  rec = np.zeros((I, _IMAGE_WORDS), np.float32)
-  rec[:, :16] = vps.reshape(I, 16).numpy()
+  rec, num_inst, max_len = _image_records(ranges, vps, cull_back_facing)
   rec[:, 16:19] = lights.numpy()
   rec[:, 19:22] = cams.numpy()
   rec[:, 22:25] = _rows(light_colors, I, 3, "light_colors").numpy()
   rec[:, 25:28] = _rows(ambient_light_colors, I, 3, "ambient_light_colors").numpy()
   rec[:, 28:31] = _rows(clear_colors, I, 3, "clear_colors").numpy()
-  ints = rec.view(np.int32)
-  ints[:, 31] = cull.numpy()
-  ints[:, 32] = normal_modes.numpy()
-  ints[:, 33] = ranges[:, 0].numpy()
-  ints[:, 34] = ranges[:, 1].numpy()
-  ints[:, 35] = inst0.numpy()
+  rec.view(np.int32)[:, 32] = normal_modes.numpy()
   images = t.from_numpy(rec)
-  max_len = int(lens.max())
   M = materials.shape[0]
   lib = _lib()
   if dev.type == "cuda":
-    from corenet_amd import _lib as L
-    images = images.to(dev)
-    ntiles = ((H + TILE - 1) // TILE) * ((W + TILE - 1) // TILE)
-    records = t.empty((max(num_inst, 1), 16), dtype=t.float32, device=dev)
-    counts = t.empty(I * ntiles, dtype=t.int32, device=dev)
-    offsets = t.empty(I * ntiles + 1, dtype=t.int64, device=dev)
-    s = L.stream()
-    lib.crn_render_bin(triangles.data_ptr(), images.data_ptr(), I, H, W, max_len, num_inst, records.data_ptr(),
-                       counts.data_ptr(), offsets.data_ptr(), s)
-    total = int(offsets[-1].item())                                     # the call's one synchronisation
-    bins = t.empty(max(total, 1), dtype=t.int32, device=dev)
+    images, records, counts, offsets, bins, s = _bin(lib, triangles, images, I, H, W, max_len, num_inst)
     out = t.empty((I, H, W, 3), dtype=t.uint8, device=dev)
     if tex is None:
       lib.crn_render_raster(triangles.data_ptr(), None if normals is None else normals.data_ptr(),
@@ -224,6 +249,105 @@ def render_batch(triangles: t.Tensor, material_ids: t.Tensor, materials: t.Tenso
     lib.crn_render_cpu_tex(triangles.data_ptr(), None if normals is None else normals.data_ptr(),
                            material_ids.data_ptr(), materials.data_ptr(), M, images.data_ptr(), I, H, W, out.data_ptr(),
                            *tex.abi(), t.get_num_threads())
+  return out
+
+
+GEOMETRY_OUTPUTS = ("triangle_index", "barycentrics", "depth", "z_ndc")
+
+
+class GeometryBuffers(NamedTuple):
+  """What the raster stage decides per pixel (render_geometry); an output that was not asked for is None."""
+  triangle_index: Optional[t.Tensor]   # int32 [I, H, W]: index into the call's triangles, -1 on background
+  barycentrics: Optional[t.Tensor]     # f32 [I, H, W, 3]: perspective-correct weights of the winner's vertices, 0 on background
+  depth: Optional[t.Tensor]            # f32 [I, H, W]: clip-space w of the fragment, +inf on background
+  z_ndc: Optional[t.Tensor]            # f32 [I, H, W]: the depth-test value in [-1, 1], +inf on background
+
+  @property
+  def mask(self) -> t.Tensor:
+    """bool [I, H, W]: the pixels a triangle covers (the silhouette)."""
+    if self.triangle_index is None:
+      raise ValueError("render: mask needs the triangle_index output")
+    return self.triangle_index >= 0
+
+
+def render_geometry(triangles: t.Tensor, ranges, view_projections, image_size: Tuple[int, int], cull_back_facing=False,
+                    *, outputs: Sequence[str] = GEOMETRY_OUTPUTS) -> GeometryBuffers:
+  """The geometry of I images of image_size = (H, W) instead of their colour -> GeometryBuffers on the triangles' device.
+
+  triangles, ranges, view_projections and cull_back_facing are render_batch's, with the same checks.  Every pixel's
+  winner is the triangle render_batch shades there (module docstring: coverage, z_ndc in [-1, 1], nearest, the later
+  triangle on equal depth).  outputs names the tensors to compute, any non-empty subset of GEOMETRY_OUTPUTS:
+    triangle_index  the winner's index into triangles (not relative to the image's range); -1 on background
+    barycentrics    b_i = E_i / (E0 + E1 + E2), the weights render_batch interpolates position and texture
+                    coordinates with; they sum to 1 up to rounding; 0 on background
+    depth           the fragment's clip-space w, sum b_i w_i; for transformations.perspective_lh / perspective_rh
+                    projections (camera_util.perspective_projection, the dataset's camera_transform) that is the
+                    distance from the eye along the view axis; +inf on background
+    z_ndc           the value of the depth test; +inf on background
+  The GPU kernel and the host twin agree bit for bit on all four.  On the GPU the call synchronises once, as
+  render_batch does."""
+  H, W = (int(v) for v in image_size)
+  dev = triangles.device
+  triangles = _triangles(triangles)
+  outputs = tuple(outputs)
+  unknown = [o for o in outputs if o not in GEOMETRY_OUTPUTS]
+  if unknown or not outputs:
+    raise ValueError(f"render: outputs must be a non-empty subset of {GEOMETRY_OUTPUTS}, got {outputs}")
+  ranges, vps = _ranges_and_cameras(ranges, view_projections, H, W, triangles.shape[0])
+  I = ranges.shape[0]
+  rec, num_inst, max_len = _image_records(ranges, vps, cull_back_facing)
+  images = t.from_numpy(rec)
+  if dev.type not in ("cuda", "cpu"):
+    raise ValueError(f"render: unsupported device {dev}")
+  shapes = {"triangle_index": ((I, H, W), t.int32), "barycentrics": ((I, H, W, 3), t.float32),
+            "depth": ((I, H, W), t.float32), "z_ndc": ((I, H, W), t.float32)}
+  out = {o: (t.empty(shapes[o][0], dtype=shapes[o][1], device=dev) if o in outputs else None) for o in GEOMETRY_OUTPUTS}
+  ptrs = [None if out[o] is None else out[o].data_ptr() for o in GEOMETRY_OUTPUTS]
+  lib = _lib()
+  if dev.type == "cuda":
+    images, records, counts, offsets, bins, s = _bin(lib, triangles, images, I, H, W, max_len, num_inst)
+    lib.crn_render_raster_geometry(triangles.data_ptr(), images.data_ptr(), I, H, W, max_len, records.data_ptr(),
+                                   counts.data_ptr(), offsets.data_ptr(), bins.data_ptr(), *ptrs, s)
+  else:
+    lib.crn_render_cpu_geometry(triangles.data_ptr(), images.data_ptr(), I, H, W, *ptrs, t.get_num_threads())
+  return GeometryBuffers(**out)
+
+
+def _on_pixels(buffers: GeometryBuffers, what: str):
+  if buffers.triangle_index is None:
+    raise ValueError(f"render: {what} needs the triangle_index output")
+  covered = buffers.triangle_index >= 0
+  return covered, buffers.triangle_index.clamp(min=0).to(t.int64)
+
+
+def gather_triangle_attribute(buffers: GeometryBuffers, per_triangle: t.Tensor, fill) -> t.Tensor:
+  """per_triangle [T, ...] (one entry per triangle of the render_geometry call) -> [I, H, W, ...]: the entry of every
+  pixel's triangle, `fill` on background.  Label images (voxel_faces' material_ids are material_base + label), object
+  ids, flat normals."""
+  covered, index = _on_pixels(buffers, "gather_triangle_attribute")
+  per_triangle = t.as_tensor(per_triangle).to(index.device)
+  if per_triangle.dim() < 1 or (per_triangle.shape[0] == 0 and bool(covered.any())):
+    raise ValueError(f"render: per_triangle must be [T, ...], got {tuple(per_triangle.shape)}")
+  out = t.empty(tuple(index.shape) + tuple(per_triangle.shape[1:]), dtype=per_triangle.dtype, device=index.device)
+  out[...] = fill
+  out[covered] = per_triangle[index[covered]]
+  return out
+
+
+def interpolate_vertex_attribute(buffers: GeometryBuffers, per_vertex: t.Tensor, fill) -> t.Tensor:
+  """per_vertex [T, 3, K] -> [I, H, W, K]: sum_i b_i a_i at every covered pixel (perspective-correct), `fill` on
+  background.  View-space positions (per_vertex = triangles), smooth normals, texture coordinates."""
+  covered, index = _on_pixels(buffers, "interpolate_vertex_attribute")
+  if buffers.barycentrics is None:
+    raise ValueError("render: interpolate_vertex_attribute needs the barycentrics output")
+  per_vertex = t.as_tensor(per_vertex).to(index.device)
+  if per_vertex.dim() != 3 or per_vertex.shape[1] != 3:
+    raise ValueError(f"render: per_vertex must be [T, 3, K], got {tuple(per_vertex.shape)}")
+  out = t.empty(tuple(index.shape) + (per_vertex.shape[2],), dtype=per_vertex.dtype, device=index.device)
+  out[...] = fill
+  b = buffers.barycentrics[covered].to(per_vertex.dtype)[:, :, None]
+  a = per_vertex[index[covered]]
+  out[covered] = (b[:, 0] * a[:, 0] + b[:, 1] * a[:, 1]) + b[:, 2] * a[:, 2]
   return out
 
 

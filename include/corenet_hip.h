@@ -763,6 +763,28 @@ int crn_render_cpu_tex(const float* triangles, const float* normals, const int32
                        int M, const crnRenderImage* images, int I, int H, int W, uint8_t* out,
                        const float* texcoords, const int32_t* texture_ids, const uint8_t* textures, int L, int Ht, int Wt,
                        int num_threads);
+/* Geometry buffers: what the raster stage decides per pixel, instead of a colour.  crn_render_raster_geometry follows
+ * crn_render_bin exactly as crn_render_raster does (same images, records and bins; it consumes bin_counts and does not
+ * wait for the GPU).  Four outputs, each NULL or contiguous [I][H][W] (barycentrics [I][H][W][3]); at least one must be
+ * given (CRN_EINVAL otherwise):
+ *   triangle_index  the index t into `triangles` of the pixel's winner, t0 + (record id - inst0) -- not the record id;
+ *                   -1 where no fragment survives.  The winner is the colour renderer's: coverage with the top-left
+ *                   rule, z_ndc in [-1, 1], the smallest z, the later triangle on equal z, culling per image.
+ *   barycentrics    b_i = E_i / ((E0 + E1) + E2), the perspective-correct weights the shader interpolates position and
+ *                   texture coordinates with; 0 on background.
+ *   z_ndc           the very float that decided the winner; +inf on background.
+ *   depth           the clip-space w of the fragment, ((E0 w0 + E1 w1) + E2 w2) / ((E0 + E1) + E2) with w_k the fourth
+ *                   component of vp . (p_k, 1); +inf on background.  For a projection whose last row is (0, 0, 1, 0)
+ *                   after the view transform (transformations.perspective_lh, the dataset's camera_transform) this is
+ *                   the distance along the view axis.
+ * Of crnRenderImage only vp, cull, t0, t1 and inst0 are read; lights, clear colour and normal_mode are ignored.  One
+ * copy of the arithmetic (csrc/render_common.h, rd_geometry), compiled without contraction: the GPU and the host twin
+ * agree bit for bit on all four outputs.  DESIGN section 21.                                                        */
+int crn_render_raster_geometry(const float* triangles, const crnRenderImage* images, int I, int H, int W, int max_len,
+                               const float* records, int32_t* bin_counts, const int64_t* bin_offsets, int32_t* bin_list,
+                               int32_t* triangle_index, float* barycentrics, float* depth, float* z_ndc, crnStream s);
+int crn_render_cpu_geometry(const float* triangles, const crnRenderImage* images, int I, int H, int W,
+                            int32_t* triangle_index, float* barycentrics, float* depth, float* z_ndc, int num_threads);
 /* Exposed faces of N label grids labels[n][d][h][w] (int32, contiguous) as the voxel renderer draws them: voxel
  * (x, y, z) = (w, h, d) is a unit cube iff palette[label] (f32 [P][3]) exists and has no negative channel; of its faces
  * +x, -x, +y, -y, +z, -z only those whose neighbour is not drawn (or outside) are emitted, each as two triangles.

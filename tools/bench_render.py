@@ -36,6 +36,42 @@ def batch(B):
   return (noise + 2 * onehot).softmax(1), ex
 
 
+def render_inputs(pmf, ex, grids):
+  """The buffers visualize_output builds for its one render call: per scene 4 triangle ranges x 5 cameras ->
+  (triangles, normals, material_ids, materials, ranges, view_projections, normal_modes, triangle counts)."""
+  from corenet_amd.visualization import camera_util as C
+  from corenet_amd.visualization import render as R
+  from corenet_amd.visualization.colors import DEFAULT_COLOR_PALETTE
+  from corenet_amd.visualization.marching_cubes import to_marching_cubes
+  B = pmf.shape[0]
+  pal = t.as_tensor(DEFAULT_COLOR_PALETTE)
+  v2x_inv = ex.v2x_transform[0].cpu().inverse()
+  objs = pmf[:, 1:].reshape((B * (NC - 1),) + tuple(pmf.shape[2:]))
+  mc_tri, mc_nrm, mc_cnt = to_marching_cubes(objs)
+  faces = R.voxel_faces(grids, pal, v2x_inv)
+  T_mc, T_gt = mc_tri.shape[0], ex.vertices.shape[0]
+  tri = t.cat([mc_tri * (1 / 128.0), ex.vertices, faces.triangles], 0)
+  nrm = t.cat([mc_nrm, t.zeros_like(ex.vertices), faces.normals], 0)
+  mats = t.cat([R.voxel_materials(pal), R.make_materials(pal[1:2])], 0)
+  mid = t.cat([t.full((T_mc + T_gt,), pal.shape[0], dtype=t.int32, device="cuda"), faces.material_ids], 0)
+  mc_cnt, gt_cnt, vx_cnt = mc_cnt.cpu().long().reshape(B, NC - 1).sum(1), [int(n.sum()) for n in ex.mesh_num_tri], faces.num_triangles.cpu()
+  st = lambda c: (t.cumsum(t.as_tensor(c), 0) - t.as_tensor(c)).tolist()
+  mc0, gt0, vx0 = st(mc_cnt), [s + T_mc for s in st(gt_cnt)], [s + T_mc + T_gt for s in st(vx_cnt)]
+  ranges, vps, modes = [], [], []
+  for b in range(B):
+    box = tri[gt0[b]:gt0[b] + gt_cnt[b]].reshape(-1, 3)
+    cams = [ex.camera_transform[b].cpu()] + [C.get_default_camera_for_mesh(box.reshape(-1, 3, 3)) for _ in range(4)]
+    for cam in cams:
+      for r, m in (((mc0[b], mc0[b] + int(mc_cnt[b])), 1), ((gt0[b], gt0[b] + gt_cnt[b]), 0),
+                   ((vx0[b], vx0[b] + int(vx_cnt[b])), 2), ((vx0[B + b], vx0[B + b] + int(vx_cnt[B + b])), 2)):
+        ranges.append(r)
+        vps.append(cam)
+        modes.append(m)
+  counts = {"marching_cubes": T_mc, "gt_meshes": T_gt, "voxel_faces": int(vx_cnt.sum()),
+            "drawn_per_batch": int(sum(r[1] - r[0] for r in ranges))}
+  return tri, nrm, mid, mats, ranges, t.stack(vps), modes, counts
+
+
 def timed(fn, iters, warmup):
   for _ in range(warmup):
     fn()
@@ -72,32 +108,9 @@ def main():
   objs = pmf[:, 1:].reshape((B * (NC - 1),) + tuple(pmf.shape[2:]))
   res["mc_ms"], _ = timed(lambda: marching_cubes(objs, 0.5, matrices=v2x_inv.cuda()), a.iters, a.warmup)
   res["faces_ms"], _ = timed(lambda: R.voxel_faces(grids, pal, v2x_inv, box_matrices=v2x_inv), a.iters, a.warmup)
-  # the render pass alone, on the buffers visualize_output builds: per scene 4 ranges x 5 cameras
-  mc_tri, mc_nrm, mc_cnt = to_marching_cubes(objs)
-  faces = R.voxel_faces(grids, pal, v2x_inv)
-  T_mc, T_gt = mc_tri.shape[0], ex.vertices.shape[0]
-  tri = t.cat([mc_tri * (1 / 128.0), ex.vertices, faces.triangles], 0)
-  nrm = t.cat([mc_nrm, t.zeros_like(ex.vertices), faces.normals], 0)
-  mats = t.cat([R.voxel_materials(pal), R.make_materials(pal[1:2])], 0)
-  mid = t.cat([t.full((T_mc + T_gt,), pal.shape[0], dtype=t.int32, device="cuda"), faces.material_ids], 0)
-  mc_cnt, gt_cnt, vx_cnt = mc_cnt.cpu().long().reshape(B, NC - 1).sum(1), [int(n.sum()) for n in ex.mesh_num_tri], faces.num_triangles.cpu()
-  st = lambda c: (t.cumsum(t.as_tensor(c), 0) - t.as_tensor(c)).tolist()
-  mc0, gt0, vx0 = st(mc_cnt), [s + T_mc for s in st(gt_cnt)], [s + T_mc + T_gt for s in st(vx_cnt)]
-  ranges, vps, modes = [], [], []
-  for b in range(B):
-    box = tri[gt0[b]:gt0[b] + gt_cnt[b]].reshape(-1, 3)
-    cams = [ex.camera_transform[b].cpu()] + [C.get_default_camera_for_mesh(box.reshape(-1, 3, 3)) for _ in range(4)]
-    for cam in cams:
-      for r, m in (((mc0[b], mc0[b] + int(mc_cnt[b])), 1), ((gt0[b], gt0[b] + gt_cnt[b]), 0),
-                   ((vx0[b], vx0[b] + int(vx_cnt[b])), 2), ((vx0[B + b], vx0[B + b] + int(vx_cnt[B + b])), 2)):
-        ranges.append(r)
-        vps.append(cam)
-        modes.append(m)
-  vps = t.stack(vps)
+  tri, nrm, mid, mats, ranges, vps, modes, res["triangles"] = render_inputs(pmf, ex, grids)
   res["render_ms"], _ = timed(lambda: R.render_batch(tri, mid, mats, ranges, vps, (384, 384), normals=nrm,
                                                      normal_modes=modes), a.iters, a.warmup)
-  res["triangles"] = {"marching_cubes": T_mc, "gt_meshes": T_gt, "voxel_faces": int(vx_cnt.sum()),
-                      "drawn_per_batch": int(sum(r[1] - r[0] for r in ranges))}
   res["visualize_output_ms"], res["visualize_output_min_ms"] = timed(lambda: ER.visualize_output(pmf, ex, "semantic"),
                                                                      a.iters, a.warmup)
   res["iters"], res["warmup"] = a.iters, a.warmup
