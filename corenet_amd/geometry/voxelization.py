@@ -20,13 +20,10 @@ def dynamic_tile(partition_lengths: t.Tensor, device=None, total: int = None) ->
   return t.repeat_interleave(t.arange(len(partition_lengths), dtype=t.int32, device=device), n, output_size=total)
 
 
-def voxelize_mesh(triangles, mesh_num_tri, resolution: Tuple[int, int, int], view2voxel,
-                  sub_grid_sampling: bool = False, image_resolution_multiplier: float = 4,
-                  conservative_rasterization: bool = False, projection_depth_multiplier: int = 1,
-                  cuda_device=None) -> t.Tensor:
-  """voxelization.py:32-164.  Returns float32[num_meshes, D, H, W] (or the
-  (2D+1,2H+1,2W+1) sub-grid) on the GPU."""
-  dev = t.device("cuda" if cuda_device is None else f"cuda:{cuda_device}")
+def check_arguments(triangles, mesh_num_tri, view2voxel, sub_grid_sampling, image_resolution_multiplier,
+                    projection_depth_multiplier):
+  """The host half of voxelize_mesh (voxelization.py:98-113): (triangles f32 [T, 3, 3], mesh_num_tri i32 [M], view2voxel f32
+  [M, 4, 4]) wherever they came in; a [4, 4] matrix is expanded to every mesh.  Touches no GPU."""
   triangles = t.as_tensor(triangles, dtype=t.float32)
   assert triangles.shape[1:] == (3, 3)
   mesh_num_tri = t.as_tensor(mesh_num_tri, dtype=t.int32)
@@ -41,6 +38,21 @@ def voxelize_mesh(triangles, mesh_num_tri, resolution: Tuple[int, int, int], vie
         "image_resolution_multiplier must be off if sub_grid_sampling is True")   # :107-109
   if sub_grid_sampling and projection_depth_multiplier == 0:
     raise ValueError("projection_depth_multiplier must be 1 if sub_grid_sampling is True")
+  if projection_depth_multiplier < 1:                 # the reference would build a projection of no or negative depth
+    raise ValueError("projection_depth_multiplier must be at least 1")
+  return triangles, mesh_num_tri, view2voxel
+
+
+def voxelize_mesh(triangles, mesh_num_tri, resolution: Tuple[int, int, int], view2voxel,
+                  sub_grid_sampling: bool = False, image_resolution_multiplier: float = 4,
+                  conservative_rasterization: bool = False, projection_depth_multiplier: int = 1,
+                  cuda_device=None) -> t.Tensor:
+  """voxelization.py:32-164.  Returns float32[num_meshes, D, H, W] (or the
+  (2D+1,2H+1,2W+1) sub-grid) on the GPU."""
+  dev = t.device("cuda" if cuda_device is None else f"cuda:{cuda_device}")
+  triangles, mesh_num_tri, view2voxel = check_arguments(triangles, mesh_num_tri, view2voxel, sub_grid_sampling,
+                                                        image_resolution_multiplier, projection_depth_multiplier)
+  M = len(mesh_num_tri)
   D, H, W = resolution
   tri = triangles.to(dev).contiguous()
   if not mesh_num_tri.is_cuda:

@@ -12,9 +12,11 @@ Pinning status:
   * model forward/backward, BatchRenorm, SampleGrid2d: pinned by golden vectors
     generated from the imported reference (oracle/gen_golden.py ->
     tests/golden/*.npz) -- the reference's tests do not cover them.
-  * surface voxelizer: pinned ONLY by the three known-answer tests of
-    voxelization_test.py:53-147; beyond them "parity unpinned" (the reference
-    uses the NVIDIA GL rasterizer, which cannot run here).
+  * surface voxelizer: the three known-answer tests of
+    voxelization_test.py:53-147, and its geometry by the independent float64
+    reference of tests/voxelize_cases.py (every voxel that reference decides);
+    agreement with the NVIDIA GL rasterizer of the reference on the samples
+    within rounding of a boundary stays unpinned: it cannot run here.
 
 Every function cites the reference file:line it follows.  All tensors are
 fp32 NCHW / NCDHW like the reference.
@@ -441,8 +443,11 @@ def voxelize_mesh(triangles: np.ndarray, mesh_num_tri: Sequence[int], resolution
                   projection_depth_multiplier=1, chunk_pixels: int = 1 << 22) -> np.ndarray:
   """Restatement of voxelization.py:98-164 with the rasterizer written out.
 
-  Rules (PARITY UNPINNED beyond voxelization_test.py:53-147 -- the reference
-  uses the NVIDIA GL rasterizer):
+  Rules (the geometry is pinned by the independent float64 reference of
+  tests/voxelize_cases.py: every voxel it decides must agree; agreement with the
+  NVIDIA GL rasterizer the reference uses, on the samples within rounding of an
+  edge, a clip plane or a voxel border, stays unpinned beyond
+  voxelization_test.py:53-147 -- there is no GL to compare with):
     * vertices -> voxel space with the mesh's view2voxel (voxelize.geom:31-45)
     * dominant axis of the normal picks the projection plane (voxelize.geom:53-55):
       a.x>a.y && a.x>a.z -> screen=(y,z); a.y>a.x && a.y>a.z -> screen=(z,x);
@@ -521,10 +526,12 @@ def voxelize_mesh(triangles: np.ndarray, mesh_num_tri: Sequence[int], resolution
     area = (sx[:, 1] - sx[:, 0]) * (sy[:, 2] - sy[:, 0]) - (sx[:, 2] - sx[:, 0]) * (sy[:, 1] - sy[:, 0])
     alive &= (area != 0) & ~np.isnan(area)
     sgn = np.where(area > 0, one, -one).astype(f)
-    def toint(q):                    # (int) of a finite float; triangles with NaN / inf corners are dropped above
-      return np.where(np.isfinite(q), q, 0).astype(np.int64)
-    smin = lambda s: np.minimum(s[:, 0], np.minimum(s[:, 1], s[:, 2]))
-    smax = lambda s: np.maximum(s[:, 0], np.maximum(s[:, 1], s[:, 2]))
+    smin = lambda s: np.fmin(s[:, 0], np.fmin(s[:, 1], s[:, 2]))
+    smax = lambda s: np.fmax(s[:, 0], np.fmax(s[:, 1], s[:, 2]))
+    # a non-finite corner is an empty box; finite corners are clamped to [-1, R + 1] before the conversion to int, like the kernel
+    alive &= np.isfinite(smin(sx)) & np.isfinite(smax(sx)) & np.isfinite(smin(sy)) & np.isfinite(smax(sy))
+    def toint(q):
+      return np.clip(np.where(np.isfinite(q), q, 0), -one, Rf + one).astype(np.int64)
     x0 = np.maximum(toint(np.floor(smin(sx))) - 1, 0); x1 = np.minimum(toint(np.ceil(smax(sx))) + 1, R)
     y0 = np.maximum(toint(np.floor(smin(sy))) - 1, 0); y1 = np.minimum(toint(np.ceil(smax(sy))) + 1, R)
     alive &= (x1 > x0) & (y1 > y0)
