@@ -175,6 +175,11 @@ _SIGS = {
     "crn_softmax_superres": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "crn_eval_labels": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "crn_eval_labels_cpu": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32],
+    "crn_eval_scores_tiles": [vp],
+    "crn_eval_scores": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "crn_eval_scores_cpu": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32],
+    "crn_score_softmax": [vp, i32, i32, i64, vp, vp],
+    "crn_score_softmax_cpu": [vp, i32, i32, i64, vp, i32],
     "crn_adam_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp],
     "crn_adam_set_hyper": [vp, f32, f32, f32, f32, f32, i32, vp],
     "crn_adam_step_hyper": [vp, vp, vp, vp, i64, vp, vp],

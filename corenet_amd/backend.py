@@ -532,6 +532,17 @@ class HipBackend:
     self.lib.crn_eval_labels(ptr(scores), ptr(gt_i32), ptr(scene_class), B, Cn, K, D, H, W, m, n, ptr(labels), ptr(cm), ptr(bad),
                              _lib.stream())
 
+  def eval_scores(self, scores, from_logits, gt_i32, scene_class, B, Cn, K, D, H, W, m, n, nbins, table, sq, bad):
+    """One native pass of an x m evaluation, binned by score: scores [B, Cn, D, H, W] (a pmf, or logits with from_logits)
+    against gt_i32 into table int64 [K+1, nbins, 2, 2], sq int64 [K+1, 2] and bad int64 [1], all accumulated
+    (crn_eval_scores; scene_class may be None)."""
+    self.lib.crn_eval_scores(ptr(scores), int(bool(from_logits)), ptr(gt_i32), ptr(scene_class), B, Cn, K, D, H, W, m, n, nbins,
+                             ptr(table), ptr(sq), ptr(bad), _lib.stream())
+
+  def score_softmax(self, logits, B, Cn, S, out):
+    """out = the shared softmax of logits [B, Cn, S] over Cn (crn_score_softmax)."""
+    self.lib.crn_score_softmax(ptr(logits), B, Cn, S, ptr(out), _lib.stream())
+
   def adam_step(self, p, g, m, v, n, lr, b1, b2, eps, grad_scale, step):
     self.lib.crn_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), n, lr, b1, b2, eps, grad_scale, step,
                            _lib.stream())

@@ -17,7 +17,11 @@ consistency is reported beside them.
 Quantitative voxel results (evaluation_results.py:185-279): QuantitativeResults accumulates the confusion matrix over the
 dataset's classes on the device (`crn_eval_labels`: from a pmf, or streamed pass by pass at the resolution of the ground
 truth), compute_voxel_metrics turns it into the reference's table (iou / precision / recall per class
-plus the class-agnostic `__global__` column) and MetricsTable.to_csv writes what pandas writes for it, without pandas."""
+plus the class-agnostic `__global__` column) and MetricsTable.to_csv writes what pandas writes for it, without pandas.
+
+Score-level results (no counterpart in the reference): ScoreResults accumulates the per-class score histogram of
+corenet_amd.score_metrics (`crn_eval_scores`) the same way and reports calibration, Brier score,
+average precision and the threshold sweep."""
 from __future__ import annotations
 
 import csv
@@ -917,3 +921,119 @@ class QuantitativeResults:
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "w", newline="") as f:
       f.write(self.metrics.to_csv())
+
+
+def score_metrics_for_batch(pmf: t.Tensor, ex, task_type, nbins: int = 20, num_classes: Optional[int] = None, out=None):
+  """Score-level evaluation of a batch (corenet_amd.score_metrics): the ScoreHistogram of pmf f32
+  [B, C, D, H, W] against ex.grid, from which the reliability diagram, the calibration errors, the Brier score, the
+  threshold curve and average precision follow.  With num_classes (the dataset's class count) an fg_bg batch is scored
+  per dataset class, the scene's mesh label scaling label and row as in QuantitativeResults; without it the rows are the
+  pmf's own channels.  Accumulates into `out` when given; nothing is read back."""
+  from corenet_amd import score_metrics
+  task = _task(task_type)
+  dev = pmf.device
+  scene = scene_classes_of(ex).to(dev) if task == "fg_bg" and num_classes is not None else None
+  return score_metrics.score_histogram(pmf, ex.grid.to(dev, t.int32).contiguous(), num_classes, scene, nbins=nbins, out=out)
+
+
+SCORE_SUMMARY_NAMES = ("ece", "mce", "brier", "ap", "best_threshold", "best_iou", "iou_at_0.5")
+
+
+class ScoreResults:
+  """Accumulates the score histogram of an evaluation run over the dataset's classes (corenet_amd.score_metrics, DESIGN
+  section 22) beside QuantitativeResults' confusion matrix: from a pmf, or streamed pass by pass at the resolution of the
+  ground truth.  The tables live on the device of the first batch; nothing is read back before compute_metrics."""
+
+  def __init__(self, classes: Sequence[str], task_type="fg_bg", nbins: int = 20):
+    from corenet_amd import score_metrics
+    self.classes = [str(c) for c in classes]
+    self.task = _task(task_type)
+    self.nbins = int(nbins)
+    if not 1 <= self.nbins <= score_metrics.MAX_NBINS or (len(self.classes) + 1) * self.nbins > score_metrics.MAX_ENTRIES:
+      raise ValueError(f"ScoreResults: {self.nbins} bins for {len(self.classes)} classes exceed the table of "
+                       f"{score_metrics.MAX_ENTRIES} entries (or the limit of {score_metrics.MAX_NBINS} bins)")
+    self.histogram = None
+    self.reduced = False
+
+  def ensure_tables(self, dev):
+    from corenet_amd import score_metrics
+    if self.histogram is None:
+      self.histogram = score_metrics.empty_histogram(len(self.classes), self.nbins, dev)
+
+  def _batch_args(self, ex, dev):
+    self.ensure_tables(dev)
+    scene = scene_classes_of(ex).to(dev) if self.task == "fg_bg" else None
+    return ex.grid.to(dev, t.int32).contiguous(), scene
+
+  def add_batch(self, pmf: t.Tensor, ex):
+    """Counts a batch from its pmf f32 [B, C, D, H, W]; returns the run's histogram."""
+    from corenet_amd import score_metrics
+    gt, scene = self._batch_args(ex, pmf.device)
+    return score_metrics.score_histogram(pmf, gt, len(self.classes), scene, nbins=self.nbins, out=self.histogram)
+
+  def add_batch_streaming(self, inference, ex):
+    """Counts a batch without a pmf: `inference.predict_score_histogram` (SuperResolutionInference) at the resolution of
+    ex.grid, the tables accumulated pass by pass; returns the run's histogram."""
+    gt, scene = self._batch_args(ex, ex.grid.device)
+    with t.no_grad():
+      return inference.predict_score_histogram(ex.input_image, ex.camera_transform, ex.v2x_transform, ex.grid_sampling_offset,
+                                               tuple(gt.shape[1:]), gt, num_classes=len(self.classes), scene_classes=scene,
+                                               nbins=self.nbins, out=self.histogram)
+
+  def compute_metrics(self, dst: int = 0, group=None):
+    """Sums the tables over the ranks onto rank dst the way the confusion matrix is summed, then reads this rank's count
+    of rejected voxels and raises ValueError when it is not 0.  Returns the histogram on rank dst (None elsewhere)."""
+    if self.histogram is None:
+      raise ValueError("ScoreResults.compute_metrics: no batch was added")
+    h = self.histogram
+    dist_util.reduce_confusion_matrix(h.table, dst, group)
+    dist_util.reduce_confusion_matrix(h.sq, dst, group)
+    bad = int(h.bad.item())
+    if bad:
+      raise ValueError(f"{bad} voxels had a label outside the {len(self.classes)} classes of the dataset, a scene class that "
+                       "does not fit them, or a score that is NaN or outside [0, 1]")
+    self.reduced = True
+    if dist_util.dist.is_initialized() and dist_util.dist.get_rank(group) != dst:
+      return None
+    return h
+
+  def _columns(self) -> Tuple[str, ...]:
+    return tuple(self.classes) + (GLOBAL_CLASS_NAME,)
+
+  def summary(self) -> Dict:
+    """Per class and for the `__global__` row (the class-agnostic foreground): expected and maximum calibration error,
+    Brier score, average precision, the first threshold of maximum IoU with that IoU, and the IoU at threshold 0.5
+    (the first threshold j / nbins >= 0.5).  NaN where a row has no voxel (or no positive, where positives are needed)."""
+    from corenet_amd import score_metrics as SM
+    h = self.histogram
+    if h is None:
+      raise ValueError("ScoreResults.summary: no batch was added")
+    thr, best = SM.best_threshold(h)
+    half = (self.nbins + 1) // 2
+    cols = (SM.expected_calibration_error(h), SM.maximum_calibration_error(h), SM.brier_score(h), SM.average_precision(h),
+            thr, best, SM.threshold_curve(h).iou[:, half])
+    values = t.stack(cols, 1).cpu().tolist()
+    return {name: dict(zip(SCORE_SUMMARY_NAMES, row)) for name, row in zip(self._columns(), values)}
+
+  def write_csv(self, path: str):
+    """One line per (class, threshold) with the curve -- kind `threshold`: value j / nbins, tp, fp, fn, iou, precision,
+    recall -- and one per (class, bin) with the reliability diagram -- kind `bin`: value the bin's lower edge, count,
+    confidence, frequency.  NaN as an empty field, floats in their shortest round-trip form."""
+    from corenet_amd import score_metrics as SM
+    h = self.histogram
+    c, curve, rel = SM.threshold_counts(h), SM.threshold_curve(h), SM.reliability(h)
+    tp, fp, fn = (x.cpu().tolist() for x in c)
+    iou, prec, rec = (x.cpu().tolist() for x in (curve.iou, curve.precision, curve.recall))
+    cnt, conf, freq = (x.cpu().tolist() for x in rel)
+    cell = lambda v: "" if v != v else repr(float(v))
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+      w = csv.writer(f, lineterminator="\n", quoting=csv.QUOTE_MINIMAL)
+      w.writerow(("class", "kind", "value", "tp", "fp", "fn", "iou", "precision", "recall", "count", "confidence", "frequency"))
+      for r, name in enumerate(self._columns()):
+        for j in range(self.nbins + 1):
+          w.writerow([name, "threshold", repr(j / self.nbins), tp[r][j], fp[r][j], fn[r][j], cell(iou[r][j]), cell(prec[r][j]),
+                      cell(rec[r][j]), "", "", ""])
+        for j in range(self.nbins):
+          w.writerow([name, "bin", repr(j / self.nbins), "", "", "", "", "", "", int(cnt[r][j]), cell(conf[r][j]),
+                      cell(freq[r][j])])

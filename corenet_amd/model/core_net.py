@@ -421,6 +421,33 @@ class CoreNet(nn.Module):
         be.eval_labels(logits, gt, scene_classes, B, C, K, D, H, W, m, i, labels, cm, bad)
     return labels
 
+  def multi_offset_score_histogram(self, image: t.Tensor, voxel_projection_matrix: t.Tensor, grid_offsets: t.Tensor,
+                                   resolution_multiplier: int, gt: t.Tensor, num_classes: Optional[int] = None,
+                                   scene_classes: Optional[t.Tensor] = None, nbins: int = 20, out=None):
+    """The score histogram (corenet_amd.score_metrics.ScoreHistogram) of an x m inference against gt int32
+    [B, m*D, m*H, m*W], without the pmf: the encoder runs once, and after every decoder pass `crn_eval_scores` takes that
+    pass's logits through the shared softmax into the per-class table, against the pass's sub-lattice of gt.  No stash of
+    the m^3 passes and no pmf is allocated.  Accumulates into `out` when given.  Arguments, checks, eval-mode and weight
+    handling as multi_offset_labels; m = 1 takes the same path."""
+    m = int(resolution_multiplier)
+    if m < 1:
+      raise ValueError("resolution_multiplier >= 1 expected")
+    from corenet_amd import score_metrics
+    # the tensors are checked once, before anything runs; the passes then go to the kernel directly
+    B, C = image.shape[0], self.engine.num_classes
+    D, H, W = self.engine.resolution
+    K = score_metrics.check_score_args((B, C, D, H, W), image.device, gt, num_classes, scene_classes, m, nbins, out)
+    plan, v2s, offs, n, m = self._multi_offset_encoder(image, voxel_projection_matrix, grid_offsets, m)
+    assert plan.logits.shape == (B, C, D, H, W) and plan.logits.is_contiguous()
+    if out is None:
+      out = score_metrics.empty_histogram(K, nbins, plan.logits.device)
+    be = self.engine.be
+    with t.no_grad():
+      for i in range(n):
+        logits = plan.forward_decoder(v2s, offs[i], training=False)
+        be.eval_scores(logits, True, gt, scene_classes, B, C, K, D, H, W, m, i, int(nbins), out.table, out.sq, out.bad)
+    return out
+
   # fused training step (bench.py / the train hot loop pipeline.py:215-240) ------
   def train_step(self, image: t.Tensor, voxel_projection_matrix: t.Tensor,
                  voxel_sample_locations: t.Tensor, grid: t.Tensor, loss: str = "iou_fgbg",

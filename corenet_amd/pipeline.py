@@ -85,7 +85,7 @@ def evaluate_batch(inference_fn, batch: List[dataset_lib.DatasetElement], task_t
 
 def run_eval(inference, dataset, output_dir: str, task_type: str, batch_size: int, global_rank: int = 0,
              global_world_size: int = 1, resolution: Tuple[int, int, int] = (128, 128, 128), qualitative=None,
-             num_data_workers: int = 0, device="cuda", **voxelization) -> Optional[float]:
+             num_data_workers: int = 0, device="cuda", scores=None, **voxelization) -> Optional[float]:
   """One evaluation run over this rank's share of `dataset` (EvalPipeline.run_eval, pipeline.py:292-343): per batch the
   ground truth is voxelized at `resolution` and scored into the confusion matrix over dataset.classes; at the end the
   matrix is summed over the ranks and rank 0 writes <output_dir>/voxel_metrics.csv and returns the mean IoU over the
@@ -97,6 +97,9 @@ def run_eval(inference, dataset, output_dir: str, task_type: str, batch_size: in
   computed only for the batches a given `qualitative` (evaluation_results.QualitativeResults) wants to draw.  Such a
   batch runs the network twice, encoder and all m^3 decoder passes: once for the pmf to draw and once for the labels.
   device: where the batches and the confusion matrix are put, as in evaluate_batch.
+  scores: an evaluation_results.ScoreResults to feed alongside the confusion matrix (score-level evaluation, DESIGN
+  section 22): streamed pass by pass when the inference streams (`predict_score_histogram`), from the pmf otherwise.  Its
+  tables are summed over the ranks at the end and rank 0 writes <output_dir>/score_metrics.csv.
   voxelization: the keyword arguments of voxelize_batch other than task_type and resolution."""
   from corenet_amd import evaluation_results as results_lib
   loader = create_distributed_loader(dataset, batch_size, global_rank, global_world_size,
@@ -118,12 +121,26 @@ def run_eval(inference, dataset, output_dir: str, task_type: str, batch_size: in
       quantitative.add_batch(pmf, ex)
     if draw:
       qualitative.add_batch(pmf, ex)
+    if scores is not None:
+      if streaming and hasattr(inference, "predict_score_histogram"):
+        scores.add_batch_streaming(inference, ex)
+      else:
+        if pmf is None:
+          with t.no_grad():
+            pmf = inference(ex.input_image, ex.camera_transform, ex.v2x_transform, ex.grid_sampling_offset, resolution)
+        scores.add_batch(pmf, ex)
   if quantitative.confusion_matrix is None:           # a rank without a batch still takes part in the sum
     K = len(quantitative.classes)
     quantitative.confusion_matrix = t.zeros((K, K), dtype=t.int64, device=device)
     quantitative.bad = t.zeros((1,), dtype=t.int32, device=device)
   quantitative.compute_metrics()
+  if scores is not None:
+    if scores.histogram is None:                      # a rank without a batch still takes part in the sum
+      scores.ensure_tables(device)
+    scores.compute_metrics()
   if global_rank != 0:
     return None
   quantitative.write_csv(os.path.join(output_dir, "voxel_metrics.csv"))
+  if scores is not None:
+    scores.write_csv(os.path.join(output_dir, "score_metrics.csv"))
   return quantitative.get_mean_iou()

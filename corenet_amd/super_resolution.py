@@ -7,7 +7,8 @@ Same classes, argument meaning and errors as the reference.  The MI355X-specific
 once per image batch and only the decoder per offset (`CoreNet.multi_offset_pmf`), and the softmax +
 stack + reshape + permute + reshape of super_resolution.py:105-112,124 is one HIP kernel with coalesced
 writes (`crn_softmax_superres`).  `predict_labels` is the evaluation form: labels and confusion matrix per pass
-(`crn_eval_labels`), no stash of the passes and no pmf.
+(`crn_eval_labels`), no stash of the passes and no pmf; `predict_score_histogram` is its score-level
+sibling (`crn_eval_scores`).
 """
 from typing import Optional, Tuple
 
@@ -99,6 +100,22 @@ class SuperResolutionInference:
     return streaming(input_image, camera_transform, v2x_native, offsets, m, gt=gt, num_classes=num_classes,
                      scene_classes=scene_classes, cm=cm, bad=bad)
 
+  def predict_score_histogram(self, input_image: t.Tensor, camera_transform: t.Tensor, view_to_voxel_transform: t.Tensor,
+                              grid_offsets: t.Tensor, output_resolution: Tuple[int, int, int], gt: t.Tensor,
+                              num_classes: Optional[int] = None, scene_classes: Optional[t.Tensor] = None, nbins: int = 20,
+                              out=None):
+    """The score histogram (corenet_amd.score_metrics.ScoreHistogram) of __call__'s pmf against gt int32[B, m*D, m*H, m*W]
+    without the pmf: every native pass goes from logits through the shared softmax into the per-class table
+    (`CoreNet.multi_offset_score_histogram`), accumulated into `out` when given.  The native resolution (m = 1) takes the
+    same path.  TypeError when the wrapped inference function cannot stream scores."""
+    streaming = getattr(self.inference_fn, "score_histogram", None)
+    if streaming is None:
+      raise TypeError(f"{type(self.inference_fn).__name__} has no score_histogram(): predict_score_histogram needs an "
+                      "inference function that streams scores (CoreNetMultiOffset)")
+    m, offsets, v2x_native = self._native_passes(view_to_voxel_transform, grid_offsets, output_resolution)
+    return streaming(input_image, camera_transform, v2x_native, offsets, m, gt, num_classes=num_classes,
+                     scene_classes=scene_classes, nbins=nbins, out=out)
+
 
 class CoreNetMultiOffset(MultiOffsetInferenceFn):
   """The inference_fn of super_resolution_from_state (super_resolution.py:115-126) with encoder reuse."""
@@ -122,6 +139,13 @@ class CoreNetMultiOffset(MultiOffsetInferenceFn):
     """int32[B, m*D, m*H, m*W] labels of the m^3 passes, streamed (`CoreNet.multi_offset_labels`)."""
     return self.model.multi_offset_labels(input_image, self._v2s(camera_transform, view_to_voxel_transform), grid_offsets,
                                           m, gt=gt, num_classes=num_classes, scene_classes=scene_classes, cm=cm, bad=bad)
+
+  def score_histogram(self, input_image, camera_transform, view_to_voxel_transform, grid_offsets, m, gt, num_classes=None,
+                      scene_classes=None, nbins=20, out=None):
+    """The score histogram of the m^3 passes, streamed (`CoreNet.multi_offset_score_histogram`)."""
+    return self.model.multi_offset_score_histogram(input_image, self._v2s(camera_transform, view_to_voxel_transform),
+                                                   grid_offsets, m, gt, num_classes=num_classes, scene_classes=scene_classes,
+                                                   nbins=nbins, out=out)
 
 
 def super_resolution_from_state(state) -> SuperResolutionInference:

@@ -602,6 +602,46 @@ int crn_eval_labels(const float* scores, const int32_t* gt, const int32_t* scene
 int crn_eval_labels_cpu(const float* scores, const int32_t* gt, const int32_t* scene_class, int B, int C, int K, int D, int H,
                         int W, int m, int n, int32_t* labels, int64_t* cm, int32_t* bad, int num_threads);
 
+/* Score-level evaluation epilogue (corenet_amd.score_metrics; csrc/eval_scores.hip, host twin csrc/eval_scores_cpu.cpp,
+ * shared arithmetic csrc/eval_scores_common.h): ONE native pass of an x m inference, as in
+ * crn_eval_labels (same pairing of coarse voxel (b, z, y, x) with fine voxel (b, z*m+iz, y*m+iy, x*m+ix), pass
+ * n = (iz*m + iy)*m + ix), binned by score into a small per-class table from which reliability diagrams, calibration
+ * errors, the Brier score, threshold sweeps and average precision follow exactly.
+ *   scores  f32 [B][C][D][H][W]: a pmf, or with from_logits != 0 logits that go through the shared softmax first
+ *           (es_softmax: first maximum over c, e_c = es_exp(x_c - max), sum in channel order, one IEEE division per
+ *           channel, a quotient below FLT_MIN is 0, a NaN is the canonical quiet NaN; es_exp is built from +, *,
+ *           comparisons and integer bit operations only and both builds compile with -ffp-contract=off, so kernel
+ *           and twin agree to the bit)
+ *   gt      int32 [B][mD][mH][mW]; s = scene_class ? scene_class[b] : 1, g = gt * s (crn_eval_labels' scaling)
+ *   A voxel is BAD -- bad[0] += 1, counted nowhere else -- when s < 1, g is outside [0, K), (C-1)*s >= K, or any p_c
+ *   is NaN or outside [0, 1].  Otherwise every channel c makes one entry: row r = c*s, y = (g == r),
+ *   q = (int)rintf(p_c * 2^24) (exact), bin = min(nbins-1, (q*nbins) >> 24) in 64-bit integers; and one more entry goes
+ *   to row K, the class-agnostic foreground: q = 2^24 - q(p_0), y = (g != 0).  An entry adds 1 and q to
+ *   table[r][bin][y][0..1] and (e16*e16 + 128) >> 8 to sq[r][y], e = y ? 2^24 - q : q, e16 = (e + 128) >> 8 (the squared
+ *   error in units of 2^-24; e is rounded to 16 bits first, so a voxel's term is within e * 2^-16 + 2^-25 of exact, to
+ *   either side).
+ *   table int64 [K+1][nbins][2][2], sq int64 [K+1][2] and bad int64 [1] are ACCUMULATED.  Every sum is an integer sum:
+ *   the same inputs give the same bits on every run, on the GPU and on the twin, whatever crn_set_deterministic says.
+ *   A row holds 2^39 voxels before a sum of q can wrap; the calls do not check that.
+ * 1 <= C <= CRN_EVAL_MAX_CLASSES, 1 <= K <= CRN_EVAL_MAX_BINS, 1 <= nbins <= CRN_SCORE_MAX_NBINS,
+ * (K+1)*nbins <= CRN_SCORE_MAX_ENTRIES, crn_eval_labels' rules for B, D, H, W, m, n and the byte sizes (the GPU call:
+ * B <= 65535 and D*H*W below 2^24 chunks of CRN_SCORE_CHUNK voxels), every pointer but scene_class given: anything else
+ * returns CRN_EINVAL, launches nothing and writes nothing.  The GPU call does not wait for the GPU; the twin takes HOST
+ * memory.  crn_score_softmax(_cpu) writes es_softmax of logits [B][C][S] to out of the same shape (1 <= C <=
+ * CRN_EVAL_MAX_CLASSES, B, S >= 1, sizes within int64).  crn_eval_scores_tiles writes (CRN_SCORE_CHUNK,
+ * CRN_SCORE_MAX_ENTRIES, CRN_SCORE_MAX_NBINS).                                                                        */
+#define CRN_SCORE_MAX_ENTRIES 2048
+#define CRN_SCORE_MAX_NBINS 256
+#define CRN_SCORE_CHUNK 8192
+int crn_eval_scores_tiles(int32_t* out3);
+int crn_eval_scores(const float* scores, int from_logits, const int32_t* gt, const int32_t* scene_class, int B, int C, int K,
+                    int D, int H, int W, int m, int n, int nbins, int64_t* table, int64_t* sq, int64_t* bad, crnStream s);
+int crn_eval_scores_cpu(const float* scores, int from_logits, const int32_t* gt, const int32_t* scene_class, int B, int C,
+                        int K, int D, int H, int W, int m, int n, int nbins, int64_t* table, int64_t* sq, int64_t* bad,
+                        int num_threads);
+int crn_score_softmax(const float* logits, int B, int C, int64_t S, float* out, crnStream s);
+int crn_score_softmax_cpu(const float* logits, int B, int C, int64_t S, float* out, int num_threads);
+
 /* ---------------- optimizer --------------------------------------------------
  * torch.optim.Adam step (state.py:65; train hot loop pipeline.py:230) on a flat
  * fp32 parameter slab.  grad_scale multiplies the gradient first (1/world).   */
