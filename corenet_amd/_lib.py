@@ -221,6 +221,9 @@ _SIGS = {
     "crn_voxel_overlap_tiles": [vp],
     "crn_voxel_overlap": [vp, C.POINTER(i64), i32, vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp],
     "crn_voxel_overlap_cpu": [vp, C.POINTER(i64), i32, vp, C.POINTER(i64), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32],
+    "crn_voxel_topology_tiles": [vp],
+    "crn_voxel_topology": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "crn_voxel_topology_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, vp, vp, i32],
     "crn_voxelize_mesh": [vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "crn_batch_renorm_eval_affine": [vp, vp, vp, i32, f32, vp, vp, vp],
     "crn_transform_meshes": [vp, vp, i32, vp, i32, vp, vp],

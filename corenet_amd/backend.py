@@ -652,6 +652,15 @@ class HipBackend:
     self.lib.crn_voxel_overlap(ptr(a), sa, _DTYPE_CODE[a.dtype], ptr(b), sb, _DTYPE_CODE[b.dtype], N, D, H, W, ptr(num_a),
                                ptr(num_b), table_offsets.data_ptr(), ptr(table), 8 * table.numel(), ptr(bad), _lib.stream())
 
+  # -- configuration histogram (corenet_amd.voxel_topology) --------------------------------------------
+  def voxel_topology(self, grid: t.Tensor, num_labels: int, mask: bool, table: t.Tensor, bad: t.Tensor):
+    """table (int64 [N, num_labels + 1, 256]) / bad (int64 [N]) <- the 2x2x2 configuration counts of grid (uint8 or
+    int32, W stride 1): a mask grid (value != 0, num_labels 0) or a label grid; queued on the current stream."""
+    N, D, H, W = grid.shape
+    st = (C.c_int64 * 4)(*grid.stride())
+    self.lib.crn_voxel_topology(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, int(num_labels), int(bool(mask)), ptr(table),
+                                ptr(bad), _lib.stream())
+
   # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
   def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
                      tri_index: t.Tensor, valid: t.Tensor):

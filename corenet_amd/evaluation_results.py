@@ -21,7 +21,11 @@ plus the class-agnostic `__global__` column) and MetricsTable.to_csv writes what
 
 Score-level results (no counterpart in the reference): ScoreResults accumulates the per-class score histogram of
 corenet_amd.score_metrics (`crn_eval_scores`) the same way and reports calibration, Brier score,
-average precision and the threshold sweep."""
+average precision and the threshold sweep.
+
+Topology results (no counterpart in the reference): topology_metrics_for_batch compares the Betti numbers, volume,
+exposed faces and Crofton area of prediction and ground truth per (scene, class) (corenet_amd.voxel_topology, DESIGN
+section 23) and TopologyResults accumulates them."""
 from __future__ import annotations
 
 import csv
@@ -808,6 +812,113 @@ class InstanceResults:
     present = [c for c in range(tp.numel()) if int(tp[c] + fp[c] + fn[c])]
     return {"overall": entry(tp.sum(), fp.sum(), fn.sum(), sum_iou.sum(), t.ones_like(cls, dtype=t.bool)),
             "per_class": {c: entry(tp[c], fp[c], fn[c], sum_iou[c], cls == c) for c in present}}
+
+
+class TopologyRows(NamedTuple):
+  """One row per (scene, class) in which prediction or ground truth has a voxel, scene-major; class 0 is the
+  class-agnostic mask (any object).  Everything is on the host."""
+  scene_id: List[str]                      # [R]
+  scene_index: t.Tensor                    # i64 [R]
+  class_index: t.Tensor                    # i64 [R]
+  pred: t.Tensor                           # i64 [R, 6]: b0, b1, b2, chi, volume (voxels), exposed_faces
+  gt: t.Tensor                             # i64 [R, 6]
+  pred_area: t.Tensor                      # f64 [R]: Crofton area in view-space units
+  gt_area: t.Tensor                        # f64 [R]
+
+
+def topology_metrics_for_batch(pmf: t.Tensor, ex, task_type, connectivity: int = 26) -> TopologyRows:
+  """Shape type per (scene, class) (corenet_amd.voxel_topology): the Betti numbers b0 (pieces), b1
+  (handles), b2 (cavities), the Euler characteristic, the volume, the exposed faces and the Crofton surface area of the
+  predicted label grid extract_labels(pmf, ex, task_type)[0] and of the ground truth [1].  Rows: the class-agnostic mask
+  (class 0) of every scene, then every label for `semantic`, the scene's mesh label for `fg_bg`; rows empty on both
+  sides are left out.  The area is in view-space units (voxel edge from inverse(ex.v2x_transform[b]); ValueError unless
+  the voxels are cubic).  A ground-truth label outside 0 .. the number of labels raises ValueError.  The default
+  connectivity is 26: thin parts digitised along a diagonal are one piece under it and many under 6.
+
+  Per call: one configuration histogram and three connected-components passes over prediction and ground truth together."""
+  from corenet_amd import voxel_topology as VT
+  task = _task(task_type)
+  if connectivity not in (6, 26):
+    raise ValueError(f"topology_metrics_for_batch: connectivity must be 6 or 26, got {connectivity}")
+  if pmf.dim() != 5 or pmf.shape[1] < 2:
+    raise ValueError(f"topology_metrics_for_batch: pmf must be [B, C >= 2, D, H, W], got {tuple(pmf.shape)}")
+  dev = pmf.device
+  B, C = pmf.shape[:2]
+  if len(ex.scene_id) != B:
+    raise ValueError(f"topology_metrics_for_batch: pmf has {B} elements, the batch {len(ex.scene_id)}")
+  if tuple(ex.grid.shape) != (B,) + tuple(pmf.shape[2:]):
+    raise ValueError(f"topology_metrics_for_batch: ex.grid is {tuple(ex.grid.shape)}, pmf {tuple(pmf.shape)}")
+  sizes = _voxel_sizes(ex.v2x_transform).to(t.float64)
+  if task == "fg_bg":
+    if C != 2:
+      raise ValueError(f"topology_metrics_for_batch: fg_bg expects 2 classes, pmf has {C}")
+    scene_label = t.cat([t.as_tensor(v).reshape(-1) for v in ex.mesh_labels]).to(t.int64).cpu()
+    if scene_label.numel() != B or bool((scene_label < 0).any()):
+      raise ValueError(f"topology_metrics_for_batch: fg_bg expects one non-negative mesh label per scene, got {scene_label.tolist()}")
+    L = int(scene_label.max()) if B else 0
+  else:
+    L = C - 1
+  pred, gt = extract_labels(pmf, ex, task)
+  both = t.cat([pred, t.as_tensor(gt).to(dev, t.int32)])
+  grid, L, mask = VT._prepare(both, L, "topology_metrics_for_batch")
+  betti, hist = VT._betti(grid, L, mask, connectivity, VT._CHUNK_BYTES)
+  if bool(hist.bad[B:].any()):
+    raise ValueError(f"topology_metrics_for_batch: ex.grid has labels outside 0 .. {L} ({hist.bad[B:].tolist()} voxels)")
+  table = hist.table.cpu()
+  ints = t.stack([x.cpu() for x in betti] + [VT.volume(table), VT.exposed_faces(table)], -1)             # [2B, L + 1, 6]
+  area = VT.crofton_area(table, t.cat([sizes, sizes])[:, None])                                          # [2B, L + 1]
+  keep = (ints[:B, :, 4] > 0) | (ints[B:, :, 4] > 0)
+  if task == "fg_bg":
+    own = t.zeros_like(keep)
+    own[:, 0] = True
+    own[t.arange(B), scene_label] = True
+    keep &= own
+  scene, cls = keep.nonzero(as_tuple=True)
+  return TopologyRows([ex.scene_id[int(b)] for b in scene], scene, cls, ints[:B][scene, cls], ints[B:][scene, cls],
+                      area[:B][scene, cls], area[B:][scene, cls])
+
+
+class TopologyResults:
+  """Accumulates topology_metrics_for_batch over an evaluation run, in the manner of InstanceResults: add_batch(pmf, ex)
+  takes what pipeline.evaluate_batch returns; summary() gives, for the class-agnostic rows (`any_object`), per class and
+  `overall` (the rows of all classes together): the mean |b0 - b0'|, |b1 - b1'|, |b2 - b2'| between prediction and ground
+  truth, the share of rows with all three equal (`topology_correct`), the pooled volume and area ratios, predicted over
+  ground truth (NaN where the ground truth has none), and the number of rows."""
+
+  def __init__(self, task_type="fg_bg", connectivity: int = 26):
+    self.task_type = task_type
+    self.connectivity = connectivity
+    self.batches: List[TopologyRows] = []
+
+  def add_batch(self, pmf: t.Tensor, ex) -> TopologyRows:
+    rows = topology_metrics_for_batch(pmf, ex, self.task_type, connectivity=self.connectivity)
+    self.batches.append(rows)
+    return rows
+
+  def rows(self) -> TopologyRows:
+    """Every row added so far; scene_index counts within its batch."""
+    if not self.batches:
+      z, f = t.zeros(0, dtype=t.int64), t.zeros(0, dtype=t.float64)
+      return TopologyRows([], z, z, t.zeros((0, 6), dtype=t.int64), t.zeros((0, 6), dtype=t.int64), f, f)
+    return TopologyRows(sum((b.scene_id for b in self.batches), []), *(t.cat(x) for x in list(zip(*self.batches))[1:]))
+
+  def summary(self) -> Dict:
+    r = self.rows()
+    delta = (r.pred[:, :3] - r.gt[:, :3]).abs()
+
+    def entry(sel):
+      n = int(sel.sum())
+      nan = float("nan")
+      d = delta[sel].to(t.float64)
+      gt_volume, gt_area = float(r.gt[sel, 4].sum()), float(r.gt_area[sel].sum())
+      return {"mean_abs_delta_b0": float(d[:, 0].mean()) if n else nan, "mean_abs_delta_b1": float(d[:, 1].mean()) if n else nan,
+              "mean_abs_delta_b2": float(d[:, 2].mean()) if n else nan,
+              "topology_correct": float((d.sum(1) == 0).to(t.float64).mean()) if n else nan,
+              "volume_ratio": float(r.pred[sel, 4].sum()) / gt_volume if gt_volume else nan,
+              "area_ratio": float(r.pred_area[sel].sum()) / gt_area if gt_area else nan, "num_rows": n}
+    cls = r.class_index
+    return {"connectivity": self.connectivity, "any_object": entry(cls == 0), "overall": entry(cls > 0),
+            "per_class": {int(c): entry(cls == c) for c in sorted(set(cls[cls > 0].tolist()))}}
 
 
 GLOBAL_CLASS_NAME = "__global__"

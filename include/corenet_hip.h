@@ -1078,6 +1078,49 @@ int crn_voxel_overlap_cpu(const void* a, const int64_t* strides_a, int dtype_a, 
                           int dtype_b, int N, int D, int H, int W, const int64_t* num_a, const int64_t* num_b,
                           const int64_t* table_offsets, int64_t* table, int64_t* bad, int num_threads);
 
+/* ---------------- configuration histogram of voxel grids (corenet_amd.voxel_topology) -----------------
+ * How often each of the 256 possible 2x2x2 voxel configurations occurs in N independent grids grid[n][d][h][w].
+ * Contract: DESIGN section 23.  Every voxel outside the grid is background.  Cell (d, h, w), 0 <= d <= D, 0 <= h <= H,
+ * 0 <= w <= W, holds the voxels (d - 1 + i, h - 1 + j, w - 1 + k), i, j, k in {0, 1}; for a mask X its code is the sum
+ * of X(voxel) << (4 * i + 2 * j + k): a grid has (D + 1)(H + 1)(W + 1) cells and every voxel lies in 8 of them.
+ *   grid        dtype 1 = uint8, 2 = int32 (the codes of crn_voxel_components), strides [4] in elements: W stride 1,
+ *               N / D / H strides arbitrary (>= 0).  D*H*W <= 2^31 - 1.
+ *   num_labels  L, 0 <= L <= CRN_VT_MAX_LABELS.
+ *   mask        0: a label grid -- row 0 counts the mask value != 0, row l in 1 .. L the mask value == l, and a voxel
+ *               with value < 0 or value > L is counted once in bad[n] and is background everywhere else.
+ *               non-zero: a mask grid -- L must be 0, row 0 counts value != 0 and bad stays 0.
+ *   table       int64 [N][L + 1][256]; bin 0 of every row is the number of cells minus the row's other bins, so every
+ *               row sums to (D + 1)(H + 1)(W + 1).
+ *   bad         int64 [N].
+ * CRN_EINVAL: an empty extent (N == 0 is valid and does nothing), an unknown dtype, a W stride other than 1, a negative
+ * stride, num_labels outside its range, mask with num_labels != 0.
+ *
+ * GPU: crn_voxel_topology queues two memsets and, per CRN_VT_BATCH grids, one counting launch and one launch that
+ * derives bin 0, on stream s, and does not wait for the GPU; no workgroup waits for another one.  A workgroup owns a brick
+ * of CRN_VT_BRICK_D x bh x CRN_VT_BRICK_W cells (bh = CRN_VT_BRICK_H_I32 for int32, CRN_VT_BRICK_H_U8 for uint8 grids)
+ * and reads the voxels of its cells plus one voxel in front of them on every axis: the halo is the only voxel read by two
+ * workgroups.  A lane owns 16 bytes of a row (4 int32 or 16 uint8 voxels), read with one 16-byte load where the unit lies
+ * inside the row and is 16-byte aligned and element by element otherwise, keeps the rows of the plane before in
+ * registers while it walks along D, merges equal neighbouring (row, code) keys into runs and adds a run that ends to the
+ * u32 rows in LDS; after one barrier the non-zero entries go to the table with 64-bit atomics.  Integer adds only: the
+ * result is the same from run to run and equal to the host twin's; nothing depends on crn_set_deterministic.
+ * crn_voxel_topology_tiles writes (CRN_VT_BRICK_D, CRN_VT_BRICK_H_I32, CRN_VT_BRICK_H_U8, CRN_VT_BRICK_W,
+ * CRN_VT_MAX_LABELS, CRN_VT_BATCH).
+ *
+ * Host twin (HOST memory, same contract, identical results): the (grid, d) cell planes are spread over num_threads
+ * (<= 0: all); every thread counts into a table of its own, summed at the end.                                    */
+#define CRN_VT_BRICK_D 16
+#define CRN_VT_BRICK_H_I32 32
+#define CRN_VT_BRICK_H_U8 128
+#define CRN_VT_BRICK_W 256
+#define CRN_VT_MAX_LABELS 63
+#define CRN_VT_BATCH 1024
+int crn_voxel_topology_tiles(int32_t* out6);
+int crn_voxel_topology(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int num_labels,
+                       int mask, int64_t* table, int64_t* bad, crnStream s);
+int crn_voxel_topology_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int num_labels,
+                           int mask, int64_t* table, int64_t* bad, int num_threads);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
