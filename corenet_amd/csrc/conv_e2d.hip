@@ -134,15 +134,6 @@ __device__ __forceinline__ void wait_patch(float (&pf)[NF], f32x4 (&pv)[NV]) {
 template <typename R>
 __device__ __forceinline__ void keep_live(const R& a, const R& b) { asm volatile("" ::"v"(a), "v"(b)); }
 
-// The fused in-transform of one element (BatchRenorm-apply and the ReLUs around it): max, *, +, max in this order, never
-// contracted.  Padding and channels past C are not x: the callers keep them zero.
-__device__ __forceinline__ float in_transform(float a, int pre_relu, float scale, float shift, int post_relu) {
-  if (pre_relu) a = fmaxf(a, 0.f);
-  a = a * scale + shift;
-  if (post_relu) a = fmaxf(a, 0.f);
-  return a;
-}
-
 // T = window taps (9: 3x3, 1: 1x1); CB = 32-channel blocks per chunk; TW = tile width (3x3: 16 or 8, tile = 64/TW
 // rows; 1x1: the 64 positions of a tile are consecutive in the flattened image and TW only names the instance)
 template <int T, int CB, int TW>

@@ -25,7 +25,6 @@
 #include "conv_kernels.h"
 #include <algorithm>
 #include <cstring>
-#include <cstdio>
 #include <cstdlib>
 
 namespace {
@@ -55,15 +54,20 @@ struct PwGeom {
   int C1;
 };
 
+constexpr int kPwBM = 64;           // positions of one workgroup
 constexpr int kPwBN = 32;           // output columns of one workgroup (64 x 32 tiles)
+constexpr int kPwKC = 64;           // input channels of one chunk (KC 64: half the barriers of KC 32)
+constexpr int kPwPad = 16;          // LDS row pad of both operands: 16 (mod 32) banks
 constexpr int kPwTab = 2048;        // channels of one workgroup (its split's range) whose scale / shift are staged in LDS
+constexpr int kPwLds = kPwKC * (kPwBM + kPwPad + kPwBN + kPwPad) * 4;   // static LDS of the kernel: both operand chunks
 // NS = 16-column blocks per workgroup (kPwBN / 16); PAIR: two K sources onto one output (PwGeom), no input transform
 template <int NS, bool PAIR = false>
 __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
-  constexpr int BM = 64, BN = NS * 16, KC = 64, SA = BM + 16, SB = BN + 16;   // KC 64: half the barriers of KC 32
+  constexpr int BM = kPwBM, BN = NS * 16, KC = kPwKC, SA = BM + kPwPad, SB = BN + kPwPad;
   constexpr int NRA = KC / 16;
   __shared__ __attribute__((aligned(16))) float ldsA[KC * SA];
   __shared__ __attribute__((aligned(16))) float ldsB[KC * SB];
+  static_assert(NS * 16 != kPwBN || sizeof(ldsA) + sizeof(ldsB) == kPwLds, "");
   crn_kernargs_now(g.x, g.y, g.w, g.bias, g.tr.scale, g.tr.shift, g.tr.pre_relu, g.tr.post_relu, g.B, g.C, g.N, g.Npad,
                    g.S, g.xsB, g.ysB, g.ysC, g.ysP, g.bias_sB, g.mode, g.splits, g.cps);
   if (PAIR) crn_kernargs_now(g.x2, g.w2, g.x2sB, g.C1);
@@ -131,13 +135,7 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
     if (has_tr && a_ok && c < cend) {
       const float sc = tsc[c - cbeg], sh = tsh[c - cbeg];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float t = v[i];
-        if (g.tr.pre_relu) t = fmaxf(t, 0.f);
-        t = t * sc + sh;
-        if (g.tr.post_relu) t = fmaxf(t, 0.f);
-        v[i] = t;
-      }
+      for (int i = 0; i < 4; ++i) v[i] = in_transform(v[i], g.tr.pre_relu, sc, sh, g.tr.post_relu);
     }
     return v;
   };
@@ -217,6 +215,7 @@ __global__ __launch_bounds__(256) void pointwise_fwd_kernel(PwGeom g) {
 // MFMA row block and spent 67 / 76 / 47 us (forward / data gradient / weight gradient) on 1.1 M multiply-adds per
 // sample; these three loops are bandwidth bound on the 4.4 MB of weights instead.
 constexpr int kDenseB = 8;      // samples per launch
+constexpr int kDenseColsLds = 3 * kDenseB * 64 * 4;   // static LDS of dense_cols_kernel: the partial sums of waves 1..3
 // many output columns, few input channels: a workgroup owns 64 columns, its four waves split the input channels (one
 // thread per column and 256 columns per workgroup left 192 CUs idle and walked the 67 rows in three batches of loads:
 // 25 us for 4.4 MB of weights); the weight rows of a thread are in flight before the inputs are staged
@@ -226,6 +225,7 @@ __global__ __launch_bounds__(256) void dense_cols_kernel(const float* x, int64_t
                                                          int64_t ysC, int accumulate) {
   extern __shared__ float xs[];                        // [B][C] transformed inputs
   __shared__ float red[3][kDenseB][64];
+  static_assert(sizeof(red) == kDenseColsLds, "");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = blockIdx.x * 64 + lane;
   const int cq = (C + 3) >> 2, cbeg = wave * cq, cend = min(C, cbeg + cq);
@@ -236,11 +236,7 @@ __global__ __launch_bounds__(256) void dense_cols_kernel(const float* x, int64_t
   for (int i = threadIdx.x; i < B * C; i += blockDim.x) {
     const int b = i / C, c = i - b * C;
     float v = x[b * xsB + c * xsC];
-    if (tr.scale) {
-      if (tr.pre_relu) v = fmaxf(v, 0.f);
-      v = v * tr.scale[c] + tr.shift[c];
-      if (tr.post_relu) v = fmaxf(v, 0.f);
-    }
+    if (tr.scale) v = in_transform(v, tr.pre_relu, tr.scale[c], tr.shift[c], tr.post_relu);
     xs[i] = v;
   }
   __syncthreads();
@@ -321,11 +317,7 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(const float* x, int64_
   float acc = 0.f;
   for (int b = 0; b < B; ++b) {
     float v = x[b * xsB + c * xsC];
-    if (tr.scale) {
-      if (tr.pre_relu) v = fmaxf(v, 0.f);
-      v = v * tr.scale[c] + tr.shift[c];
-      if (tr.post_relu) v = fmaxf(v, 0.f);
-    }
+    if (tr.scale) v = in_transform(v, tr.pre_relu, tr.scale[c], tr.shift[c], tr.post_relu);
     acc += v * dy[b * dsB + n * dsC];
   }
   dw[(int64_t)c * Npad + n] += acc;
@@ -381,6 +373,7 @@ constexpr size_t kLdsBudget = 72 * 1024;   // 2 workgroups per CU (160 KiB LDS)
 // ---------------- forward configuration search -------------------------------
 struct FwdCfg {
   int MSUB, NSUB, CC, mw, mh, tsd, tsh, tsw;
+  int PSP;                   // LDS channel stride of the patch
   int64_t blocks;
   size_t lds;
 };
@@ -388,13 +381,32 @@ struct FwdCfg {
 // Sub-tile = 1 x mh x mw output positions (16 MFMA rows); tile = tsd x tsh x tsw sub-tiles.
 // lead >= 0: vector staging with `lead` extra patch columns on the left (units of `unit` = 4 positions for
 // unit-stride views, 2 for stride-2 space-to-depth views); lead < 0: scalar staging
-thread_local int g_stage_unit = 4;
-int patch_width(int TW, int kw, int lead) {
-  return lead < 0 ? TW + kw - 1 : (lead + TW + kw - 1 + g_stage_unit - 1) / g_stage_unit * g_stage_unit;
+int patch_width(int TW, int kw, int lead, int unit) {
+  return lead < 0 ? TW + kw - 1 : (lead + TW + kw - 1 + unit - 1) / unit * unit;
+}
+
+crnInTransform tr_or_none(const crnInTransform* tr) { return tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0}; }
+
+// The one patch geometry of a launch: the patch of a TD x TH x TW tile under a kd x kh x kw window, staged in 16-byte
+// units of `unit` positions with `lead` extra columns (lead >= 0) or as scalars (lead < 0), CC channels at a time,
+// PSP floats apart in LDS.
+void fill_patch(PatchDesc& p, const crnView& x, const crnInTransform* tr, int pd, int ph, int pw, int TD, int TH, int TW,
+                int kd, int kh, int kw, int lead, int unit, int CC, int PSP) {
+  p.x = x; p.tr = tr_or_none(tr);
+  p.lead = lead >= 0 ? lead : 0;
+  p.pd = pd; p.ph = ph; p.pw = pw + p.lead;
+  p.PD = TD + kd - 1; p.PH = TH + kh - 1; p.PW = patch_width(TW, kw, lead, unit);
+  p.plane = p.PH * p.PW; p.PSP = PSP;
+  p.lg2 = ilog2_ceil(p.plane); p.npass = lead >= 0 ? 0 : stage_passes(CC * p.PD, p.plane);
+  p.magic_PW = magic20(p.PW); p.magic_PD = magic20(p.PD);
+  if (lead >= 0) {
+    p.plu = p.plane / unit; p.pw4 = p.PW / unit; p.nunits = CC * p.PD * p.plu;
+    p.magic_PLU = magic20(p.plu); p.magic_PW4 = magic20(p.pw4);
+  }
 }
 
 bool fwd_cfg(int MSUB, int NSUB, int B, int Cin, int Npad, int D, int H, int W, int kd, int kh, int kw, int lead,
-             FwdCfg* out) {
+             int unit, FwdCfg* out) {
   FwdCfg c;
   c.MSUB = MSUB; c.NSUB = NSUB;
   c.mw = W >= 16 ? 16 : (W >= 8 ? 8 : (W >= 4 ? 4 : (W >= 2 ? 2 : 1)));
@@ -408,17 +420,17 @@ bool fwd_cfg(int MSUB, int NSUB, int B, int Cin, int Npad, int D, int H, int W, 
       const int cw = want / (a * bq);
       const int TD = a, TH = bq * c.mh, TW = cw * c.mw;
       const double tiles = (double)crn_cdiv(D, TD) * crn_cdiv(H, TH) * crn_cdiv(W, TW);
-      const double patch = (double)(TD + kd - 1) * (TH + kh - 1) * patch_width(TW, kw, lead);
+      const double patch = (double)(TD + kd - 1) * (TH + kh - 1) * patch_width(TW, kw, lead, unit);
       const double cost = tiles * (patch + 0.25 * TD * TH * TW);   // loads + wasted MFMA rows
       if (cost < best) { best = cost; c.tsd = a; c.tsh = bq; c.tsw = cw; }
     }
   const int TD = c.tsd, TH = c.tsh * c.mh, TW = c.tsw * c.mw;
-  if (lead >= 0 && (TW % g_stage_unit)) return false;
-  const int PDp = TD + kd - 1, plane = (TH + kh - 1) * patch_width(TW, kw, lead);
+  if (lead >= 0 && (TW % unit)) return false;
+  const int PDp = TD + kd - 1, plane = (TH + kh - 1) * patch_width(TW, kw, lead, unit);
   const int PS = PDp * plane;
   const int PSP = pad16mod32(PS), WSP = pad16mod32(T * NSUB * 16);
   auto fits = [&](int cc) {
-    const bool staged = lead >= 0 ? (int64_t)cc * PS / g_stage_unit <= 256 * NVX : stage_passes(cc * PDp, plane) <= PREG;
+    const bool staged = lead >= 0 ? (int64_t)cc * PS / unit <= 256 * NVX : stage_passes(cc * PDp, plane) <= PREG;
     return (size_t)cc * (PSP + WSP) * 4 + 2 * kChTab * 4 <= kLdsBudget && staged &&
            (int64_t)cc * T * NSUB * 16 <= 256 * WREG * 4;
   };
@@ -426,7 +438,7 @@ bool fwd_cfg(int MSUB, int NSUB, int B, int Cin, int Npad, int D, int H, int W, 
   int CC = 4;
   const int cin4 = (Cin + 3) & ~3;
   while (CC * 2 <= cin4 && CC * 2 <= 64 && fits(CC * 2)) CC *= 2;
-  c.CC = CC;
+  c.CC = CC; c.PSP = PSP;
   c.lds = (size_t)CC * (PSP + WSP) * 4 + 2 * kChTab * 4;
   c.blocks = (int64_t)B * crn_cdiv(D, TD) * crn_cdiv(H, TH) * crn_cdiv(W, TW) * crn_cdiv(Npad, NSUB * 16);
   *out = c;
@@ -451,7 +463,8 @@ struct FwdSel {
   int pw_splits, pw_cps;     // pointwise: K splits to ask the scratch for (1: none) and their channels
   int pw_cps_whole;          // ... channels of the only split when the launch does not split
   FwdCfg cfg;                // generic: tile configuration,
-  int xvec, lead;            // staging of x (0 scalar, 1 float4 units, 2 position pairs) and its left lead,
+  int xvec, lead, unit;      // staging of x (0 scalar, 1 float4 units, 2 position pairs), its left lead (-1: scalar) and the
+                             // positions per 16-byte unit (4 or 2),
   bool forced;               // scalar staging because no 16-byte configuration fits,
   int splits, nchunks;       // splits of the nchunks channel chunks the launch asks for
 };
@@ -469,6 +482,26 @@ int pw_auto_splits(int C, int64_t blocks) {
   constexpr int pw_blocks = 256, pw_fill = 512, pw_minc = 128;
   if (blocks >= pw_blocks || C < 2 * pw_minc) return 1;
   return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(C / pw_minc, 16), crn_cdiv(pw_fill, blocks)));
+}
+
+// Launch tail of both pointwise entry points: pw_split, then pw_launch.  p describes the unsplit launch onto y (S positions
+// per sample); with splits > 1, and the scratch to be had, the partial sums over cps channels each go to the dense scratch
+// instead (p.y) and crn_splitk_finish adds them up (or hands them to the BatchRenorm launch the caller armed).
+void pw_split(PwGeom& p, const crnView& y, int64_t S, int splits, int cps, hipStream_t st) {
+  float* scratch = splits > 1 ? crn_splitk_scratch((size_t)splits * y.B * y.C * S, st) : nullptr;
+  if (scratch) {
+    p.splits = splits; p.cps = cps;
+    p.y = scratch; p.ysB = (int64_t)y.C * S; p.ysC = S; p.ysP = 1; p.mode = 0;
+  }
+}
+template <bool PAIR>
+int pw_launch(const PwGeom& p, const crnView& y, int64_t S, int accumulate, bool armed, hipStream_t st) {
+  float* scratch = p.splits > 1 ? p.y : nullptr;
+  dim3 grid((unsigned)crn_cdiv(S, kPwBM), (unsigned)crn_cdiv(y.C, kPwBN), (unsigned)(y.B * p.splits));
+  const size_t tab_bytes = p.tr.scale ? (size_t)2 * p.cps * sizeof(float) : 0;
+  hipLaunchKernelGGL((pointwise_fwd_kernel<kPwBN / 16, PAIR>), grid, dim3(256), tab_bytes, st, p);
+  CRN_CHECK_LAUNCH();
+  return p.splits > 1 ? crn_splitk_finish(y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
 }
 
 int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int Npad, const crnView* y,
@@ -495,7 +528,7 @@ int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int N
     // split the channels over blocks, partial sums to the split-K scratch, one reduction launch
     // (64-column tiles were measured equal to 32-column ones on the whole step, 10.07 vs 10.04 ms: these launches are
     // latency bound, not operand-traffic bound)
-    const int64_t blocks = crn_cdiv(Sx, 64) * crn_cdiv(y->C, kPwBN) * (int64_t)x->B;
+    const int64_t blocks = crn_cdiv(Sx, kPwBM) * crn_cdiv(y->C, kPwBN) * (int64_t)x->B;
     if (splits < 1) {
       int sp = pw_auto_splits(x->C, blocks);
       if (sp > 1) {
@@ -514,7 +547,7 @@ int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int N
   static const int kN[3] = {4, 2, 1};
   // staging of x: float4 units (unit-stride views), position pairs (stride-2 space-to-depth views), scalars
   const int xmode = vec_view(*x) ? 1 : ((x->sW == 2 && (x->W & 1) == 0) ? 2 : 0);   // s2d views and stride-2 views
-  g_stage_unit = xmode == 2 ? 2 : 4;
+  const int unit = xmode == 2 ? 2 : 4;
   const int lead = xmode == 1 ? vec_lead(pw) : (xmode == 2 ? ((pw % 2) + 2) % 2 : -1);
   // Estimated cycles per CU (calibrated on tools/sweep_fwd.sh): work that adds up on the SIMDs
   // (MFMA issue at ~77% + staging instructions, which do not hide under MFMAs) plus one exposed
@@ -529,11 +562,11 @@ int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int N
       if (kN[ni] > 1 && kN[ni] * 16 > Npad) continue;
       if (kM[mi] * kN[ni] > 8) continue;              // instantiated tiles (conv_kernels.h)
       FwdCfg c;
-      if (!fwd_cfg(kM[mi], kN[ni], y->B, x->C, Npad, y->D, y->H, y->W, kd, kh, kw, lead, &c)) continue;
+      if (!fwd_cfg(kM[mi], kN[ni], y->B, x->C, Npad, y->D, y->H, y->W, kd, kh, kw, lead, unit, &c)) continue;
       const int T = kd * kh * kw, nchunks = crn_cdiv(x->C, c.CC), NB = kN[ni] * 16;
       const int TD = c.tsd, TH = c.tsh * c.mh, TW = c.tsw * c.mw;
-      const double patch = (double)c.CC * (TD + kd - 1) * (TH + kh - 1) * patch_width(TW, kw, lead);
-      const double slots = (lead >= 0 ? patch / g_stage_unit / 256 * (g_stage_unit == 4 ? 450.0 : 400.0) : patch / 256 * 350.0) +
+      const double patch = (double)c.CC * (TD + kd - 1) * (TH + kh - 1) * patch_width(TW, kw, lead, unit);
+      const double slots = (lead >= 0 ? patch / unit / 256 * (unit == 4 ? 450.0 : 400.0) : patch / 256 * 350.0) +
                            (double)c.CC * T * NB / 4 / 256 * 300.0;
       const double chunk_work = (double)kM[mi] * kN[ni] * (c.CC / 4) * T * 32.0 * 1.3 + slots;
       for (int sp = 1; sp <= (splits < 1 ? std::min(nchunks, 64) : 1); sp *= 2) {
@@ -550,11 +583,11 @@ int fwd_select(const crnView* x, const crnInTransform* tr, const float* w, int N
     xvec = 0;
     for (int mi = 0; mi < 4 && !have; ++mi) {
       FwdCfg c;
-      if (fwd_cfg(kM[mi], 1, y->B, x->C, Npad, y->D, y->H, y->W, kd, kh, kw, -1, &c)) { best = c; have = true; forced = true; }
+      if (fwd_cfg(kM[mi], 1, y->B, x->C, Npad, y->D, y->H, y->W, kd, kh, kw, -1, unit, &c)) { best = c; have = true; forced = true; }
     }
   }
   if (!have) return CRN_EINVAL;
-  s->cfg = best; s->xvec = xvec; s->lead = lead; s->forced = forced;
+  s->cfg = best; s->xvec = xvec; s->lead = xvec ? lead : -1; s->unit = unit; s->forced = forced;
   s->nchunks = crn_cdiv(x->C, best.CC);
   if (splits < 1) {   // auto split-K (atomic accumulate) only when the output grid cannot fill the chip
     splits = forced ? (best.blocks >= 192 ? 1 : (int)std::min<int64_t>(std::min(s->nchunks, 16), crn_cdiv(256, best.blocks)))
@@ -591,9 +624,8 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   if (rcs != CRN_OK) return rcs;
   const int64_t Sx = (int64_t)x->D * x->H * x->W;
   if (sel.path == CRN_PLAN_DENSE_COLS) {
-    const crnInTransform trv = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
     hipLaunchKernelGGL(dense_cols_kernel, dim3((unsigned)crn_cdiv(y->C, 64)), dim3(256), (size_t)x->B * x->C * 4, st,
-                       x->base, x->sB, x->sC, trv, w, Npad, y->C, x->C, x->B, bias, bias_sB, y->base, y->sB, y->sC,
+                       x->base, x->sB, x->sC, tr_or_none(tr), w, Npad, y->C, x->C, x->B, bias, bias_sB, y->base, y->sB, y->sC,
                        accumulate);
     CRN_CHECK_LAUNCH();
     return CRN_OK;
@@ -611,17 +643,12 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
   if (sel.path == CRN_PLAN_POINTWISE) {
     PwGeom p{};
     p.x = x->base; p.y = y->base; p.w = w; p.bias = bias;
-    p.tr = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
+    p.tr = tr_or_none(tr);
     p.B = x->B; p.C = x->C; p.N = y->C; p.Npad = Npad; p.S = (int)Sx;
     p.xsB = x->sB; p.ysB = y->sB; p.bias_sB = bias_sB; p.mode = accumulate ? 1 : 0;
     p.ysC = y->sC; p.ysP = y->sW;
     p.splits = 1; p.cps = sel.pw_cps_whole;
-    const int64_t ytot = (int64_t)y->B * y->C * Sx;
-    float* scratch = nullptr;
-    if (sel.pw_splits > 1 && (scratch = crn_splitk_scratch((size_t)sel.pw_splits * ytot, st)) != nullptr) {
-      p.splits = sel.pw_splits; p.cps = sel.pw_cps;
-      p.y = scratch; p.ysB = (int64_t)y->C * Sx; p.ysC = Sx; p.ysP = 1; p.mode = 0;
-    }
+    pw_split(p, *y, Sx, sel.pw_splits, sel.pw_cps, st);
 #ifdef CRN_TOOLS
     static const bool want_stamps = getenv("CRN_PW_STAMPS") != nullptr;
 #else
@@ -634,37 +661,25 @@ extern "C" int crn_conv_fwd(const crnView* x, const crnInTransform* tr, const fl
       p.stamps = pw_stamps;
       g_pw_stamps = pw_stamps;
     }
-    dim3 grid((unsigned)crn_cdiv(Sx, 64), (unsigned)crn_cdiv(y->C, kPwBN), (unsigned)(x->B * p.splits));
-    const size_t tab_bytes = p.tr.scale ? (size_t)2 * p.cps * sizeof(float) : 0;
-    hipLaunchKernelGGL(pointwise_fwd_kernel<kPwBN / 16>, grid, dim3(256), tab_bytes, st, p);
-    CRN_CHECK_LAUNCH();
-    return p.splits > 1 ? crn_splitk_finish(*y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
+    return pw_launch<false>(p, *y, Sx, accumulate, armed, st);
   }
   const FwdCfg& best = sel.cfg;
-  const int xvec = sel.xvec, lead = sel.lead;
+  const int xvec = sel.xvec;
   splits = sel.splits;
   ConvGeom g{};
-  g.x = *x; g.y = *y;
-  if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
+  g.y = *y;
   g.w = w; g.bias = bias; g.Npad = Npad; g.bias_sB = bias_sB;
-  g.lead = xvec ? lead : 0;
-  g.kd = kd; g.kh = kh; g.kw = kw; g.pd = pd; g.ph = ph; g.pw = pw + g.lead; g.T = kd * kh * kw;
+  g.kd = kd; g.kh = kh; g.kw = kw; g.T = kd * kh * kw;
   g.mw = best.mw; g.mh = best.mh; g.nsh = best.tsh; g.nsw = best.tsw;
   g.TD = best.tsd; g.TH = best.tsh * best.mh; g.TW = best.tsw * best.mw;
-  g.PD = g.TD + kd - 1; g.PH = g.TH + kh - 1; g.PW = patch_width(g.TW, kw, xvec ? lead : -1);
-  g.PS = g.PD * g.PH * g.PW; g.PSP = pad16mod32(g.PS);
-  g.tilesD = crn_cdiv(y->D, g.TD); g.tilesH = crn_cdiv(y->H, g.TH); g.tilesW = crn_cdiv(y->W, g.TW);
   const int NSUB = best.NSUB, CC = best.CC;
+  fill_patch(g, *x, tr, pd, ph, pw, g.TD, g.TH, g.TW, kd, kh, kw, sel.lead, sel.unit, CC, best.PSP);
+  g.tilesD = crn_cdiv(y->D, g.TD); g.tilesH = crn_cdiv(y->H, g.TH); g.tilesW = crn_cdiv(y->W, g.TW);
   g.CC = CC; g.WSP = pad16mod32(g.T * NSUB * 16);
   g.nchunks = sel.nchunks;
   g.chunks_per_split = crn_cdiv(g.nchunks, splits);
   g.mode = splits > 1 ? 2 : (accumulate ? 1 : 0);
-  g.lg2 = ilog2_ceil(g.PH * g.PW); g.npass = xvec ? 0 : stage_passes(CC * g.PD, g.PH * g.PW);
-  g.magic_PW = magic20(g.PW); g.magic_PD = magic20(g.PD); g.magic_T = magic20(g.T);
-  if (xvec) {
-    g.plu = g.PH * g.PW / g_stage_unit; g.pw4 = g.PW / g_stage_unit; g.nunits = CC * g.PD * g.plu;
-    g.magic_PLU = magic20(g.plu); g.magic_PW4 = magic20(g.pw4);
-  }
+  g.magic_T = magic20(g.T);
   // split-K: partial sums into a dense scratch tensor + one reduction launch (mode 3); atomics (mode 2)
   // only when the scratch cannot be had
   const crnView yreal = *y;
@@ -719,41 +734,33 @@ extern "C" int crn_conv1x1_fwd_pair(const crnView* x1, const float* w1, const cr
   if (rcf != CRN_OK) return rcf;
   // the split rule of the single launch (fwd_select) on the concatenated K; splits > 1: as asked.  cps a multiple of 64
   int sp = splits;
-  if (sp == 0) sp = pw_auto_splits(C, crn_cdiv(S, 64) * crn_cdiv(y->C, kPwBN) * (int64_t)y->B);
+  if (sp == 0) sp = pw_auto_splits(C, crn_cdiv(S, kPwBM) * crn_cdiv(y->C, kPwBN) * (int64_t)y->B);
   sp = std::max(1, std::min(sp, C / 64));
   int cps = (crn_cdiv(C, sp) + 63) & ~63;
   sp = crn_cdiv(C, cps);
   PwGeom p{};
   p.x = x1->base; p.w = w1; p.x2 = x2->base; p.w2 = w2; p.y = y->base;
-  p.tr = crnInTransform{nullptr, nullptr, 0, 0};
   p.B = y->B; p.C = C; p.C1 = C1; p.N = y->C; p.Npad = Npad; p.S = (int)S;
   p.xsB = x1->sB; p.x2sB = x2->sB; p.ysB = y->sB; p.ysC = y->sC; p.ysP = 1; p.mode = accumulate ? 1 : 0;
   p.splits = 1; p.cps = (C + 63) & ~63;
-  const int64_t ytot = (int64_t)y->B * y->C * S;
-  float* scratch = nullptr;
-  if (sp > 1 && (scratch = crn_splitk_scratch((size_t)sp * ytot, st)) != nullptr) {
-    p.splits = sp; p.cps = cps;
-    p.y = scratch; p.ysB = (int64_t)y->C * S; p.ysC = S; p.mode = 0;
-  }
-  dim3 grid((unsigned)crn_cdiv(S, 64), (unsigned)crn_cdiv(y->C, kPwBN), (unsigned)(y->B * p.splits));
-  hipLaunchKernelGGL((pointwise_fwd_kernel<kPwBN / 16, true>), grid, dim3(256), 0, st, p);
-  CRN_CHECK_LAUNCH();
-  return p.splits > 1 ? crn_splitk_finish(*y, scratch, p.splits, accumulate, armed, st) : CRN_OK;
+  pw_split(p, *y, S, sp, cps, st);
+  return pw_launch<true>(p, *y, S, accumulate, armed, st);
 }
 
 namespace {
-struct WgCand { int TD, TH, TW, RSUB, NSUB, CC, PW, PSP, POSP; double cost; size_t lds; };
+struct WgCand { int TD, TH, TW, RSUB, NSUB, CC, PSP, POSP; double cost; size_t lds; };
 
 // One weight-grad configuration: position tile TDxTHxTW, RSUB x NSUB MFMA tiles per wave.
-// xlead >= 0: x staged in 16-byte units; dvec: dy staging mode (0 scalar, 1 float4 units, 2 position pairs).
-bool wg_cand(int TD, int TH, int TW, int RSUB, int NSUB, int Cin, int Npad, int kd, int kh, int kw, int xlead,
+// xlead >= 0: x staged in 16-byte units of `unit` positions; dvec: dy staging mode (0 scalar, 1 float4 units, 2 position pairs).
+constexpr int kWgUnit = 4;                       // x patches of the weight gradient: float4 units only
+bool wg_cand(int TD, int TH, int TW, int RSUB, int NSUB, int Cin, int Npad, int kd, int kh, int kw, int xlead, int unit,
              int dvec, size_t lds_budget, WgCand* out) {
   const int T = kd * kh * kw, NB = NSUB * 16, npos = TD * TH * TW;
   if (npos > 512 || RSUB * NSUB > 8 || (NSUB > 1 && NB > Npad)) return false;
   if ((xlead >= 0 || dvec) && (TW & 3)) return false;
   if (dvec == 1 ? (int64_t)NB * npos / 4 > 256 * NV
                 : dvec == 2 ? (int64_t)NB * npos / 2 > 256 * NVX : stage_passes(NB, npos) > DREG) return false;
-  const int PDp = TD + kd - 1, PH = TH + kh - 1, PW = patch_width(TW, kw, xlead), plane = PH * PW;
+  const int PDp = TD + kd - 1, PH = TH + kh - 1, PW = patch_width(TW, kw, xlead, unit), plane = PH * PW;
   int CC = std::min(std::min(std::max(1, (64 * RSUB) / T), Cin), 64);
   auto staged = [&](int cc) {
     return xlead >= 0 ? (int64_t)cc * PDp * plane / 4 <= 256 * NVX : stage_passes(cc * PDp, plane) <= PREG;
@@ -773,7 +780,7 @@ bool wg_cand(int TD, int TH, int TW, int RSUB, int NSUB, int Cin, int Npad, int 
   const double dslots = dvec == 1 ? (double)NB * npos / 4 / 256 * 300.0
                                   : dvec == 2 ? (double)NB * npos / 2 / 256 * 300.0 : (double)NB * npos / 256 * 300.0;
   const double useful = (double)rows * std::min(NB, Npad) * npos;
-  *out = WgCand{TD, TH, TW, RSUB, NSUB, CC, PW, PSP, POSP, (mfma + xslots + dslots + 800.0) / useful, lds};
+  *out = WgCand{TD, TH, TW, RSUB, NSUB, CC, PSP, POSP, (mfma + xslots + dslots + 800.0) / useful, lds};
   return true;
 }
 }  // namespace
@@ -802,7 +809,6 @@ struct WgSel {
 int wg_select(const crnView* x, const crnView* dy, int Npad, int kd, int kh, int kw, int pw, const crnTapBoxes* boxes,
               WgSel* s) {
   const int T = kd * kh * kw;
-  g_stage_unit = 4;                              // x patches of the weight gradient: float4 units only
   const int Dy = dy->D, Hy = dy->H, Wy = dy->W;
   const int TWc = Wy >= 16 ? 16 : ((Wy + 3) & ~3);
   int xlead = vec_view(*x) ? vec_lead(pw) : -1;
@@ -812,7 +818,7 @@ int wg_select(const crnView* x, const crnView* dy, int Npad, int kd, int kh, int
   WgCand best{}; bool have = false;
   auto consider = [&](int TD, int TH, int RSUB, int NSUB, size_t budget) {
     WgCand c;
-    if (!wg_cand(std::min(TD, Dy), std::min(TH, Hy), TWc, RSUB, NSUB, x->C, Npad, kd, kh, kw, xlead, dvec, budget, &c))
+    if (!wg_cand(std::min(TD, Dy), std::min(TH, Hy), TWc, RSUB, NSUB, x->C, Npad, kd, kh, kw, xlead, kWgUnit, dvec, budget, &c))
       return false;
     if (RSUB > 1 && c.CC * T <= 32 * RSUB) return false;   // a smaller RSUB covers it
     if (!have || c.cost < best.cost) { best = c; have = true; }
@@ -833,7 +839,7 @@ int wg_select(const crnView* x, const crnView* dy, int Npad, int kd, int kh, int
   if (xlead < 0 || !dvec) {
     // the candidate was costed with dvec; re-derive it with the variant that will run
     WgCand c;
-    if (!wg_cand(best.TD, best.TH, best.TW, best.RSUB, best.NSUB, x->C, Npad, kd, kh, kw, xlead, dvec, 150 * 1024, &c)) {
+    if (!wg_cand(best.TD, best.TH, best.TW, best.RSUB, best.NSUB, x->C, Npad, kd, kh, kw, xlead, kWgUnit, dvec, 150 * 1024, &c)) {
       have = false; search();
       if (!have) return CRN_EINVAL;
     } else {
@@ -866,16 +872,14 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
   const int xlead = sel.xlead, dvec = sel.dvec;
   const int Dy = dy->D, Hy = dy->H, Wy = dy->W;
   WgradGeom g{};
-  g.x = *x; g.dy = *dy;
-  if (tr) g.tr = *tr; else g.tr = crnInTransform{nullptr, nullptr, 0, 0};
+  g.dy = *dy;
   g.dw = dw; g.Npad = Npad;
-  g.lead = xlead >= 0 ? xlead : 0;
-  g.kd = kd; g.kh = kh; g.kw = kw; g.pd = pd; g.ph = ph; g.pw = pw + g.lead; g.T = T;
+  g.kd = kd; g.kh = kh; g.kw = kw; g.T = T;
   g.TD = best.TD; g.TH = best.TH; g.TW = best.TW;
-  g.PD = g.TD + kd - 1; g.PH = g.TH + kh - 1; g.PW = best.PW;
-  g.PSP = best.PSP; g.POSP = best.POSP;
+  g.POSP = best.POSP;
   const int NSUB = best.NSUB, RSUB = best.RSUB, NB = NSUB * 16, CC = best.CC;
   const int npos = g.TD * g.TH * g.TW;
+  fill_patch(g, *x, tr, pd, ph, pw, g.TD, g.TH, g.TW, kd, kh, kw, xlead, kWgUnit, CC, best.PSP);
   g.CC = CC;
   g.tilesD = crn_cdiv(Dy, g.TD); g.tilesH = crn_cdiv(Hy, g.TH); g.tilesW = crn_cdiv(Wy, g.TW);
   g.ntiles = sel.ntiles;
@@ -900,17 +904,9 @@ int wgrad_launch(const crnView* x, const crnInTransform* tr, const crnView* dy, 
       g.zoff[gi + 1] = g.zoff[gi] + g.nbpg * g.sg[gi];
     }
   }
-  g.lg2 = ilog2_ceil(g.PH * g.PW); g.npass = xlead >= 0 ? 0 : stage_passes(CC * g.PD, g.PH * g.PW);
   g.dlg2 = ilog2_ceil(npos); g.dnpass = dvec ? 0 : stage_passes(NB, npos);
-  g.magic_PW = magic20(g.PW); g.magic_PD = magic20(g.PD); g.magic_T = magic20(T);
   g.magic_TW = magic20(g.TW); g.magic_TH = magic20(g.TH);
-  if (xlead >= 0) {
-    g.plu = g.PH * g.PW / 4; g.pw4 = g.PW / 4; g.nunits = CC * g.PD * g.plu;
-    g.magic_PLU = magic20(g.plu); g.magic_PW4 = magic20(g.pw4);
-  }
   if (dvec) { g.np4 = npos / (dvec == 2 ? 2 : 4); g.dnunits = NB * g.np4; g.magic_NP4 = magic20(g.np4); }
-  // the whole packed window in one launch: no tap sub-box, every column, XCD-aware block order
-  g.Tfull = T; g.khf = kh; g.kwf = kw; g.ncols = Npad; g.xcd = 1;
   dim3 grid((unsigned)cblocks, (unsigned)(g.balanced ? 1 : nblocks), (unsigned)(g.balanced ? g.zoff[g.n_groups] : splits));
   const size_t lds_bytes = best.lds;
 #define CRN_WG_CASE(R, N) \
@@ -931,9 +927,8 @@ extern "C" int crn_conv_wgrad(const crnView* x, const crnInTransform* tr, const 
   const int T = kd * kh * kw;
   if (zero_first) CRN_HIP(hipMemsetAsync(dw, 0, (size_t)x->C * T * Npad * 4, st));
   if (wgrad_dense(x, dy, T)) {
-    const crnInTransform trv = tr ? *tr : crnInTransform{nullptr, nullptr, 0, 0};
     hipLaunchKernelGGL(dense_wgrad_kernel, dim3((unsigned)crn_cdiv(dy->C, 256), (unsigned)x->C), dim3(256), 0, st, x->base,
-                       x->sB, x->sC, trv, dy->base, dy->sB, dy->sC, dw, Npad, dy->C, x->C, x->B);
+                       x->sB, x->sC, tr_or_none(tr), dy->base, dy->sB, dy->sC, dw, Npad, dy->C, x->C, x->B);
     CRN_CHECK_LAUNCH();
     return CRN_OK;
   }
@@ -958,15 +953,15 @@ extern "C" int crn_conv_fwd_plan(const crnView* x, const crnInTransform* tr, con
   crnConvPlan p{};
   p.path = sel.path; p.splits = 1; p.chunks = 1; p.lds_budget = (int)kLdsBudget;
   if (sel.path == CRN_PLAN_DENSE_COLS) {
-    p.lds_bytes = x->B * x->C * 4 + 3 * kDenseB * 64 * 4;
+    p.lds_bytes = x->B * x->C * 4 + kDenseColsLds;
   } else if (sel.path == CRN_PLAN_DENSE_ROWS) {
     p.splits = sel.zs; p.chunks = crn_cdiv(x->C, 256); p.lds_bytes = 4 * 8 * 4;
   } else if (sel.path == CRN_PLAN_POINTWISE) {
     // 64 positions x 32 columns per workgroup, K chunks of 64 (pointwise_fwd_kernel)
-    p.msub = 4; p.nsub = kPwBN / 16; p.xstage = 1; p.cc = 64; p.td = 1; p.th = 1; p.tw = 64; p.mw = 16;
+    p.msub = 4; p.nsub = kPwBN / 16; p.xstage = 1; p.cc = kPwKC; p.td = 1; p.th = 1; p.tw = kPwBM; p.mw = 16;
     p.splits = sel.pw_splits; p.chunks = crn_cdiv(x->C, 32);
     p.vec_store = (sel.pw_splits > 1 || y->sW == 1) ? 1 : 0;
-    p.lds_bytes = 64 * (64 + 16) * 4 + 64 * (kPwBN + 16) * 4 + ((tr && tr->scale) ? 2 * sel.pw_cps * 4 : 0);
+    p.lds_bytes = kPwLds + ((tr && tr->scale) ? 2 * sel.pw_cps * 4 : 0);
   } else {
     const FwdCfg& c = sel.cfg;
     p.msub = c.MSUB; p.nsub = c.NSUB; p.xstage = sel.xvec; p.forced = sel.forced ? 1 : 0; p.cc = c.CC;

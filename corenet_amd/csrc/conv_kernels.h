@@ -10,38 +10,6 @@ namespace crnk {
 constexpr int PREG = 32;    // staged patch floats per thread   (CC*PS   <= 256*PREG)
 constexpr int WREG = 8;     // staged weight float4 per thread  (CC*T*NB <= 256*WREG*4)
 constexpr int DREG = 32;    // staged dy floats per thread      (NB*npos <= 256*DREG)
-constexpr int kMaxStage = 256 * PREG;
-
-struct ConvGeom {
-  crnView x, y;
-  crnInTransform tr;
-  const float* w;
-  const float* bias;
-  int Npad, bias_sB;
-  int kd, kh, kw, pd, ph, pw, T;
-  int TD, TH, TW;          // tile (positions)
-  int mw, mh;              // M-subtile shape, mw*mh == 16
-  int nsh, nsw;            // sub-tiles per tile along H, W
-  int PD, PH, PW, PS, PSP; // patch dims, size, padded channel stride
-  int WSP;                 // LDS weight channel stride
-  int CC;                  // channels per chunk (multiple of 4)
-  int tilesD, tilesH, tilesW;
-  int nchunks, chunks_per_split;
-  int mode;                // 0 store, 1 accumulate (rmw), 2 atomic add, 3 split-K partials to scratch (+ reduce
-                           // launch)
-  int lg2, npass;          // patch staging: plane padded to 2^lg2 slots, passes of 256 slots
-  unsigned magic_PW, magic_PD, magic_T;
-  int vec_store;           // epilogue may use 16-B stores (unit W stride, 4-aligned rows)
-  int n_groups, c_groups;  // crnTapBoxes (0 = all taps)
-  signed char n_box[8][6], c_box[8][6];
-  int lead;                // extra patch columns on the left (16-byte staging), already included in pw/PW
-  int nunits, plu, pw4;    // 16-byte staging geometry (PatchDesc)
-  unsigned magic_PLU, magic_PW4;
-};
-
-__device__ __forceinline__ int64_t view_chan(const crnView& v, int c) {
-  return v.chan_off ? (int64_t)v.chan_off[c] : (int64_t)c * v.sC;
-}
 
 // ---- patch staging: global -> registers (issue) and registers -> LDS (commit) ----
 // The patch of one chunk is CC*PD planes of PH*PW elements.  Staging slots are laid out as
@@ -50,15 +18,59 @@ __device__ __forceinline__ int64_t view_chan(const crnView& v, int c) {
 //   lg2 <  8: r is a per-thread constant.
 // Everything that depends only on r (ph, pw, h/w bounds, h/w address part) is loop invariant
 // and hoisted by the compiler; per slot ~6 VALU remain for issue and ~8 for commit.
+// The one patch geometry: base of ConvGeom and WgradGeom, filled on the host by fill_patch (conv_igemm.hip).
+// The kernels hand the staging helpers a local copy of it, which becomes one scalar load per field.  The scalar staging
+// reads these fields about a thousand times, and past 300 uses the compiler no longer reads a kernel argument struct in
+// place: it keeps a copy in private memory, whose loads are not wave-uniform (the "+s" constraints then fail to compile).
+// Seen with hipcc of ROCm 7.2 (clang 22): with `g` passed instead of the copy every XV == 0 instance, conv_fwd_kernel<1,1,0>
+// for one, stops with "illegal VGPR to SGPR copy" at the asm of patch_slot; its IR keeps `alloca ConvGeom` with 943 loads
+// of it (the kernels with fewer uses lose the alloca).  300 is LLVM's instcombine-max-copied-from-constant-users.
 struct PatchDesc {
   crnView x;
   crnInTransform tr;
-  int pd, ph, pw, PD, PH, PW, plane, lg2, PSP;
+  int pd, ph, pw;                    // padding; pw includes lead
+  int lead;                          // extra patch columns on the left (16-byte staging), already included in pw/PW
+  int PD, PH, PW, plane, PSP;        // patch dims, PH*PW, padded LDS channel stride
+  int lg2, npass;                    // scalar staging: plane padded to 2^lg2 slots, passes of 256 slots
   unsigned magic_PW, magic_PD;       // ceil(2^20 / d)
   // 16-byte staging (XV kernels): the patch is nunits float4 units, plu per plane, pw4 per row
   int nunits, plu, pw4;
   unsigned magic_PLU, magic_PW4;
 };
+
+struct ConvGeom : PatchDesc {
+  crnView y;
+  const float* w;
+  const float* bias;
+  int Npad, bias_sB;
+  int kd, kh, kw, T;
+  int TD, TH, TW;          // tile (positions)
+  int mw, mh;              // M-subtile shape, mw*mh == 16
+  int nsh, nsw;            // sub-tiles per tile along H, W
+  int WSP;                 // LDS weight channel stride
+  int CC;                  // channels per chunk (multiple of 4)
+  int tilesD, tilesH, tilesW;
+  int nchunks, chunks_per_split;
+  int mode;                // 0 store, 1 accumulate (rmw), 2 atomic add, 3 split-K partials to scratch (+ reduce
+                           // launch)
+  unsigned magic_T;
+  int vec_store;           // epilogue may use 16-B stores (unit W stride, 4-aligned rows)
+  int n_groups, c_groups;  // crnTapBoxes (0 = all taps)
+  signed char n_box[8][6], c_box[8][6];
+};
+
+__device__ __forceinline__ int64_t view_chan(const crnView& v, int c) {
+  return v.chan_off ? (int64_t)v.chan_off[c] : (int64_t)c * v.sC;
+}
+
+// tile index (batch outermost, W innermost) -> sample and origin of the tile
+template <typename G>
+__device__ __forceinline__ void tile_origin(const G& g, int tile, int& b, int& d0, int& h0, int& w0) {
+  const int twi = tile % g.tilesW; tile /= g.tilesW;
+  const int thi = tile % g.tilesH; tile /= g.tilesH;
+  const int tdi = tile % g.tilesD; tile /= g.tilesD;
+  b = tile; d0 = tdi * g.TD; h0 = thi * g.TH; w0 = twi * g.TW;
+}
 
 // 16-byte staging.  Eligible views (unit W stride, everything 4-aligned) are staged as float4
 // units: 4x fewer staging instructions, and on gfx950 every VALU/SALU instruction issued next to an
@@ -154,8 +166,21 @@ __device__ __forceinline__ void patch_hw(const PatchDesc& g, int h0, int w0, HWV
   }
 }
 
-__device__ __forceinline__ unsigned chan_off_s(const crnView& v, int c) {   // c wave-uniform -> scalar load
-  return v.chan_off ? (unsigned)v.chan_off[c] : (unsigned)c * (unsigned)v.sC;
+// Slot J -> plane q of the chunk, (local channel cl, patch row pd) and the staged depth gd; the slot's in-plane
+// variant is hw[U ? J % U : 0].  One decode for both U forms and for issue and commit.  U >= 1: q is wave-uniform and
+// recomputed per chunk on the scalar unit, so the guards on it are branches; U == 0: per thread.
+struct Slot { int q, cl, pd, gd; };
+template <int J, int U>
+__device__ __forceinline__ Slot patch_slot(const PatchDesc& g, int d0) {
+  int q = U ? J / U : J * (256 >> g.lg2);
+  asm volatile("" : "+s"(q));
+  if constexpr (U == 0) q += (int)threadIdx.x >> g.lg2;
+  Slot s;
+  s.q = q;
+  s.cl = mdiv(q, g.magic_PD);
+  s.pd = q - s.cl * g.PD;
+  s.gd = d0 + s.pd - g.pd;
+  return s;
 }
 
 template <int J, int U>
@@ -163,28 +188,14 @@ __device__ __forceinline__ void patch_issue_one(const PatchDesc& g, const unsign
                                                 const HWVar (&hw)[U ? U : 1], const crn_rsrc& rs, int nplanes,
                                                 int c0, int d0, float& v) {
   unsigned goff = 0x80000000u;               // outside the descriptor range -> the load returns 0
-  if constexpr (U >= 1) {
-    int q = J / U;
-    asm volatile("" : "+s"(q));              // recompute per chunk on the scalar unit
-    const HWVar& h = hw[J % U];
-    const int cl = mdiv(q, g.magic_PD), pd = q - cl * g.PD;
-    const int c = c0 + cl, gd = d0 + pd - g.pd;
-    if (q < nplanes && c < g.x.C && (unsigned)gd < (unsigned)g.x.D) {       // wave-uniform
-      // channel offset from the LDS table, NOT from global memory: a compiler-visible global load
-      // here makes hipcc emit s_waitcnt vmcnt(0), which also drains every asm staging load issued so
-      // far (measured: one full memory latency per slot, 27 us per wgrad tile)
-      const unsigned sbase = choff[cl] + (unsigned)gd * (unsigned)g.x.sD;
-      goff = h.in ? (sbase + h.off) * 4u : 0x80000000u;
-    }
-  } else {
-    int jq = J * (256 >> g.lg2);
-    asm volatile("" : "+s"(jq));
-    const HWVar& h = hw[0];
-    const int q = jq + ((int)threadIdx.x >> g.lg2);
-    const int cl = mdiv(q, g.magic_PD), pd = q - cl * g.PD;
-    const int gd = d0 + pd - g.pd;
-    const bool in = h.in && q < nplanes && (c0 + cl < g.x.C) && (unsigned)gd < (unsigned)g.x.D;
-    if (in) goff = (choff[cl] + (unsigned)gd * (unsigned)g.x.sD + h.off) * 4u;
+  const Slot s = patch_slot<J, U>(g, d0);
+  const HWVar& h = hw[U ? J % U : 0];
+  if (s.q < nplanes && c0 + s.cl < g.x.C && (unsigned)s.gd < (unsigned)g.x.D) {
+    // channel offset from the LDS table, NOT from global memory: a compiler-visible global load
+    // here makes hipcc emit s_waitcnt vmcnt(0), which also drains every asm staging load issued so
+    // far (measured: one full memory latency per slot, 27 us per wgrad tile)
+    const unsigned sbase = choff[s.cl] + (unsigned)s.gd * (unsigned)g.x.sD;
+    goff = h.in ? (sbase + h.off) * 4u : 0x80000000u;
   }
   crn_bload(v, rs, goff);
 }
@@ -193,89 +204,78 @@ template <int J, int U>
 __device__ __forceinline__ void patch_commit_one(const PatchDesc& g, const unsigned* choff,
                                                  const HWVar (&hw)[U ? U : 1], float* ldsA, int nplanes, int c0,
                                                  int d0, float v) {
-  if constexpr (U >= 1) {
-    int q = J / U;
-    asm volatile("" : "+s"(q));
-    const HWVar& h = hw[J % U];
-    if (q < nplanes) {                                   // wave-uniform
-      const int cl = mdiv(q, g.magic_PD), pd = q - cl * g.PD;
-      const int c = c0 + cl, gd = d0 + pd - g.pd;
-      if (g.tr.scale && c < g.x.C && (unsigned)gd < (unsigned)g.x.D) {
-        const float* tab = reinterpret_cast<const float*>(choff);
-        const float sc = tab[64 + cl], sh = tab[128 + cl];            // LDS broadcast reads
-        float t = v;
-        if (g.tr.pre_relu) t = fmaxf(t, 0.f);
-        t = t * sc + sh;
-        if (g.tr.post_relu) t = fmaxf(t, 0.f);
-        v = h.in ? t : v;                                // zero padding stays zero
-      }
-      if (h.r >= 0) ldsA[cl * g.PSP + pd * g.plane + h.r] = v;
+  const Slot s = patch_slot<J, U>(g, d0);
+  const HWVar& h = hw[U ? J % U : 0];
+  if (s.q < nplanes) {
+    if (g.tr.scale && c0 + s.cl < g.x.C && (unsigned)s.gd < (unsigned)g.x.D) {
+      const float* tab = reinterpret_cast<const float*>(choff);
+      const float t = in_transform(v, g.tr.pre_relu, tab[64 + s.cl], tab[128 + s.cl], g.tr.post_relu);   // LDS broadcast reads
+      v = h.in ? t : v;                                  // zero padding stays zero
     }
-  } else {
-    int jq = J * (256 >> g.lg2);
-    asm volatile("" : "+s"(jq));
-    const HWVar& h = hw[0];
-    const int q = jq + ((int)threadIdx.x >> g.lg2);
-    if (q < nplanes && h.r >= 0) {
-      const int cl = mdiv(q, g.magic_PD), pd = q - cl * g.PD;
-      const int gd = d0 + pd - g.pd;
-      const bool in = h.in && (c0 + cl < g.x.C) && (unsigned)gd < (unsigned)g.x.D;
-      if (in && g.tr.scale) {
-        const float* tab = reinterpret_cast<const float*>(choff);
-        if (g.tr.pre_relu) v = fmaxf(v, 0.f);
-        v = v * tab[64 + cl] + tab[128 + cl];
-        if (g.tr.post_relu) v = fmaxf(v, 0.f);
-      }
-      ldsA[cl * g.PSP + pd * g.plane + h.r] = v;
-    }
+    if (h.r >= 0) ldsA[s.cl * g.PSP + s.pd * g.plane + h.r] = v;
   }
+}
+
+template <int V>
+struct IntC { static constexpr int value = V; };
+// f(IntC<J>, val[J]) for the N slots from B0 on; ... for every group of 8 slots that npass reaches
+template <int B0, int N, typename T, int M, typename F>
+__device__ __forceinline__ void for_slots(T (&val)[M], F&& f) {
+  if constexpr (N > 0) {
+    f(IntC<B0>{}, val[B0]);
+    for_slots<B0 + 1, N - 1>(val, f);
+  }
+}
+template <int B0 = 0, typename T, int M, typename F>
+__device__ __forceinline__ void for_slot_groups(int npass, T (&val)[M], F&& f) {
+  if constexpr (B0 < M) {
+    if (npass > B0) for_slots<B0, 8>(val, f);
+    for_slot_groups<B0 + 8>(npass, val, f);
+  }
+}
+// Runtime (wave-uniform) dispatch on the plane padding: f(IntC<U>, hw[U ? U : 1]).  HWVar storage is sized for the largest U.
+struct PatchHW { HWVar v[2]; };
+template <typename F>
+__device__ __forceinline__ void patch_dispatch(int lg2, PatchHW& p, F&& f) {
+  switch (lg2) {   // wave-uniform
+    case 8: f(IntC<1>{}, reinterpret_cast<HWVar(&)[1]>(p.v)); break;
+    case 9: f(IntC<2>{}, reinterpret_cast<HWVar(&)[2]>(p.v)); break;
+    default: f(IntC<0>{}, reinterpret_cast<HWVar(&)[1]>(p.v)); break;
+  }
+}
+__device__ __forceinline__ void patch_prepare(const PatchDesc& g, int h0, int w0, PatchHW& p) {
+  patch_dispatch(g.lg2, p, [&](auto u, auto& hw) __attribute__((always_inline)) { patch_hw<decltype(u)::value>(g, h0, w0, hw); });
 }
 
 template <int U, int J = 0>
 __device__ __forceinline__ void patch_issue_u(const PatchDesc& g, const unsigned* choff,
                                               const HWVar (&hw)[U ? U : 1], const crn_rsrc& rs, int nplanes,
-                                              int npass, int c0, int d0, float (&val)[PREG]) {
+                                              int c0, int d0, float (&val)[PREG]) {
   if constexpr (J < PREG) {
-    patch_issue_one<J, U>(g, choff, hw, rs, J < npass ? nplanes : 0, c0, d0, val[J]);
-    patch_issue_u<U, J + 1>(g, choff, hw, rs, nplanes, npass, c0, d0, val);
+    patch_issue_one<J, U>(g, choff, hw, rs, J < g.npass ? nplanes : 0, c0, d0, val[J]);
+    patch_issue_u<U, J + 1>(g, choff, hw, rs, nplanes, c0, d0, val);
   }
 }
 template <int U, int J = 0>
 __device__ __forceinline__ void patch_commit_u(const PatchDesc& g, const unsigned* choff,
-                                               const HWVar (&hw)[U ? U : 1], float* ldsA, int nplanes, int npass,
-                                               int c0, int d0, const float (&val)[PREG]) {
+                                               const HWVar (&hw)[U ? U : 1], float* ldsA, int nplanes, int c0,
+                                               int d0, const float (&val)[PREG]) {
   if constexpr (J < PREG) {
-    if (J < npass) patch_commit_one<J, U>(g, choff, hw, ldsA, nplanes, c0, d0, val[J]);
-    patch_commit_u<U, J + 1>(g, choff, hw, ldsA, nplanes, npass, c0, d0, val);
+    if (J < g.npass) patch_commit_one<J, U>(g, choff, hw, ldsA, nplanes, c0, d0, val[J]);
+    patch_commit_u<U, J + 1>(g, choff, hw, ldsA, nplanes, c0, d0, val);
   }
 }
-
-// Runtime (wave-uniform) dispatch on the plane padding; HWVar storage is sized for the largest U.
-struct PatchHW { HWVar v[2]; };
-__device__ __forceinline__ void patch_prepare(const PatchDesc& g, int h0, int w0, PatchHW& p) {
-  switch (g.lg2) {
-    case 8: patch_hw<1>(g, h0, w0, reinterpret_cast<HWVar(&)[1]>(p.v)); break;
-    case 9: patch_hw<2>(g, h0, w0, reinterpret_cast<HWVar(&)[2]>(p.v)); break;
-    default: patch_hw<0>(g, h0, w0, reinterpret_cast<HWVar(&)[1]>(p.v)); break;
-  }
+__device__ __forceinline__ void patch_issue(const PatchDesc& g, const unsigned* choff, PatchHW& p, const crn_rsrc& rs,
+                                            int nplanes, int c0, int d0, float (&val)[PREG]) {
+  patch_dispatch(g.lg2, p, [&](auto u, auto& hw) __attribute__((always_inline)) {
+    patch_issue_u<decltype(u)::value>(g, choff, hw, rs, nplanes, c0, d0, val);
+  });
 }
-__device__ __forceinline__ void patch_issue(const PatchDesc& g, const unsigned* choff, const PatchHW& p,
-                                            const crn_rsrc& rs, int nplanes, int npass, int c0, int d0,
-                                            float (&val)[PREG]) {
-  switch (g.lg2) {   // wave-uniform
-    case 8: patch_issue_u<1>(g, choff, reinterpret_cast<const HWVar(&)[1]>(p.v), rs, nplanes, npass, c0, d0, val); break;
-    case 9: patch_issue_u<2>(g, choff, reinterpret_cast<const HWVar(&)[2]>(p.v), rs, nplanes, npass, c0, d0, val); break;
-    default: patch_issue_u<0>(g, choff, reinterpret_cast<const HWVar(&)[1]>(p.v), rs, nplanes, npass, c0, d0, val); break;
-  }
-}
-__device__ __forceinline__ void patch_commit(const PatchDesc& g, const unsigned* choff, const PatchHW& p,
-                                             float* ldsA, int nplanes, int npass, int c0, int d0,
-                                             const float (&val)[PREG]) {
-  switch (g.lg2) {
-    case 8: patch_commit_u<1>(g, choff, reinterpret_cast<const HWVar(&)[1]>(p.v), ldsA, nplanes, npass, c0, d0, val); break;
-    case 9: patch_commit_u<2>(g, choff, reinterpret_cast<const HWVar(&)[2]>(p.v), ldsA, nplanes, npass, c0, d0, val); break;
-    default: patch_commit_u<0>(g, choff, reinterpret_cast<const HWVar(&)[1]>(p.v), ldsA, nplanes, npass, c0, d0, val); break;
-  }
+__device__ __forceinline__ void patch_commit(const PatchDesc& g, const unsigned* choff, PatchHW& p, float* ldsA,
+                                             int nplanes, int c0, int d0, const float (&val)[PREG]) {
+  patch_dispatch(g.lg2, p, [&](auto u, auto& hw) __attribute__((always_inline)) {
+    patch_commit_u<decltype(u)::value>(g, choff, hw, ldsA, nplanes, c0, d0, val);
+  });
 }
 
 // unit u -> (channel cl, plane row pd, in-plane unit r); tile invariant, recomputed per use so that
@@ -297,7 +297,18 @@ __device__ __forceinline__ VUnit vec_unit(const PatchDesc& g) {
 }
 // PU = positions per unit: 4 (unit-stride views, float4) or 2 (stride-2 space-to-depth views: dwordx3 load,
 // elements 0 and 2 are two consecutive positions of this channel's parity; the patch origin is even, so both
-// are inside or both outside, and the load ends exactly at the second one)
+// are inside or both outside, and the load ends exactly at the second one: a fourth dword would reach past the
+// tensor's last element).  One load / store pair for the x patch and the dy tile.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int PU, typename VT>
+__device__ __forceinline__ void unit_load(VT& dst, const crn_rsrc& rs, unsigned byte_off) {
+  if constexpr (PU == 4) crn_bload4(dst, rs, byte_off); else crn_bload3(dst, rs, byte_off);
+}
+template <int PU, typename VT>
+__device__ __forceinline__ void unit_store(float* dst, const VT& v) {
+  if constexpr (PU == 4) *reinterpret_cast<f32x4*>(dst) = v;
+  else *reinterpret_cast<f32x2*>(dst) = (f32x2){v[0], v[2]};
+}
 template <int PU, int J = 0, typename VT>
 __device__ __forceinline__ void patch_issue_v(const PatchDesc& g, const unsigned* choff, const crn_rsrc& rs, int c0,
                                               int d0, int h0, int w0, VT (&val)[NVX], unsigned& inmask) {
@@ -314,7 +325,7 @@ __device__ __forceinline__ void patch_issue_v(const PatchDesc& g, const unsigned
         inmask |= 1u << J;
       }
     }
-    if constexpr (PU == 4) crn_bload4(val[J], rs, goff); else crn_bload3(val[J], rs, goff);
+    unit_load<PU>(val[J], rs, goff);
     patch_issue_v<PU, J + 1>(g, choff, rs, c0, d0, h0, w0, val, inmask);
   }
 }
@@ -325,44 +336,18 @@ __device__ __forceinline__ void patch_commit_v(const PatchDesc& g, const unsigne
     if (J * 256 < g.nunits) {                            // wave-uniform
       const VUnit t = vec_unit<J>(g);
       if (t.valid) {
-        float v[PU];
-#pragma unroll
-        for (int e = 0; e < PU; ++e) v[e] = val[J][PU == 4 ? e : 2 * e];
+        VT v = val[J];
         if (g.tr.scale && ((inmask >> J) & 1u)) {        // zero padding stays zero
           const float* tab = reinterpret_cast<const float*>(choff);
           const float sc = tab[64 + t.cl], sh = tab[128 + t.cl];
 #pragma unroll
-          for (int e = 0; e < PU; ++e) {
-            float x = v[e];
-            if (g.tr.pre_relu) x = fmaxf(x, 0.f);
-            x = x * sc + sh;
-            if (g.tr.post_relu) x = fmaxf(x, 0.f);
-            v[e] = x;
-          }
+          for (int e = 0; e < 4; e += 4 / PU) v[e] = in_transform(v[e], g.tr.pre_relu, sc, sh, g.tr.post_relu);
         }
-        float* dst = ldsA + t.cl * g.PSP + t.pd * g.plane + PU * t.r;
-        if constexpr (PU == 4) {
-          *reinterpret_cast<f32x4*>(dst) = (f32x4){v[0], v[1], v[2], v[3]};
-        } else {
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          *reinterpret_cast<f32x2*>(dst) = (f32x2){v[0], v[1]};
-        }
+        unit_store<PU>(ldsA + t.cl * g.PSP + t.pd * g.plane + PU * t.r, v);
       }
     }
     patch_commit_v<PU, J + 1>(g, choff, ldsA, val, inmask);
   }
-}
-
-template <int V>
-struct IntC { static constexpr int value = V; };
-
-// Two workgroups share a CU and run the same [stage | MFMA] cycle; started together they stay in
-// phase and fight for the same unit in every phase.  Delaying the workgroup in the odd CU slot by
-// about half a cycle puts them in anti-phase: one stages while the other owns the MFMA pipe.
-__device__ __forceinline__ void phase_skew(int sleeps) {
-  const unsigned tg = __builtin_amdgcn_s_getreg((3 << 11) | (16 << 6) | 4);   // HW_ID.TG_ID
-  if (tg & 1)
-    for (int i = 0; i < sleeps; ++i) __builtin_amdgcn_s_sleep(127);
 }
 
 // XCD-aware work-item order (cdna guide T1): workgroup b is dispatched to XCD b % 8, each XCD has
@@ -449,37 +434,34 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
   const int i16 = lane & 15, kk = lane >> 4;
   constexpr int NB = NSUB * 16;
 
-  int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int twi = tile % g.tilesW; tile /= g.tilesW;
-  const int thi = tile % g.tilesH; tile /= g.tilesH;
-  const int tdi = tile % g.tilesD; tile /= g.tilesD;
-  const int b = tile;
-  const int d0 = tdi * g.TD, h0 = thi * g.TH, w0 = twi * g.TW;
+  int b, d0, h0, w0;
+  tile_origin(g, xcd_remap(blockIdx.x, gridDim.x), b, d0, h0, w0);
   const int n0 = blockIdx.y * NB;
   const int split = blockIdx.z;
   const int cbeg = split * g.chunks_per_split;
   const int cend = min(cbeg + g.chunks_per_split, g.nchunks);
 
-  PatchDesc pdsc;
-  pdsc.x = g.x; pdsc.tr = g.tr; pdsc.pd = g.pd; pdsc.ph = g.ph; pdsc.pw = g.pw;
-  pdsc.PD = g.PD; pdsc.PH = g.PH; pdsc.PW = g.PW; pdsc.plane = g.PH * g.PW; pdsc.lg2 = g.lg2;
-  pdsc.PSP = g.PSP; pdsc.magic_PW = g.magic_PW; pdsc.magic_PD = g.magic_PD;
-  pdsc.nunits = g.nunits; pdsc.plu = g.plu; pdsc.pw4 = g.pw4; pdsc.magic_PLU = g.magic_PLU; pdsc.magic_PW4 = g.magic_PW4;
-  const int nplanes = g.CC * g.PD, npass = g.npass;
+  const PatchDesc pdsc = g;                // for the staging helpers (see PatchDesc)
+  const int nplanes = g.CC * g.PD;
   const crn_rsrc xrs = make_rsrc(g.x.base + (int64_t)b * g.x.sB);
   PatchHW phw;
   if constexpr (XV == 0) patch_prepare(pdsc, h0, w0, phw);
 
-  // lane's LDS offset of output position (sub-tile s, row i16) at tap (0,0,0)
-  int posbase[MSUB];
-  const int ri = i16 / g.mw, rj = i16 - ri * g.mw;
-#pragma unroll
-  for (int ms = 0; ms < MSUB; ++ms) {
+  // this wave's sub-tile ms and MFMA row (0..15) -> position inside the tile
+  auto tile_pos = [&](int ms, int row, int& td, int& th, int& tw) {
     int s = wave * MSUB + ms;
     const int sw = s % g.nsw; s /= g.nsw;
     const int sh = s % g.nsh; s /= g.nsh;
-    const int sd = s;
-    posbase[ms] = (sd * g.PH + sh * g.mh + ri) * g.PW + sw * g.mw + rj + kk * g.PSP + g.lead;
+    const int rr = row / g.mw, rc = row - rr * g.mw;
+    td = s; th = sh * g.mh + rr; tw = sw * g.mw + rc;
+  };
+  // lane's LDS offset of output position (sub-tile s, row i16) at tap (0,0,0)
+  int posbase[MSUB];
+#pragma unroll
+  for (int ms = 0; ms < MSUB; ++ms) {
+    int td, th, tw;
+    tile_pos(ms, i16, td, th, tw);
+    posbase[ms] = (td * g.PH + th) * g.PW + tw + kk * g.PSP + g.lead;
   }
   const int bbase = kk * g.WSP + i16;
 
@@ -541,7 +523,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
     stage_choff(g.x, g.tr, choff + (cbeg & 1) * kChTab, cbeg * g.CC, g.CC);
     __syncthreads();
     if constexpr (XV != 0) patch_issue_v<XPU>(pdsc, choff + (cbeg & 1) * kChTab, xrs, cbeg * g.CC, d0, h0, w0, pv4, inmask);
-    else patch_issue(pdsc, choff + (cbeg & 1) * kChTab, phw, xrs, nplanes, npass, cbeg * g.CC, d0, pval);
+    else patch_issue(pdsc, choff + (cbeg & 1) * kChTab, phw, xrs, nplanes, cbeg * g.CC, d0, pval);
     weights_issue(cbeg * g.CC);
   }
   for (int chunk = cbeg; chunk < cend; ++chunk) {
@@ -550,13 +532,13 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
     crn_wait_loads4(wval);
     __syncthreads();                       // previous chunk's MFMA reads are done
     if constexpr (XV != 0) { patch_commit_v<XPU>(pdsc, choff + (chunk & 1) * kChTab, ldsA, pv4, inmask); inmask = 0; }
-    else patch_commit(pdsc, choff + (chunk & 1) * kChTab, phw, ldsA, nplanes, npass, c0, d0, pval);
+    else patch_commit(pdsc, choff + (chunk & 1) * kChTab, phw, ldsA, nplanes, c0, d0, pval);
     weights_commit(c0);
     if (chunk + 1 < cend) stage_choff(g.x, g.tr, choff + ((chunk + 1) & 1) * kChTab, c0 + g.CC, g.CC);
     __syncthreads();
     if (chunk + 1 < cend) {                // next chunk's loads fly under this chunk's MFMAs
       if constexpr (XV != 0) patch_issue_v<XPU>(pdsc, choff + ((chunk + 1) & 1) * kChTab, xrs, c0 + g.CC, d0, h0, w0, pv4, inmask);
-      else patch_issue(pdsc, choff + ((chunk + 1) & 1) * kChTab, phw, xrs, nplanes, npass, c0 + g.CC, d0, pval);
+      else patch_issue(pdsc, choff + ((chunk + 1) & 1) * kChTab, phw, xrs, nplanes, c0 + g.CC, d0, pval);
       weights_issue(c0 + g.CC);
     }
 
@@ -590,19 +572,19 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
     if (n >= g.y.C) continue;
     const int64_t co = view_chan(g.y, n);
     const float bsv = (g.bias && split == 0) ? g.bias[(int64_t)b * g.bias_sB + n] : 0.f;
+    // where accumulator row `row` of sub-tile ms goes, or nullptr outside y
+    auto out_ptr = [&](int ms, int row) -> float* {
+      int td, th, tw;
+      tile_pos(ms, row, td, th, tw);
+      const int od = d0 + td, oh = h0 + th, ow = w0 + tw;
+      if (od >= g.y.D || oh >= g.y.H || ow >= g.y.W) return nullptr;
+      return yb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
+    };
 #pragma unroll
     for (int ms = 0; ms < MSUB; ++ms) {
-      int s = wave * MSUB + ms;
-      const int sw = s % g.nsw; s /= g.nsw;
-      const int sh = s % g.nsh; s /= g.nsh;
-      const int sd = s;
       if (g.vec_store) {
-        // the 4 accumulator rows of this lane are 4 consecutive W positions: one 16-B store
-        const int row0 = kk * 4;
-        const int rr = row0 / g.mw, rc = row0 - rr * g.mw;
-        const int od = d0 + sd, oh = h0 + sh * g.mh + rr, ow = w0 + sw * g.mw + rc;
-        if (od < g.y.D && oh < g.y.H && ow < g.y.W) {
-          float* dst = yb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + ow;
+        // the 4 accumulator rows of this lane are 4 consecutive W positions (unit W stride): one 16-B store
+        if (float* dst = out_ptr(ms, kk * 4)) {
           f32x4 v = acc[ms][ns] + bsv;
           if (g.mode == 1) v += *reinterpret_cast<const f32x4*>(dst);
           *reinterpret_cast<f32x4*>(dst) = v;
@@ -610,45 +592,30 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_kernel(ConvGeom g) {
         continue;
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row_ = kk * 4 + r;
-        const int rr = row_ / g.mw, rc = row_ - rr * g.mw;
-        const int od = d0 + sd, oh = h0 + sh * g.mh + rr, ow = w0 + sw * g.mw + rc;
-        if (od < g.y.D && oh < g.y.H && ow < g.y.W) {
-          float* dst = yb + co + (int64_t)od * g.y.sD + (int64_t)oh * g.y.sH + (int64_t)ow * g.y.sW;
+      for (int r = 0; r < 4; ++r)
+        if (float* dst = out_ptr(ms, kk * 4 + r)) {
           const float v = acc[ms][ns][r] + bsv;
           if (g.mode == 0 || g.mode >= 3) *dst = v;
           else if (g.mode == 1) *dst += v;
           else atomicAdd(dst, v);
         }
-      }
     }
   }
 }
 
 // ------------------------------ weight grad ---------------------------------
-struct WgradGeom {
-  crnView x, dy;
-  crnInTransform tr;
-  float* dw;
+struct WgradGeom : PatchDesc {
+  crnView dy;
+  float* dw;               // [Cin][T][Npad], the whole packed window in one launch
   int Npad;
-  int kd, kh, kw, pd, ph, pw, T;
+  int kd, kh, kw, T;
   int TD, TH, TW;
-  int PD, PH, PW, PSP;
   int POSP;                // LDS stride of one dy channel ([n][pos] layout), npos + 4
-  int lg2, npass;          // patch staging slots
   int dlg2, dnpass;        // dy staging slots (plane = TD*TH*TW positions of one channel)
   int CC;                  // channels per block (rows = CC*T <= 64*RSUB)
   int tilesD, tilesH, tilesW, ntiles;   // ntiles includes batch
   int tiles_per_split;
-  unsigned magic_PW, magic_PD, magic_T, magic_TW, magic_TH;
-  int lead;                // 16-byte staging of x (see ConvGeom)
-  int nunits, plu, pw4;
-  unsigned magic_PLU, magic_PW4;
-  int xcd;                 // XCD-aware block order
-  // tap sub-box of a larger packed window (crnTapBoxes): local tap (zd,zh,zw) is packed tap
-  // ((zd+bd0)*khf + zh+bh0)*kwf + zw+bw0 of Tfull; ncols = valid columns of this launch
-  int Tfull, khf, kwf, bd0, bh0, bw0, ncols;
+  unsigned magic_TW, magic_TH;
   int n_groups;            // crnTapBoxes of the output columns (0 = all taps)
   signed char n_box[8][6];
   // balanced split counts: output group g (fewer real taps -> cheaper tiles) gets sg[g] splits of tps[g]
@@ -658,8 +625,20 @@ struct WgradGeom {
   int tps[8], sg[8], zoff[9];
   int dnunits, np4;        // 16-byte staging of dy: NB * npos/4 units, np4 = npos/4 per channel
   unsigned magic_NP4;
-  int dbg;                 // zero (kept so that the kernel's code stays as measured): 1 = no MFMA loop, 2 = stage only the first tile
 };
+
+// Redefines every accumulator in place behind a row's MFMAs.  Without it the register allocator let the accumulators of
+// two instances (RSUB 4, float4 x and dy) change registers from one MFMA to the next, and an MFMA whose SrcC is not its
+// vDst wants wait states behind the one before where accumulating in place wants none (tools/check_mfma_hazards.py,
+// which tests/test_host_cpu.py runs on the instance objects).  The asm is empty, but its constraint can shape register
+// allocation, so wgrad_rows applies it to the RSUB 4 instances only; every other instance passes the check without it.
+template <int R, int N>
+__device__ __forceinline__ void keep_in_place(f32x4 (&acc)[R][N]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int n = 0; n < N; ++n) asm volatile("" : "+v"(acc[r][n]));
+}
 
 // One tile's MFMAs: a (td,th) row of WS = TW/4 k-steps is straight-line code.
 // NACT <= RSUB: row sub-tiles of this wave that hold real (channel, tap) rows; the others are skipped
@@ -696,6 +675,7 @@ __device__ __forceinline__ void wgrad_rows(f32x4 (&acc)[RSUB][NSUB], const float
         __builtin_amdgcn_sched_group_barrier(0x100, NACT + NSUB, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, NACT * NSUB, 0);
       }
+      if constexpr (RSUB == 4) keep_in_place(acc);
     }
 }
 
@@ -717,7 +697,6 @@ __device__ __forceinline__ DUnit dy_unit(const WgradGeom& g) {
   o.th = r1 - o.td * g.TH;
   return o;
 }
-// position pairs load 3 dwords (elements 0 and 2 are ours): a fourth would reach past the tensor's last element
 template <int PU, int NS, int J = 0, typename VT>
 __device__ __forceinline__ void dy_issue_v(const WgradGeom& g, const unsigned* dchoff, const crn_rsrc& rs, int n0,
                                            int d0, int h0, int w0, VT (&val)[NS]) {
@@ -730,7 +709,7 @@ __device__ __forceinline__ void dy_issue_v(const WgradGeom& g, const unsigned* d
         goff = (dchoff[t.n] + (unsigned)od * (unsigned)g.dy.sD + (unsigned)oh * (unsigned)g.dy.sH +
                 (unsigned)ow * (unsigned)(PU == 2 ? 2 : 1)) * 4u;
     }
-    if constexpr (PU == 4) crn_bload4(val[J], rs, goff); else crn_bload3(val[J], rs, goff);
+    unit_load<PU>(val[J], rs, goff);
     dy_issue_v<PU, NS, J + 1>(g, dchoff, rs, n0, d0, h0, w0, val);
   }
 }
@@ -739,15 +718,7 @@ __device__ __forceinline__ void dy_commit_v(const WgradGeom& g, float* ldsB, con
   if constexpr (J < NS) {
     if (J * 256 < g.dnunits) {
       const DUnit t = dy_unit<J, PU>(g);
-      if (t.valid) {
-        float* dst = ldsB + t.n * g.POSP + t.pos;
-        if constexpr (PU == 4) {
-          *reinterpret_cast<f32x4*>(dst) = val[J];
-        } else {
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          *reinterpret_cast<f32x2*>(dst) = (f32x2){val[J][0], val[J][2]};
-        }
-      }
+      if (t.valid) unit_store<PU>(ldsB + t.n * g.POSP + t.pos, val[J]);
     }
     dy_commit_v<PU, NS, J + 1>(g, ldsB, val);
   }
@@ -766,8 +737,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
   // XCD-aware order: the channel blocks that reduce over the same tiles (same split) read the same
   // dy tiles -> keep them, and neighbouring splits, on one XCD (one L2)
   const int nbx = gridDim.x, nby = gridDim.y;
-  const int lin0 = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
-  const int lin = g.xcd ? xcd_remap(lin0, nbx * nby * gridDim.z) : lin0;
+  const int lin = xcd_remap(blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z), nbx * nby * gridDim.z);
   const int c0 = (lin % nbx) * g.CC;
   int n0 = ((lin / nbx) % nby) * NB;
   int split = lin / (nbx * nby);
@@ -791,24 +761,26 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
   // row sub-tile s = rs*4 + wave: the real rows are spread evenly over the four wavefronts
   const int nact = max(0, ((nrows + 15) / 16 - wave + 3) / 4);
 
-  PatchDesc pdsc;
-  pdsc.x = g.x; pdsc.tr = g.tr; pdsc.pd = g.pd; pdsc.ph = g.ph; pdsc.pw = g.pw;
-  pdsc.PD = g.PD; pdsc.PH = g.PH; pdsc.PW = g.PW; pdsc.plane = g.PH * g.PW; pdsc.lg2 = g.lg2;
-  pdsc.PSP = g.PSP; pdsc.magic_PW = g.magic_PW; pdsc.magic_PD = g.magic_PD;
-  pdsc.nunits = g.nunits; pdsc.plu = g.plu; pdsc.pw4 = g.pw4; pdsc.magic_PLU = g.magic_PLU; pdsc.magic_PW4 = g.magic_PW4;
-  const int nplanes = g.CC * g.PD, npass = g.npass;
+  const PatchDesc pdsc = g;                // for the staging helpers (see PatchDesc)
+  const int nplanes = g.CC * g.PD;
 
+  // row of the block -> (local channel, tap of the window)
+  auto row_tap = [&](int row, int& cl, int& zd, int& zh, int& zw) {
+    cl = row / max(Tb, 1);
+    int t = row - cl * Tb;
+    zw = t % max(bkw, 1) + tb.w0; t /= max(bkw, 1);
+    zh = t % max(bkh, 1) + tb.h0; t /= max(bkh, 1);
+    zd = t + tb.d0;
+  };
   // row (c_local, tap) -> LDS offset inside the patch
   int rowbase[RSUB];
 #pragma unroll
   for (int rs = 0; rs < RSUB; ++rs) {
     int row = (rs * 4 + wave) * 16 + i16;
     if (row >= nrows) row = 0;                       // never stored
-    const int cl = row / max(Tb, 1);
-    int t = row - cl * Tb;
-    const int zw = t % max(bkw, 1); t /= max(bkw, 1);
-    const int zh = t % max(bkh, 1); t /= max(bkh, 1);
-    rowbase[rs] = cl * g.PSP + ((t + tb.d0) * g.PH + zh + tb.h0) * g.PW + zw + tb.w0 + kk + g.lead;
+    int cl, zd, zh, zw;
+    row_tap(row, cl, zd, zh, zw);
+    rowbase[rs] = cl * g.PSP + (zd * g.PH + zh) * g.PW + zw + kk + g.lead;
   }
 
   f32x4 acc[RSUB][NSUB];
@@ -829,13 +801,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
   using DVT = typename std::conditional<DV == 2, f32x3, f32x4>::type;
   DVT dv4[DV ? DNS : 1];
 
-  auto tile_origin = [&](int tl, int& b, int& d0, int& h0, int& w0) {
-    int tile = tl;
-    const int twi = tile % g.tilesW; tile /= g.tilesW;
-    const int thi = tile % g.tilesH; tile /= g.tilesH;
-    const int tdi = tile % g.tilesD; tile /= g.tilesD;
-    b = tile; d0 = tdi * g.TD; h0 = thi * g.TH; w0 = twi * g.TW;
-  };
   // scalar dy staging: planes = channels nl, in-plane index r = position (td,th,tw); lanes run
   // along w: coalesced global reads, consecutive LDS addresses.  Per-thread position variants
   // (npos <= 512 -> at most 2) are hoisted per tile.
@@ -887,19 +852,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
       if (q < NB && dhw0.r >= 0) ldsB[q * g.POSP + dhw0.r] = v;
     }
   };
-#define CRN_DY_8(OP, A, B0)                                                                        \
-  if (g.dnpass > B0) {                                                                             \
-    OP(A IntC<B0 + 0>{}, dval[B0 + 0]); OP(A IntC<B0 + 1>{}, dval[B0 + 1]);                        \
-    OP(A IntC<B0 + 2>{}, dval[B0 + 2]); OP(A IntC<B0 + 3>{}, dval[B0 + 3]);                        \
-    OP(A IntC<B0 + 4>{}, dval[B0 + 4]); OP(A IntC<B0 + 5>{}, dval[B0 + 5]);                        \
-    OP(A IntC<B0 + 6>{}, dval[B0 + 6]); OP(A IntC<B0 + 7>{}, dval[B0 + 7]);                        \
-  }
-#define CRN_DY_8U(OP, A, B0)                                                                       \
-  OP(A IntC<B0 + 0>{}, dval[B0 + 0]); OP(A IntC<B0 + 1>{}, dval[B0 + 1]);                          \
-  OP(A IntC<B0 + 2>{}, dval[B0 + 2]); OP(A IntC<B0 + 3>{}, dval[B0 + 3]);                          \
-  OP(A IntC<B0 + 4>{}, dval[B0 + 4]); OP(A IntC<B0 + 5>{}, dval[B0 + 5]);                          \
-  OP(A IntC<B0 + 6>{}, dval[B0 + 6]); OP(A IntC<B0 + 7>{}, dval[B0 + 7]);
-#define CRN_COMMA ,
   auto stage_issue = [&](int b, int d0, int h0, int w0) {
     const crn_rsrc xrs = make_rsrc(g.x.base + (int64_t)b * g.x.sB);
     const crn_rsrc drs = make_rsrc(g.dy.base + (int64_t)b * g.dy.sB);
@@ -908,14 +860,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
     } else {
       PatchHW phw;
       patch_prepare(pdsc, h0, w0, phw);
-      patch_issue(pdsc, choff, phw, xrs, nplanes, npass, c0, d0, pval);
+      patch_issue(pdsc, choff, phw, xrs, nplanes, c0, d0, pval);
     }
     if constexpr (DV != 0) {
       dy_issue_v<DPU, DNS>(g, choff + kChTab, drs, n0, d0, h0, w0, dv4);
     } else {
       dy_prepare(d0, h0, w0);
-      CRN_DY_8U(dy_issue, drs CRN_COMMA, 0) CRN_DY_8U(dy_issue, drs CRN_COMMA, 8)
-      CRN_DY_8U(dy_issue, drs CRN_COMMA, 16) CRN_DY_8U(dy_issue, drs CRN_COMMA, 24)
+      for_slots<0, DREG>(dval, [&](auto jc, float& v) __attribute__((always_inline)) { dy_issue(drs, jc, v); });
     }
   };
   auto stage_commit = [&](int d0, int h0, int w0) {
@@ -925,13 +876,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
     } else {
       PatchHW phw;
       patch_prepare(pdsc, h0, w0, phw);
-      patch_commit(pdsc, choff, phw, ldsA, nplanes, npass, c0, d0, pval);
+      patch_commit(pdsc, choff, phw, ldsA, nplanes, c0, d0, pval);
     }
     if constexpr (DV != 0) {
       dy_commit_v<DPU, DNS>(g, ldsB, dv4);
     } else {
       dy_prepare(d0, h0, w0);
-      CRN_DY_8(dy_commit, , 0) CRN_DY_8(dy_commit, , 8) CRN_DY_8(dy_commit, , 16) CRN_DY_8(dy_commit, , 24)
+      for_slot_groups(g.dnpass, dval, dy_commit);
     }
   };
 
@@ -943,22 +894,21 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
   }
   __syncthreads();
   if (tbeg < tend) {
-    tile_origin(tbeg, cb, cd0, ch0, cw0);
+    tile_origin(g, tbeg, cb, cd0, ch0, cw0);
     stage_issue(cb, cd0, ch0, cw0);
   }
   for (int tl = tbeg; tl < tend; ++tl) {
     if constexpr (XV) crn_wait_loads4n(pv4); else crn_wait_loads(pval);
     if constexpr (DV != 0) crn_wait_loads4n(dv4); else crn_wait_loads(dval);
     __syncthreads();
-    if (g.dbg != 2 || tl == tbeg) stage_commit(cd0, ch0, cw0);
+    stage_commit(cd0, ch0, cw0);
     __syncthreads();
-    if (tl + 1 < tend && g.dbg != 2) {
-      tile_origin(tl + 1, cb, cd0, ch0, cw0);
+    if (tl + 1 < tend) {
+      tile_origin(g, tl + 1, cb, cd0, ch0, cw0);
       stage_issue(cb, cd0, ch0, cw0);
     }
     // reduction over the tile's positions (wgrad_rows; the switches stay outside the loops)
-    if (g.dbg != 1) {
-      const int bbase = i16 * g.POSP + kk;
+    const int bbase = i16 * g.POSP + kk;
 #define CRN_WG_WS(NACT)                                                                           \
   switch (g.TW >> 2) {                                                                            \
     case 1: wgrad_rows<1, RSUB, NSUB, NACT>(acc, ldsA, ldsB, rowbase, bbase, g); break;           \
@@ -966,20 +916,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
     case 3: wgrad_rows<3, RSUB, NSUB, NACT>(acc, ldsA, ldsB, rowbase, bbase, g); break;           \
     default: wgrad_rows<4, RSUB, NSUB, NACT>(acc, ldsA, ldsB, rowbase, bbase, g); break;          \
   }
-      if constexpr (RSUB >= 4) {
-        if (nact * 8 <= RSUB * 4) { CRN_WG_WS((RSUB * 4) / 8) }
-        else if (nact * 8 <= RSUB * 5) { CRN_WG_WS((RSUB * 5 + 7) / 8) }
-        else if (nact * 8 <= RSUB * 6) { CRN_WG_WS((RSUB * 6) / 8) }
-        else { CRN_WG_WS(RSUB) }
-      } else {
-        CRN_WG_WS(RSUB)
-      }
-#undef CRN_WG_WS
+    if constexpr (RSUB >= 4) {
+      if (nact * 8 <= RSUB * 4) { CRN_WG_WS((RSUB * 4) / 8) }
+      else if (nact * 8 <= RSUB * 5) { CRN_WG_WS((RSUB * 5 + 7) / 8) }
+      else if (nact * 8 <= RSUB * 6) { CRN_WG_WS((RSUB * 6) / 8) }
+      else { CRN_WG_WS(RSUB) }
+    } else {
+      CRN_WG_WS(RSUB)
     }
+#undef CRN_WG_WS
   }
-#undef CRN_DY_8
-#undef CRN_DY_8U
-#undef CRN_COMMA
 
   // D row = kk*4 + r -> weight row (c_local, tap); col = i16 -> n
 #pragma unroll
@@ -988,16 +934,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradGeom g) {
     for (int r = 0; r < 4; ++r) {
       const int row_ = (rs * 4 + wave) * 16 + kk * 4 + r;
       if (row_ >= nrows) continue;
-      const int cl = row_ / max(Tb, 1);
-      int tl = row_ - cl * Tb;
-      const int zw = tl % max(bkw, 1); tl /= max(bkw, 1);
-      const int zh = tl % max(bkh, 1); tl /= max(bkh, 1);
-      const int64_t prow = (int64_t)(c0 + cl) * g.Tfull +
-                           ((tl + tb.d0 + g.bd0) * g.khf + zh + tb.h0 + g.bh0) * g.kwf + zw + tb.w0 + g.bw0;
+      int cl, zd, zh, zw;
+      row_tap(row_, cl, zd, zh, zw);
+      const int64_t prow = (int64_t)(c0 + cl) * g.T + (zd * g.kh + zh) * g.kw + zw;
 #pragma unroll
       for (int ns = 0; ns < NSUB; ++ns) {
         const int n = n0 + ns * 16 + i16;
-        if (n < g.ncols)
+        if (n < g.Npad)
           atomicAdd(g.dw + prow * g.Npad + n, acc[rs][ns][r]);
       }
     }

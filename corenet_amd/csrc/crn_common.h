@@ -92,6 +92,15 @@ __device__ __forceinline__ void crn_kernarg_touch(const T& g) {
   asm volatile("" ::"s"(p[sizeof(T) / 4 - 1]));
 }
 
+// The fused in-transform of one element (BatchRenorm-apply and the ReLUs around it): max, *, +, max in this order, never
+// contracted.  Padding and channels past C are not x: the callers keep them zero.
+__device__ __forceinline__ float in_transform(float a, int pre_relu, float scale, float shift, int post_relu) {
+  if (pre_relu) a = fmaxf(a, 0.f);
+  a = a * scale + shift;
+  if (post_relu) a = fmaxf(a, 0.f);
+  return a;
+}
+
 // Deterministic mode (env CRN_DETERMINISTIC=1 or crn_set_deterministic(1)): every floating-point sum of the library is
 // taken in an order that does not depend on how workgroups are scheduled, so two runs from the same state are
 // bit-identical (debugging aid: a loss regression can be told from atomic-order noise).  Weight gradients give each
