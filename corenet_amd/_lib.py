@@ -224,6 +224,20 @@ _SIGS = {
     "crn_voxel_topology_tiles": [vp],
     "crn_voxel_topology": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "crn_voxel_topology_cpu": [vp, C.POINTER(i64), i32, i32, i32, i32, i32, i32, i32, vp, vp, i32],
+    "crn_mesh_tiles": [vp],
+    "crn_mesh_corner_count": [vp, i64, vp, vp, i32, i64, vp, vp, vp],
+    "crn_mesh_corner_lists": [vp, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "crn_mesh_neighbours": [vp, vp, vp, i64, vp, vp],
+    "crn_mesh_smooth_step": [vp, vp, vp, vp, vp, f32, i64, vp],
+    "crn_mesh_face_normals": [vp, vp, i64, vp, vp, i32, i64, vp, vp],
+    "crn_mesh_vertex_normals": [vp, vp, i64, vp, i32, i64, vp, vp, vp, vp],
+    "crn_mesh_cluster_build": [vp, i64, vp, i64, vp, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp, vp],
+    "crn_mesh_cluster_emit": [vp, i64, vp, i64, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp],
+    "crn_mesh_topology_cpu": [vp, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp],
+    "crn_mesh_smooth_step_cpu": [vp, vp, vp, vp, vp, f32, i64],
+    "crn_mesh_face_normals_cpu": [vp, vp, i64, vp, vp, i32, i64, vp],
+    "crn_mesh_vertex_normals_cpu": [vp, vp, i64, vp, i32, i64, vp, vp, vp],
+    "crn_mesh_cluster_cpu": [vp, i64, vp, i64, vp, vp, i32, f32, vp, vp, vp, vp, vp],
     "crn_voxelize_mesh": [vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "crn_batch_renorm_eval_affine": [vp, vp, vp, i32, f32, vp, vp, vp],
     "crn_transform_meshes": [vp, vp, i32, vp, i32, vp, vp],

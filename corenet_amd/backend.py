@@ -661,6 +661,47 @@ class HipBackend:
     self.lib.crn_voxel_topology(ptr(grid), st, _DTYPE_CODE[grid.dtype], N, D, H, W, int(num_labels), int(bool(mask)), ptr(table),
                                 ptr(bad), _lib.stream())
 
+  # -- mesh clean-up (corenet_amd.mesh_ops); every call is queued on the current stream -----------------
+  def mesh_corner_count(self, faces: t.Tensor, voff: t.Tensor, foff: t.Tensor, V: int, deg: t.Tensor, bad: t.Tensor):
+    """deg (int32 [V]) <- face corners per vertex, bad (int64 [1]) <- bad ids; voff / foff: int64 [N + 1] on the device."""
+    self.lib.crn_mesh_corner_count(ptr(faces), faces.shape[0], ptr(voff), ptr(foff), voff.numel() - 1, V, ptr(deg), ptr(bad), _lib.stream())
+
+  def mesh_corner_lists(self, faces: t.Tensor, voff: t.Tensor, foff: t.Tensor, V: int, vf_offsets: t.Tensor, cursor: t.Tensor,
+                        vf_tmp: t.Tensor, vf_corners: t.Tensor, cand_tmp: t.Tensor, cand: t.Tensor, vvdeg: t.Tensor, irregular: t.Tensor):
+    """vf_corners, cand (sorted per vertex), vvdeg, irregular (uint8) <- the incidence lists of crn_mesh_corner_lists."""
+    self.lib.crn_mesh_corner_lists(ptr(faces), faces.shape[0], ptr(voff), ptr(foff), voff.numel() - 1, V, ptr(vf_offsets), ptr(cursor),
+                                   ptr(vf_tmp), ptr(vf_corners), ptr(cand_tmp), ptr(cand), ptr(vvdeg), ptr(irregular), _lib.stream())
+
+  def mesh_neighbours(self, cand: t.Tensor, vf_offsets: t.Tensor, vv_offsets: t.Tensor, V: int, vv: t.Tensor):
+    self.lib.crn_mesh_neighbours(ptr(cand), ptr(vf_offsets), ptr(vv_offsets), V, ptr(vv), _lib.stream())
+
+  def mesh_smooth_step(self, vin: t.Tensor, vout: t.Tensor, vv_offsets: t.Tensor, vv: t.Tensor, fixed: Optional[t.Tensor], factor: float):
+    """vout <- one smoothing step of vin (f32 [V, 3], contiguous, another tensor) with `factor`; fixed: uint8 [V] or None."""
+    self.lib.crn_mesh_smooth_step(ptr(vin), ptr(vout), ptr(vv_offsets), ptr(vv), ptr(fixed), float(factor), vin.shape[0], _lib.stream())
+
+  def mesh_face_normals(self, vertices: t.Tensor, faces: t.Tensor, voff: t.Tensor, foff: t.Tensor, out: t.Tensor):
+    self.lib.crn_mesh_face_normals(ptr(vertices), ptr(faces), faces.shape[0], ptr(voff), ptr(foff), voff.numel() - 1, vertices.shape[0],
+                                   ptr(out), _lib.stream())
+
+  def mesh_vertex_normals(self, vertices: t.Tensor, faces: t.Tensor, voff: t.Tensor, vf_offsets: t.Tensor, vf_corners: t.Tensor,
+                          out: t.Tensor):
+    self.lib.crn_mesh_vertex_normals(ptr(vertices), ptr(faces), faces.shape[0], ptr(voff), voff.numel() - 1, vertices.shape[0],
+                                     ptr(vf_offsets), ptr(vf_corners), ptr(out), _lib.stream())
+
+  def mesh_cluster_build(self, vertices: t.Tensor, faces: t.Tensor, voff: t.Tensor, foff: t.Tensor, cell: float, keys: t.Tensor,
+                         leader: t.Tensor, log2: int, slot_of: t.Tensor, vflag: t.Tensor, fkeep: t.Tensor, bad: t.Tensor):
+    self.lib.crn_mesh_cluster_build(ptr(vertices), vertices.shape[0], ptr(faces), faces.shape[0], ptr(voff), ptr(foff), voff.numel() - 1,
+                                    float(cell), ptr(keys), ptr(leader), int(log2), ptr(slot_of), ptr(vflag), ptr(fkeep), ptr(bad),
+                                    _lib.stream())
+
+  def mesh_cluster_emit(self, vertices: t.Tensor, faces: t.Tensor, voff: t.Tensor, foff: t.Tensor, cell: float, leader: t.Tensor,
+                        slot_of: t.Tensor, vflag: t.Tensor, vcs: t.Tensor, fkeep: t.Tensor, fcs: t.Tensor, new_voff: t.Tensor,
+                        vertex_map: t.Tensor, sums: t.Tensor, cluster_size: t.Tensor, new_vertices: t.Tensor, new_faces: t.Tensor):
+    self.lib.crn_mesh_cluster_emit(ptr(vertices), vertices.shape[0], ptr(faces), faces.shape[0], ptr(voff), ptr(foff), voff.numel() - 1,
+                                   float(cell), ptr(leader), ptr(slot_of), ptr(vflag), ptr(vcs), ptr(fkeep), ptr(fcs), ptr(new_voff),
+                                   new_vertices.shape[0], new_faces.shape[0], ptr(vertex_map), ptr(sums), ptr(cluster_size),
+                                   ptr(new_vertices), ptr(new_faces), _lib.stream())
+
   # -- surface points and nearest neighbours (corenet_amd.mesh_metrics) -------------------------------
   def sample_surface(self, triangles: t.Tensor, tri_offsets: t.Tensor, num_samples: int, seed: int, points: t.Tensor,
                      tri_index: t.Tensor, valid: t.Tensor):

@@ -17,7 +17,7 @@ SOURCES = ["conv_igemm.hip", "splitk.hip", "conv_bf3.hip", "conv_e2d.hip", "batc
            "eval_labels.hip", "eval_labels_cpu.cpp", "voxel_components.hip", "voxel_components_cpu.cpp",
            "voxel_distance.hip", "voxel_distance_cpu.cpp", "voxel_visibility.hip", "voxel_visibility_cpu.cpp",
            "voxel_overlap.hip", "voxel_overlap_cpu.cpp", "eval_scores.hip", "eval_scores_cpu.cpp",
-           "voxel_topology.hip", "voxel_topology_cpu.cpp"]
+           "voxel_topology.hip", "voxel_topology_cpu.cpp", "mesh_ops.hip", "mesh_ops_cpu.cpp"]
 # conv engine tile configurations (conv_kernels.h CRN_FWD_CONFIGS / CRN_WG_CONFIGS): one object each
 CONV_CONFIGS = [(8, 1), (4, 2), (4, 1), (2, 4), (2, 2), (2, 1), (1, 4), (1, 2), (1, 1)]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
@@ -37,7 +37,7 @@ def _stale(obj, src):
           os.path.join(CSRC, "eval_labels_common.h"), os.path.join(CSRC, "voxel_components_common.h"),
           os.path.join(CSRC, "voxel_distance_common.h"), os.path.join(CSRC, "voxel_visibility_common.h"),
           os.path.join(CSRC, "voxel_overlap_common.h"), os.path.join(CSRC, "eval_scores_common.h"),
-          os.path.join(CSRC, "voxel_topology_common.h"),
+          os.path.join(CSRC, "voxel_topology_common.h"), os.path.join(CSRC, "mesh_ops_common.h"),
           os.path.join(HERE, "..", "include", "corenet_hip.h")]
   return any(os.path.getmtime(d) > m for d in deps)
 

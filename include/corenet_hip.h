@@ -1121,6 +1121,110 @@ int crn_voxel_topology(const void* grid, const int64_t* strides, int dtype, int 
 int crn_voxel_topology_cpu(const void* grid, const int64_t* strides, int dtype, int N, int D, int H, int W, int num_labels,
                            int mask, int64_t* table, int64_t* bad, int num_threads);
 
+/* ---------------- mesh clean-up: incidence tables, smoothing, normals, clustering (corenet_amd.mesh_ops) --------------
+ * Contract: DESIGN section 24 and the docstring of corenet_amd/mesh_ops.py.  A batch of N indexed meshes: vertices f32
+ * [V][3], faces int32 [F][3] with vertex ids LOCAL to their object, and the ascending offsets voff / foff int64 [N + 1]
+ * (voff[0] = foff[0] = 0): object n owns the vertices voff[n] .. voff[n + 1] - 1 and the faces foff[n] .. foff[n + 1] - 1.
+ * "Global" ids have voff[n] added.  V <= 2^31 - 1 and 3 F <= 2^31 - 1.  All float arithmetic is float32 with IEEE + - * /
+ * sqrtf in the order written here, never contracted; the positions of the clustering are float64.  Every GPU entry
+ * queues its launches on stream s and does not wait for the GPU; the prefix sums between the entries are the caller's.
+ * Integer atomics, per-list sorts and sums in list order only: results are the same from run to run and equal to the host
+ * twin's bit for bit; nothing depends on crn_set_deterministic.  All pointers are device memory for the GPU entries and
+ * host memory for the *_cpu twins.
+ *
+ * A bad id is a face id < 0 or >= its object's vertex count (or a face outside foff[N], or a global id >= V).  A face
+ * with a bad id is in no list, has a zero normal and is never kept; the count of bad ids is what the caller raises on.
+ *
+ * Incidence (mesh_topology):
+ *   crn_mesh_corner_count   deg int32 [V] <- the number of face corners that name each vertex (a face that names a vertex
+ *                           twice counts twice), bad int64 [1] <- the number of bad ids.  vf_offsets is the caller's
+ *                           exclusive prefix sum of deg, int64 [V + 1].
+ *   crn_mesh_corner_lists   vf_corners int32 [3 F] <- per vertex its corners 3 * global_face + corner, ascending;
+ *                           cand int32 [6 F] <- per vertex the sorted list of 2 w + d over its corners: w the global id of
+ *                           the next (d = 0, the edge v -> w) and of the previous (d = 1, the edge w -> v) vertex of the
+ *                           corner's face; vvdeg int32 [V] <- the number of distinct w != v; irregular uint8 [V] <- 1 where
+ *                           some w has not exactly one entry of either direction, or w == v occurs (a self edge is never
+ *                           regular).  cursor int32 [V], vf_tmp int32 [3 F], cand_tmp int32 [6 F]: scratch.
+ *   crn_mesh_neighbours     vv_neighbours <- per vertex the distinct w != v of cand, ascending, at vv_offsets (the caller's
+ *                           exclusive prefix sum of vvdeg, int64 [V + 1]).
+ * Sorting: a list of up to CRN_MESH_SORT_LANE keys is sorted by one lane; a longer one by its workgroup of
+ * CRN_MESH_THREADS threads, rank by counting through LDS tiles of CRN_MESH_SORT_TILE keys (quadratic in the list).
+ *
+ * crn_mesh_smooth_step: vout <- one step with factor f.  A vertex with k >= 1 neighbours and fixed[v] == 0 (fixed: uint8
+ * [V] or NULL) gets, per component, s = ((n0 + n1) + n2) + ... over its neighbours in list order, m = s / float(k),
+ * v' = v + f * (m - v); every other vertex is copied.  vin != vout.
+ *
+ * crn_mesh_face_normals: out f32 [F][3] <- (b - a) x (c - a) of the corners 0, 1, 2; component x is
+ * (u.y * w.z) - (u.z * w.y) with u = b - a, w = c - a, y and z cyclically.
+ * crn_mesh_vertex_normals: out f32 [V][3] <- per vertex 0 + the cross products of the faces of its corner list, in list
+ * order (once per corner), divided by sqrtf((x * x + y * y) + z * z); a zero length gives (0, 0, 0).
+ *
+ * Clustering (cluster_decimate) on a lattice of pitch cell (> 0): per axis x = v / cell, c = floorf(x),
+ * u = (int64)((x - c) * 2^20); a vertex that is not finite or has a c outside [CRN_MESH_CELL_MIN, CRN_MESH_CELL_MAX] is
+ * bad.  A cluster is (object, c_x, c_y, c_z); its leader is its lowest vertex id; new vertices are ordered by leader.
+ *   crn_mesh_cluster_build  table_keys int64 [2^table_log2] / table_leader int32 [2^table_log2]: scratch, 2^table_log2 >=
+ *                           max(2, 2 V); slot_of int32 [V]: scratch; vflag int32 [V] <- 1 for leaders; fkeep int32 [F] <- 1
+ *                           for faces whose three vertices lie in three clusters; bad int64 [1] <- bad vertices + bad ids.
+ *                           N <= CRN_MESH_MAX_OBJECTS, V <= CRN_MESH_CLUSTER_MAX_VERTICES.
+ *   crn_mesh_cluster_emit   vcs / fcs int64 [V] / [F]: the caller's INCLUSIVE prefix sums of vflag / fkeep; new_voff int64
+ *                           [N + 1]: the first new vertex of every object; vertex_map int32 [V] <- old -> new global id;
+ *                           cluster_size int32 [new_V]; sums int64 [new_V][3]: scratch, the exact sums of u;
+ *                           new_vertices f32 [new_V][3] <- per axis
+ *                           float((double(c) + (double(sum u) / double(count)) * 2^-20) * double(cell));
+ *                           new_faces int32 [new_F][3] <- the kept faces in order, ids local to their object.
+ * No slot of the table shows in any output.
+ *
+ * CRN_EINVAL: a size outside the limits, a missing pointer, cell <= 0 or NaN, a table that is too small.
+ * crn_mesh_tiles writes (CRN_MESH_THREADS, CRN_MESH_SORT_LANE, CRN_MESH_SORT_TILE, CRN_MESH_CELL_MIN, CRN_MESH_CELL_MAX,
+ * CRN_MESH_MAX_OBJECTS, CRN_MESH_CLUSTER_MAX_VERTICES).
+ *
+ * Host twins (same contract, identical results; plain sequential loops):
+ *   crn_mesh_topology_cpu   all tables of mesh_topology in one call; counts int64 [2] <- (E, bad).  With vv_neighbours
+ *                           NULL only the counts, vf_* , vv_offsets and irregular are written (the sizing call).
+ *   crn_mesh_cluster_cpu    counts int64 [2 N + 1] <- new vertex counts, new face counts, bad; vertex_map always; the
+ *                           other outputs when new_vertices is not NULL (the second call, sized by the first).      */
+#define CRN_MESH_THREADS 256
+#define CRN_MESH_SORT_LANE 32
+#define CRN_MESH_SORT_TILE 2048
+#define CRN_MESH_CELL_MIN (-32768)
+#define CRN_MESH_CELL_MAX 32767
+#define CRN_MESH_MAX_OBJECTS 65534
+#define CRN_MESH_CLUSTER_MAX_VERTICES (1 << 30)
+int crn_mesh_tiles(int32_t* out7);
+int crn_mesh_corner_count(const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff, int N, int64_t V, int32_t* deg,
+                          int64_t* bad, crnStream s);
+int crn_mesh_corner_lists(const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff, int N, int64_t V,
+                          const int64_t* vf_offsets, int32_t* cursor, int32_t* vf_tmp, int32_t* vf_corners, int32_t* cand_tmp,
+                          int32_t* cand, int32_t* vvdeg, uint8_t* irregular, crnStream s);
+int crn_mesh_neighbours(const int32_t* cand, const int64_t* vf_offsets, const int64_t* vv_offsets, int64_t V, int32_t* vv_neighbours,
+                        crnStream s);
+int crn_mesh_smooth_step(const float* vin, float* vout, const int64_t* vv_offsets, const int32_t* vv_neighbours, const uint8_t* fixed,
+                         float factor, int64_t V, crnStream s);
+int crn_mesh_face_normals(const float* vertices, const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff, int N,
+                          int64_t V, float* out, crnStream s);
+int crn_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t F, const int64_t* voff, int N, int64_t V,
+                            const int64_t* vf_offsets, const int32_t* vf_corners, float* out, crnStream s);
+int crn_mesh_cluster_build(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff,
+                           int N, float cell, int64_t* table_keys, int32_t* table_leader, int table_log2, int32_t* slot_of,
+                           int32_t* vflag, int32_t* fkeep, int64_t* bad, crnStream s);
+int crn_mesh_cluster_emit(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff,
+                          int N, float cell, const int32_t* table_leader, const int32_t* slot_of, const int32_t* vflag,
+                          const int64_t* vcs, const int32_t* fkeep, const int64_t* fcs, const int64_t* new_voff, int64_t new_V,
+                          int64_t new_F, int32_t* vertex_map, int64_t* sums, int32_t* cluster_size, float* new_vertices,
+                          int32_t* new_faces, crnStream s);
+int crn_mesh_topology_cpu(const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff, int N, int64_t V,
+                          int64_t* vf_offsets, int32_t* vf_corners, int64_t* vv_offsets, int32_t* vv_neighbours, uint8_t* irregular,
+                          int64_t* counts);
+int crn_mesh_smooth_step_cpu(const float* vin, float* vout, const int64_t* vv_offsets, const int32_t* vv_neighbours,
+                             const uint8_t* fixed, float factor, int64_t V);
+int crn_mesh_face_normals_cpu(const float* vertices, const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff, int N,
+                              int64_t V, float* out);
+int crn_mesh_vertex_normals_cpu(const float* vertices, const int32_t* faces, int64_t F, const int64_t* voff, int N, int64_t V,
+                                const int64_t* vf_offsets, const int32_t* vf_corners, float* out);
+int crn_mesh_cluster_cpu(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int64_t* voff, const int64_t* foff,
+                         int N, float cell, int32_t* vertex_map, int64_t* counts, float* new_vertices, int32_t* cluster_size,
+                         int32_t* new_faces);
+
 /* voxelize_mesh (geometry/voxelization.py:32-164 + shaders/voxelize.{geom,frag}):
  * triangles [T][3][3] (view space), tri_mesh [T] mesh index per triangle
  * (misc_util.dynamic_tile), view2voxel [M][16]; grid [M][D][H][W] (or the
